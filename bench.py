@@ -405,6 +405,9 @@ def run_exact(args) -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"keys": keys_dev.cpu().numpy(), "distances": dist_dev.cpu().numpy(),
+                                         "counts": counts_dev.cpu().numpy()})
     if rank == 0:
         operations = 2.0 * args.queries * args.n * args.dim
         kernel_s = float(np.mean(kernel_ms)) / 1e3
@@ -537,6 +540,30 @@ def timed_steps(step, steps: int, world: int, device) -> float:
     return elapsed
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """`--dump-outputs DIR`: what the last timed step handed its caller, one DIR/<name>.npy per array, so that two builds can be
+    compared output for output on the same seeded inputs. Distances stay float32; keys and counters become float64 (exact: integers
+    below 2**53). Rows are queries; above DUMP_LIMIT_BYTES in all, every array keeps the same seeded sample of rows, whose indices
+    are DIR/rows.npy."""
+    out = {}
+    for name, value in arrays.items():
+        value = np.asarray(value)
+        out[name] = value.astype(np.float32 if value.dtype == np.float32 else np.float64)
+    rows = len(next(iter(out.values())))
+    row_bytes = sum(value.nbytes for value in out.values()) / max(1, rows)
+    if rows * row_bytes > DUMP_LIMIT_BYTES:
+        kept = np.sort(np.random.default_rng(0).choice(rows, size=int(DUMP_LIMIT_BYTES // (row_bytes + 8)), replace=False))
+        out = {name: value[kept] for name, value in out.items()}
+        out["rows"] = kept.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, value in out.items():
+        np.save(os.path.join(directory, f"{name}.npy"), value)
+    log(f"[bench] outputs of the last timed step written to {directory}: " + ", ".join(f"{name} {list(value.shape)}" for name, value in out.items()))
+
+
 def rehearse_on_cpu(args) -> None:
     """BENCH_REHEARSAL=cpu — the launcher path of `bench.py --gpus N --sharded` WITHOUT a GPU (tests/test_bench_helpers.py runs it with
     two ranks every round): torch.distributed.run → `join_ranks` (gloo) → the expansion chosen by rank 0 and followed by all → warm-up →
@@ -580,6 +607,8 @@ def rehearse_on_cpu(args) -> None:
     for _ in range(args.warmup):
         search_step(expansion)
     elapsed = timed_steps(lambda i: search_step(expansion), args.steps, world, device)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"keys": keys, "distances": distances, "counts": counts})
     if rank == 0:
         flush_native_stdio()
         print(json.dumps({
@@ -600,6 +629,9 @@ def main() -> None:
     parser.add_argument("--gpus", type=int, default=1)
     parser.add_argument("--steps", type=int, default=5)
     parser.add_argument("--warmup", type=int, default=1)
+    parser.add_argument("--dump-outputs", default=None, metavar="DIR",
+                        help="after the timed steps, write what the last one returned (rank 0: keys, distances, counts, traversal "
+                             "counters) as DIR/<name>.npy in float32 / float64; a seeded sample of rows above 64 MB in all")
     # (`--n` would collide with the launcher's own abbreviations — torch.distributed.run reads "--n" as an ambiguous prefix of
     # --nnodes / --nproc-per-node even behind the script name — hence the long name; `--n` stays as an alias for direct runs)
     parser.add_argument("--vectors", "--n", dest="n", type=int, default=int(os.environ.get("BENCH_N", 10_000_000)),
@@ -656,6 +688,8 @@ def main() -> None:
     parser.add_argument("--config", default=None, choices=sorted(PRESETS),
                         help="one of BASELINE.json's configurations by name: " + "; ".join(f"{k} = {v['what']}" for k, v in sorted(PRESETS.items())))
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be at least 1: the line reports the time of one timed step")
     if args.config:  # a preset fills in what the command line left at its default
         for name, value in PRESETS[args.config]["set"].items():
             if getattr(args, name) == parser.get_default(name):
@@ -916,6 +950,10 @@ def main() -> None:
         step_stats.append(stats)
 
     elapsed = timed_steps(timed_step, args.steps, world, device)
+    if rank == 0 and args.dump_outputs:  # before anything below searches into the same buffers again
+        dump_outputs(args.dump_outputs, {"keys": keys_dev.cpu().numpy(), "distances": dist_dev.cpu().numpy(),
+                                         "counts": counts_dev.cpu().numpy(), "visited": visited_dev.cpu().numpy(),
+                                         "computed": computed_dev.cpu().numpy()})
     stats = step_stats[-1]
     passes = max(int(each.passes) for each in step_stats)
 

@@ -65,6 +65,7 @@ int main(int argc, char** argv) {
     std::printf("usearch %d.%d.%d behind index_dense_t\n", USEARCH_VERSION_MAJOR, USEARCH_VERSION_MINOR, USEARCH_VERSION_PATCH);
     if (argc < 2 || std::strcmp(argv[1], "run") != 0)
         return 0;
+    const char* image_path = argc > 2 ? argv[2] : "usearch_amd_bench_loop.usearch"; // `run [where the save / load step writes]`
     const std::size_t dims = 96, count = 4000, queries = 512, wanted = 10;
     std::mt19937 generator(11);
     std::normal_distribution<float> normal;
@@ -136,8 +137,8 @@ int main(int argc, char** argv) {
     EXPECT(index.contains(ids[9]) && !index.contains(1));
     EXPECT(index.rename(ids[9], 99).completed == 1 && index.contains(99) && !index.contains(ids[9]));
     EXPECT(index.remove(99).completed == 1 && !index.contains(99) && index.size() == count - 1);
-    EXPECT(index.save("/tmp/usearch_amd_bench_loop.usearch"));
-    index_dense_t copy = index_dense_t::make("/tmp/usearch_amd_bench_loop.usearch");
+    EXPECT(index.save(image_path));
+    index_dense_t copy = index_dense_t::make(image_path);
     EXPECT(copy && copy.size() == count - 1 && copy.dimensions() == dims && copy.scalar_kind() == scalar_kind_t::f32_k);
     auto again = copy.search(data.data() + 5 * dims, wanted);
     EXPECT(again && again[0].member.key == ids[5]);

@@ -96,3 +96,47 @@ def test_launcher_path_of_the_sharded_bench_two_ranks_on_the_cpu():
     env3 = dict(env, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     assert subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--sharded", "--steps", "1", "--warmup", "0"],
                           capture_output=True, text=True, timeout=120, env=env3).returncode == 0
+
+
+def test_dump_outputs_writes_the_last_timed_step_the_same_way_every_run(tmp_path):
+    """`--dump-outputs DIR` after the timed steps: one float32 / float64 .npy per array the step returns, identical for identical
+    arguments (here through the CPU rehearsal of the launcher path, one rank); `--steps` below 1 is refused."""
+    import json
+    import os
+    import subprocess
+    import sys
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, BENCH_REHEARSAL="cpu", GLOO_SOCKET_IFNAME="lo")
+    for name in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(name, None)
+    dumps = []
+    for run in ("first", "second"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--sharded", "--config", "c5", "--steps", "3",
+                              "--warmup", "1", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=300, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([text for text in out.stdout.splitlines() if text.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        dumps.append({name: np.load(tmp_path / run / f"{name}.npy") for name in ("keys", "distances", "counts")})
+    for name, value in dumps[0].items():
+        assert value.dtype in (np.float32, np.float64) and len(value) == 64, name
+        assert np.array_equal(value, dumps[1][name]), name
+    assert dumps[0]["distances"].dtype == np.float32 and dumps[0]["keys"].shape == (64, 10)
+    refused = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert refused.returncode != 0 and "--steps" in refused.stderr
+
+
+def test_dump_outputs_keeps_a_seeded_sample_of_rows_above_the_limit(tmp_path, monkeypatch):
+    import os
+    rows = 1000
+    keys = np.arange(rows * 10, dtype=np.int64).reshape(rows, 10)
+    distances = np.linspace(0, 1, rows * 10, dtype=np.float32).reshape(rows, 10)
+    bench.dump_outputs(str(tmp_path / "whole"), {"keys": keys, "distances": distances})
+    assert np.array_equal(np.load(tmp_path / "whole" / "keys.npy"), keys) and not (tmp_path / "whole" / "rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40_000)
+    for run in ("first", "second"):
+        bench.dump_outputs(str(tmp_path / run), {"keys": keys, "distances": distances})
+    kept = np.load(tmp_path / "first" / "rows.npy").astype(np.int64)
+    assert np.array_equal(kept, np.load(tmp_path / "second" / "rows.npy")) and np.all(np.diff(kept) > 0)
+    assert sum(os.path.getsize(tmp_path / "first" / name) for name in os.listdir(tmp_path / "first")) <= 40_000 + 3 * 128
+    assert np.array_equal(np.load(tmp_path / "first" / "keys.npy"), keys[kept].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "first" / "distances.npy"), distances[kept])

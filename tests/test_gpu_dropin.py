@@ -803,7 +803,7 @@ def test_concurrent_callers_share_the_index(lib, monkeypatch, coalesce):
     lib.usearch_free(index, C.byref(err))
 
 
-def test_the_references_own_c_test_program_passes_against_the_drop_in():
+def test_the_references_own_c_test_program_passes_against_the_drop_in(tmp_path):
     """/root/reference/c/test.c itself, compiled by `__graft_entry__.build()` where the reference is mounted and linked against
     usearch_amd/lib/libusearch_c.so instead of the reference's library (oracle/Makefile `dropin_test` → oracle/_ref/)."""
     import subprocess
@@ -811,5 +811,6 @@ def test_the_references_own_c_test_program_passes_against_the_drop_in():
     if not os.path.exists(binary):
         pytest.skip("oracle/_ref/reference_test_c was not built (`make -C oracle dropin_test` needs /root/reference)")
     environment = dict(os.environ, LD_LIBRARY_PATH=os.path.join(ROOT, "usearch_amd", "lib") + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    result = subprocess.run([binary], capture_output=True, text=True, timeout=600, env=environment)
+    # (c/test.c saves and views "tmp.usearch" in its working directory)
+    result = subprocess.run([binary], capture_output=True, text=True, timeout=600, env=environment, cwd=tmp_path)
     assert result.returncode == 0, result.stdout[-2000:] + result.stderr[-2000:]

@@ -236,13 +236,13 @@ def test_the_bench_hash_names_files_that_exist():
     assert len(bench.source_hash()) == 16
 
 
-def test_calls_in_flight_share_a_launch():
+def test_calls_in_flight_share_a_launch(tmp_path):
     """The drop-in's call combiner (usearch_amd/csrc/combiner.hpp: pure host logic) under 32 threads with a mock launch
     (tests/cpp/combiner_test.cpp): every call gets its own answer, callers that queue up during a launch go out together,
     groups never mix query kinds or result counts, an exception inside a launch becomes every call's error string."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    binary = "/tmp/usearch_amd_combiner_test"
+    binary = str(tmp_path / "usearch_amd_combiner_test")
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-pthread",
                            os.path.join(root, "tests", "cpp", "combiner_test.cpp"), "-o", binary])
     out = subprocess.run([binary], capture_output=True, text=True, timeout=120)
@@ -250,7 +250,7 @@ def test_calls_in_flight_share_a_launch():
 
 
 
-def test_calls_in_flight_share_a_launch_under_the_thread_sanitizer():
+def test_calls_in_flight_share_a_launch_under_the_thread_sanitizer(tmp_path):
     """The same program under ThreadSanitizer (clang's runtime: it knows `pthread_cond_clockwait`, which the launcher's timed wait
     for returning callers uses): no data race, no lock-order report in the combiner."""
     import subprocess
@@ -258,7 +258,7 @@ def test_calls_in_flight_share_a_launch_under_the_thread_sanitizer():
     if not os.path.exists(compiler):
         pytest.skip("no clang++ with a ThreadSanitizer runtime here")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    binary = "/tmp/usearch_amd_combiner_test_tsan"
+    binary = str(tmp_path / "usearch_amd_combiner_test_tsan")
     built = subprocess.run([compiler, "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread",
                             os.path.join(root, "tests", "cpp", "combiner_test.cpp"), "-o", binary], capture_output=True, text=True)
     if built.returncode != 0:
