@@ -439,6 +439,40 @@ class dummy_progress_t {
   public:
     bool operator()(std::size_t, std::size_t) const noexcept { return true; }
 };
+class dummy_executor_t { // index_plugins.hpp: one thread
+  public:
+    std::size_t size() const noexcept { return 1; }
+};
+/// A key-to-key mapping that forgets what it is given (index.hpp:1488-1495).
+struct dummy_key_to_key_mapping_t {
+    struct member_ref_t {
+        template <typename key_at> member_ref_t& operator=(key_at&&) noexcept { return *this; }
+    };
+    template <typename key_at> member_ref_t operator[](key_at&&) const noexcept { return {}; }
+};
+
+/// `index_join_config_t` (index.hpp:1452-1463).
+struct index_join_config_t {
+    std::size_t max_proposals = 0;   ///< 0 = log(proposers) + executor.size(), capped at the proposers' size
+    std::size_t expansion = 64;      ///< `default_expansion_search()`
+    bool exact = false;
+};
+
+/// `join_result_t` (index.hpp:4321-4333). `engagements` and the two counters are the device's: parallel rounds make no
+/// intermediate engagements, and one search per proposer stands for the reference's one search per proposal.
+struct join_result_t {
+    error_t error{};
+    std::size_t intersection_size{};
+    std::size_t engagements{};
+    std::size_t visited_members{};
+    std::size_t computed_distances{};
+
+    explicit operator bool() const noexcept { return !error; }
+    join_result_t failed(error_t message) noexcept {
+        error = std::move(message);
+        return std::move(*this);
+    }
+};
 
 /// `exact_search_t` (index_plugins.hpp:2071-2164): many queries against a raw dataset, keys are dataset offsets.
 class exact_search_results_t {
@@ -497,6 +531,7 @@ class exact_search_t {
  */
 template <typename key_at = default_key_t, typename compressed_slot_at = default_slot_t> class index_dense_gt {
     static_assert(sizeof(key_at) == 8, "the device index keys its members with 64 bits (index_dense_t)");
+    template <typename, typename> friend class index_dense_gt;
     usearch_index_t handle_ = nullptr;
     metric_punned_t metric_;
     index_dense_config_t config_;
@@ -688,6 +723,36 @@ template <typename key_at = default_key_t, typename compressed_slot_at = default
     }
 
     explicit operator bool() const noexcept { return handle_ != nullptr && metric_.dimensions() != 0; }
+
+    /// `join(women, config, man_to_woman, woman_to_man, executor, progress)` (index_dense.hpp:1768-1786 → index.hpp:4359-4545): the
+    /// man-optimal stable matching of this index's members with `women`'s, on the device. The smaller side proposes; the maps
+    /// receive `map[key] = key` for every pair (raw key arrays indexed by key and `std::unordered_map` both qualify). `executor`
+    /// only sizes the default `max_proposals`; `progress` is told once, at the end. Removed members take no part.
+    template <typename other_key_at, typename other_slot_at, typename man_to_woman_at = dummy_key_to_key_mapping_t,
+              typename woman_to_man_at = dummy_key_to_key_mapping_t, typename executor_at = dummy_executor_t,
+              typename progress_at = dummy_progress_t>
+    join_result_t join(index_dense_gt<other_key_at, other_slot_at> const& women, index_join_config_t config = {},
+                       man_to_woman_at&& man_to_woman = man_to_woman_at{}, woman_to_man_at&& woman_to_man = woman_to_man_at{},
+                       executor_at&& executor = executor_at{}, progress_at&& progress = progress_at{}) const {
+        join_result_t result;
+        std::size_t const capacity = (std::min)(size(), women.size());
+        std::vector<usearch_key_t> men_keys(capacity), women_keys(capacity);
+        std::size_t stats[4] = {};
+        usearch_error_t error = nullptr;
+        std::size_t const pairs =
+            amd_detail::api().join(handle_, women.handle_, config.max_proposals, config.expansion, config.exact, executor.size(),
+                                   men_keys.data(), women_keys.data(), capacity, stats, &error);
+        if (error)
+            return result.failed(error);
+        for (std::size_t j = 0; j != pairs && j != capacity; ++j) {
+            man_to_woman[static_cast<vector_key_t>(men_keys[j])] = static_cast<other_key_at>(women_keys[j]);
+            woman_to_man[static_cast<other_key_at>(women_keys[j])] = static_cast<vector_key_t>(men_keys[j]);
+        }
+        progress(pairs, pairs);
+        result.intersection_size = stats[0], result.engagements = stats[1];
+        result.visited_members = stats[2], result.computed_distances = stats[3];
+        return result;
+    }
     std::size_t size() const noexcept { return get_(amd_detail::api().size); }
     std::size_t capacity() const noexcept { return get_(amd_detail::api().capacity); }
     std::size_t dimensions() const noexcept { return get_(amd_detail::api().dimensions); }
@@ -971,6 +1036,18 @@ template <typename key_at = default_key_t, typename compressed_slot_at = default
 };
 
 using index_dense_t = index_dense_gt<>;
+
+/// The free `join(men, women, …)` (index_dense.hpp:2254-2270), forwarding its two maps exactly as the reference does.
+template <typename men_key_at, typename women_key_at, typename men_slot_at, typename women_slot_at,
+          typename man_to_woman_at = dummy_key_to_key_mapping_t, typename woman_to_man_at = dummy_key_to_key_mapping_t,
+          typename executor_at = dummy_executor_t, typename progress_at = dummy_progress_t>
+static join_result_t join(index_dense_gt<men_key_at, men_slot_at> const& men, index_dense_gt<women_key_at, women_slot_at> const& women,
+                          index_join_config_t config = {}, man_to_woman_at&& man_to_woman = man_to_woman_at{},
+                          woman_to_man_at&& woman_to_man = woman_to_man_at{}, executor_at&& executor = executor_at{},
+                          progress_at&& progress = progress_at{}) {
+    return men.join(women, config, std::forward<woman_to_man_at>(woman_to_man), std::forward<man_to_woman_at>(man_to_woman),
+                    std::forward<executor_at>(executor), std::forward<progress_at>(progress));
+}
 
 } // namespace usearch
 } // namespace unum

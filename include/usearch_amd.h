@@ -425,6 +425,46 @@ USEARCH_AMD_EXPORT void usearch_amd_merge_many(usearch_amd_distance_t const* dis
                                                usearch_amd_key_t* out_keys, uint64_t* out_counts,
                                                usearch_amd_error_t* error);
 
+/* ---- semantic join: a one-to-one matching of two snapshots ----------------------------------------------------------------
+ *  `unum::usearch::join` (index.hpp:4359-4545 through index_dense.hpp:1768-1786): man-optimal stable marriage whose preference
+ *  lists are each man's nearest women. The smaller snapshot proposes (on equal sizes `a`); pairs always map `a` to `b`.
+ * -------------------------------------------------------------------------------------------------------------------------- */
+
+/** Zero-initialise for the reference's defaults (`index_join_config_t`, index.hpp:1452-1463). */
+typedef struct usearch_amd_join_config_t {
+    uint64_t max_proposals; /**< P; 0 = log(proposers) + threads (index.hpp:4390-4391); capped at the proposers' size; at most 65535 */
+    uint64_t expansion;     /**< ef of every list search; 0 = 64 */
+    uint32_t exact;         /**< 1 = lists from the bit-exact brute-force scan of `usearch_amd_exact_search_many` */
+    uint32_t threads;       /**< the `executor.size()` term of the default P; 0 counts as 1 */
+} usearch_amd_join_config_t;
+
+typedef struct usearch_amd_join_stats_t {
+    uint64_t pairs;              /**< `join_result_t::intersection_size` */
+    uint64_t rounds;             /**< matching rounds: every free proposer offers at once, every woman keeps the best offer */
+    uint64_t proposals;          /**< offers made in all rounds */
+    uint64_t engagements;        /**< offers accepted; smaller than the reference's count (no intermediate engagements) */
+    uint64_t visited_members;    /**< sums over the list searches; one search here stands for up to P of the reference's */
+    uint64_t computed_distances;
+    uint64_t max_proposals;      /**< P after the default and the cap */
+    uint64_t expansion;          /**< ef the lists were searched with */
+    uint64_t list_width;         /**< results per proposer of the first list search (P exact, min(P, ef) otherwise) */
+    uint64_t lazy_searches;      /**< searches for proposals number ef + 1 … P, one per distinct number per round */
+    uint32_t a_proposes;         /**< 0: `b` was smaller and proposed */
+    uint32_t frontier;           /**< frontier of the first list search: 1 heap, 2 open cells of `top`, 0 exact */
+    double seconds_lists;        /**< wall time of the list searches (lazy ones included) */
+    double seconds_matching;     /**< wall time of the rest: rounds and export */
+} usearch_amd_join_stats_t;
+
+/**
+ *  Joins two snapshots of the same metric, scalar kind and dimensions on one device. Writes up to `capacity` pairs
+ *  `a_keys[j]` ↔ `b_keys[j]` in ascending order of `a`'s slots and returns how many pairs the matching holds. Tombstoned
+ *  members take no part on either side. `stats` may be NULL. Refused with an error: a snapshot joined with itself,
+ *  different devices, different metric / scalar kind / dimensions, P above 65535, lists that do not fit in free HBM.
+ */
+USEARCH_AMD_EXPORT size_t usearch_amd_join(usearch_amd_snapshot_t a, usearch_amd_snapshot_t b, usearch_amd_join_config_t const* config,
+                                           usearch_amd_key_t* a_keys, usearch_amd_key_t* b_keys, size_t capacity,
+                                           usearch_amd_join_stats_t* stats, usearch_amd_error_t* error);
+
 /* ---- index construction on the device ------------------------------------------------------------------------------ */
 
 typedef void* usearch_amd_builder_t;

@@ -314,6 +314,13 @@ typedef struct usearch_amd_c_api_t {
                                  usearch_key_t*, size_t, usearch_distance_t*, size_t, size_t*, size_t*, size_t*, usearch_error_t*);
     void (*filtered_search_exact_many)(usearch_index_t, usearch_filter_t, void const*, usearch_scalar_kind_t, size_t, size_t, size_t,
                                        usearch_key_t*, size_t, usearch_distance_t*, size_t, size_t*, usearch_error_t*);
+    /** Semantic join of two indexes, `index_dense_gt::join` (the reference's index_dense.hpp:1768-1786 → index.hpp:4359-4545):
+     *  (a, b, max_proposals, expansion, exact, threads, a_keys, b_keys, capacity, stats, error) → pairs. Writes up to `capacity`
+     *  pairs a_keys[j] ↔ b_keys[j] in ascending order of `a`'s slots; `stats` (may be NULL) receives `join_result_t`'s
+     *  {intersection_size, engagements, visited_members, computed_distances}. Both indexes are brought up to date first (deferred
+     *  adds linked); removed members take no part. `expansion` 0 = 64, `threads` is the executor.size() term of the default P. */
+    size_t (*join)(usearch_index_t, usearch_index_t, size_t, size_t, bool, size_t, usearch_key_t*, usearch_key_t*, size_t, size_t*,
+                   usearch_error_t*);
 } usearch_amd_c_api_t;
 USEARCH_EXPORT usearch_amd_c_api_t const* usearch_amd_c_api(void);
 

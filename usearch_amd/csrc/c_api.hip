@@ -9,6 +9,8 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <cstring>
 #include <memory>
 #include <new>
 #include <vector>
@@ -17,6 +19,7 @@
 #include "casts.hpp"
 #include "engine.hpp"
 #include "filter.hpp"
+#include "join.hpp"
 #include "kernels.hpp"
 #include "sharded.hpp"
 
@@ -699,6 +702,43 @@ int usearch_amd_cast(int from_kind, int to_kind, void const* input, size_t dimen
                        dimensions, static_cast<std::uint8_t*>(output))
                ? 1
                : 0;
+}
+
+// ---- semantic join (join.hpp)
+size_t usearch_amd_join(usearch_amd_snapshot_t a, usearch_amd_snapshot_t b, usearch_amd_join_config_t const* config,
+                        usearch_amd_key_t* a_keys, usearch_amd_key_t* b_keys, size_t capacity, usearch_amd_join_stats_t* stats,
+                        usearch_amd_error_t* error) try {
+    if (!a || !b)
+        return fail(error, "Join needs two snapshots"), 0;
+    join_config_t c;
+    if (config) {
+        c.max_proposals = config->max_proposals;
+        c.expansion = config->expansion;
+        c.exact = config->exact != 0;
+        c.threads = config->threads ? config->threads : 1;
+    }
+    std::vector<std::uint64_t> left, right;
+    join_stats_t s;
+    const char* e = join_snapshots(*as_snapshot(a), *as_snapshot(b), c, left, right, &s);
+    if (stats) {
+        stats->pairs = s.pairs, stats->rounds = s.rounds, stats->proposals = s.proposals, stats->engagements = s.engagements;
+        stats->visited_members = s.visited_members, stats->computed_distances = s.computed_distances;
+        stats->max_proposals = s.max_proposals, stats->expansion = s.expansion, stats->list_width = s.list_width;
+        stats->lazy_searches = s.lazy_searches, stats->a_proposes = s.a_proposes, stats->frontier = s.frontier;
+        stats->seconds_lists = s.seconds_lists, stats->seconds_matching = s.seconds_matching;
+    }
+    if (e)
+        return fail(error, e), 0;
+    const std::size_t written = std::min<std::size_t>(capacity, left.size());
+    if (written && ((a_keys == nullptr) != (b_keys == nullptr) || !a_keys))
+        return fail(error, "Join needs both key buffers"), 0;
+    if (written) {
+        std::memcpy(a_keys, left.data(), written * 8);
+        std::memcpy(b_keys, right.data(), written * 8);
+    }
+    return left.size();
+} catch (...) {
+    return fail_from_exception(error), 0;
 }
 
 } // extern "C"

@@ -41,6 +41,7 @@
 #include "engine.hpp"
 #include "filter.hpp"
 #include "host_util.hpp"
+#include "join.hpp"
 
 using namespace usearch_amd;
 
@@ -1451,9 +1452,56 @@ void usearch_gpu_release(usearch_index_t handle, usearch_error_t*) {
     index.drop_device();
 }
 
+/// The table's `join`: both indexes brought up to date under their own locks, taken alone and in address order (a join in the
+/// other direction running at the same time takes them in the same order), then `join_snapshots` over their device snapshots.
+static size_t dropin_join(usearch_index_t a_handle, usearch_index_t b_handle, size_t max_proposals, size_t expansion, bool exact,
+                          size_t threads, usearch_key_t* a_keys, usearch_key_t* b_keys, size_t capacity, size_t* stats,
+                          usearch_error_t* error) {
+    if (!a_handle || !b_handle) {
+        fail(error, "Join needs two indexes");
+        return 0;
+    }
+    if (a_handle == b_handle) {
+        fail(error, "Can't join with itself, consider copying"); // index.hpp:4388
+        return 0;
+    }
+    index_t& a = *as_index(a_handle);
+    index_t& b = *as_index(b_handle);
+    size_t pairs = 0;
+    guarded(error, [&] {
+        index_t& first = &a < &b ? a : b;
+        index_t& second = &a < &b ? b : a;
+        unique_lock_t first_lock(first.mutex);
+        unique_lock_t second_lock(second.mutex);
+        snapshot_t *a_snapshot = nullptr, *b_snapshot = nullptr;
+        if (const char* e = a.ready(&a_snapshot))
+            return fail(error, e);
+        if (const char* e = b.ready(&b_snapshot))
+            return fail(error, e);
+        if (!a_snapshot || !b_snapshot) // an empty index has no device snapshot: nothing to match
+            return;
+        join_config_t config;
+        config.max_proposals = max_proposals, config.expansion = expansion, config.exact = exact;
+        config.threads = threads ? threads : 1;
+        std::vector<std::uint64_t> left, right;
+        join_stats_t s;
+        if (const char* e = join_snapshots(*a_snapshot, *b_snapshot, config, left, right, &s))
+            return fail(error, e);
+        const std::size_t written = std::min<std::size_t>(capacity, left.size());
+        if (written && (!a_keys || !b_keys))
+            return fail(error, "Join needs both key buffers");
+        std::copy(left.begin(), left.begin() + written, a_keys);
+        std::copy(right.begin(), right.begin() + written, b_keys);
+        if (stats)
+            stats[0] = s.pairs, stats[1] = s.engagements, stats[2] = s.visited_members, stats[3] = s.computed_distances;
+        pairs = left.size();
+    });
+    return pairs;
+}
+
 usearch_amd_c_api_t const* usearch_amd_c_api(void) {
     static const usearch_amd_c_api_t table = {
-        51,
+        52,
         &usearch_version, &usearch_init, &usearch_free, &usearch_memory_usage, &usearch_hardware_acceleration,
         &usearch_serialized_length, &usearch_save, &usearch_load, &usearch_view, &usearch_metadata, &usearch_save_buffer,
         &usearch_load_buffer, &usearch_view_buffer, &usearch_metadata_buffer, &usearch_size, &usearch_capacity,
@@ -1464,7 +1512,7 @@ usearch_amd_c_api_t const* usearch_amd_c_api(void) {
         &usearch_distance, &usearch_exact_search, &usearch_clear, &usearch_search_many, &usearch_cluster_many,
         &usearch_search_exact_many, &usearch_threads_search, &usearch_gpu_sync, &usearch_gpu_release,
         &usearch_filter_from_key_range, &usearch_filter_from_keys, &usearch_filter_from_callback, &usearch_filter_allowed,
-        &usearch_filter_free, &usearch_filtered_search_many, &usearch_filtered_search_exact_many,
+        &usearch_filter_free, &usearch_filtered_search_many, &usearch_filtered_search_exact_many, &dropin_join,
     };
     return &table;
 }

@@ -4,7 +4,8 @@ It mirrors the *search* surface of the reference's Python package (`/root/refere
 `Index.restore(path_or_buffer)` (index.py:574-630) gives an object whose `search(vectors, count, ...)` has the argument
 meaning of `Index.search` (index.py:700-748) and returns `Matches` / `BatchMatches` shaped like index.py:291-385 —
 row-major `keys[Q, k]` (u64), `distances[Q, k]` (f32), `counts[Q]`, plus the two traversal counters. Everything else of
-that package (add / remove / cluster / join …) stays with the reference: this engine consumes the index files it writes.
+that package (add / remove …) stays with the reference: this engine consumes the index files it writes. `Index.join`
+(index.py:1170-1200) runs on the device: preference lists from the batched search, the matching as HIP kernels.
 
 There is no CPU fallback: without `libusearch_amd.so` or without a HIP device, constructing an `Index` raises.
 """
@@ -13,7 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Optional, Union
+from typing import Dict, Optional, Union
 
 import numpy as np
 
@@ -61,6 +62,22 @@ class Arrays(C.Structure):
                 ("row_stride", C.c_uint32), ("level0_cells", C.c_uint32), ("device", C.c_int), ("reserved", C.c_uint32)]
 
 
+class JoinConfig(C.Structure):
+    """`usearch_amd_join_config_t`; zeros = the reference's defaults."""
+    _fields_ = [("max_proposals", C.c_uint64), ("expansion", C.c_uint64), ("exact", C.c_uint32), ("threads", C.c_uint32)]
+
+
+class JoinStats(C.Structure):
+    """`usearch_amd_join_stats_t`."""
+    _fields_ = [("pairs", C.c_uint64), ("rounds", C.c_uint64), ("proposals", C.c_uint64), ("engagements", C.c_uint64),
+                ("visited_members", C.c_uint64), ("computed_distances", C.c_uint64), ("max_proposals", C.c_uint64),
+                ("expansion", C.c_uint64), ("list_width", C.c_uint64), ("lazy_searches", C.c_uint64), ("a_proposes", C.c_uint32),
+                ("frontier", C.c_uint32), ("seconds_lists", C.c_double), ("seconds_matching", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class BuildConfig(C.Structure):
     """`usearch_amd_build_config_t`; zeros = the reference's defaults."""
     _fields_ = [("connectivity", C.c_uint32), ("connectivity_base", C.c_uint32), ("expansion_add", C.c_uint32),
@@ -103,6 +120,7 @@ EXPORTED_SYMBOLS = [
     "usearch_amd_cast",
     "usearch_amd_build", "usearch_amd_build_free", "usearch_amd_build_snapshot",
     "usearch_amd_build_serialized_length", "usearch_amd_build_save_buffer", "usearch_amd_build_stats",
+    "usearch_amd_join",
     # sharded search across GPUs (usearch_amd/sharded.py binds these)
     "usearch_amd_comm_unique_id", "usearch_amd_comm_init_rccl", "usearch_amd_comm_init_custom", "usearch_amd_comm_free",
     "usearch_amd_comm_rank", "usearch_amd_comm_world", "usearch_amd_comm_broadcast", "usearch_amd_sharded_search_many",
@@ -228,6 +246,9 @@ def library() -> C.CDLL:
     L.usearch_amd_build_serialized_length.argtypes = [C.c_void_p]
     L.usearch_amd_build_save_buffer.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, err_p]
     L.usearch_amd_build_stats.argtypes = [C.c_void_p, C.POINTER(BuildStats)]
+    L.usearch_amd_join.restype = C.c_size_t
+    L.usearch_amd_join.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(JoinConfig), C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.POINTER(JoinStats), err_p]
     _library = L
     return L
 
@@ -706,6 +727,42 @@ class Index:
                                            C.byref(err))
         _raise(err, "usearch_amd_cluster_many")
         return keys, distances, visited, computed
+
+    # ---- semantic join
+    def join(self, other: "Index", max_proposals: int = 0, exact: bool = False, *, expansion: Optional[int] = None,
+             threads: int = 0) -> Dict[int, int]:
+        """`Index.join` (index.py:1170-1200 → python/lib.cpp:780-797): a one-to-one mapping from keys of `self` to keys of `other`,
+        the man-optimal stable matching in which the smaller index proposes to its nearest members. `expansion` defaults to the
+        larger of the two indexes' `expansion_search`; `threads` is the `executor.size()` term of the default `max_proposals`
+        (log(proposers) + threads). Members removed from either index take no part. The numbers of the run: `join_stats()`."""
+        if not isinstance(other, Index):
+            raise TypeError("join needs another usearch_amd.Index")
+        a_keys, b_keys, stats = self.join_arrays(other, max_proposals, exact, expansion=expansion, threads=threads)
+        return dict(zip(a_keys.tolist(), b_keys.tolist()))
+
+    def join_arrays(self, other: "Index", max_proposals: int = 0, exact: bool = False, *, expansion: Optional[int] = None,
+                    threads: int = 0):
+        """`join` as two aligned key arrays in ascending order of `self`'s slots, and the `JoinStats` of the run."""
+        if expansion is None:
+            expansion = max(self.expansion_search or 64, other.expansion_search or 64)
+        config = JoinConfig(max_proposals=max_proposals, expansion=expansion, exact=int(bool(exact)), threads=threads)
+        capacity = min(len(self), len(other))
+        a_keys = np.zeros(max(1, capacity), dtype=np.uint64)
+        b_keys = np.zeros(max(1, capacity), dtype=np.uint64)
+        stats = JoinStats()
+        err = C.c_char_p()
+        pairs = library().usearch_amd_join(self._handle, other._handle, C.byref(config), _pointer(a_keys), _pointer(b_keys), capacity,
+                                           C.byref(stats), C.byref(err))
+        _raise(err, "usearch_amd_join")
+        self._join_stats = stats
+        return a_keys[:pairs].copy(), b_keys[:pairs].copy(), stats
+
+    def join_stats(self) -> dict:
+        """Numbers of the last `join` called on this index: pairs, rounds, proposals, engagements, the list searches' visited and
+        computed sums, P, ef, and the seconds of the lists and of the matching. `engagements` and the two counters are not the
+        reference's: parallel rounds make no intermediate engagements, and one search stands for up to P of the reference's."""
+        stats = getattr(self, "_join_stats", None)
+        return stats.as_dict() if stats is not None else {}
 
     def distances(self, queries: np.ndarray, slots: np.ndarray) -> np.ndarray:
         """out[q, j] = metric(queries[q], stored vector of slot slots[q, j]); queries in the storage kind."""
