@@ -120,6 +120,23 @@ def assert_float_parity(got_keys, got_distances, got_counts, reference_search, q
     return float(separated.sum() / max(1, found.sum())), float(((np.asarray(got_keys) == rkeys) | ~found).mean())
 
 
+def slot_distance(vectors: np.ndarray, metric: str, dtype: str, ndim: int, lanes: int = 0):
+    """→ `dist(a, b)`: the oracle's distance (`oraclebind.distance`) with row `a` of `vectors` as the query and row `b` as the stored
+    vector, in the summation layout of `lanes` lanes per row (0 = the reference's serial loop). Rows are addressed in place:
+    a graph model calls this a million times."""
+    import ctypes
+    assert vectors.flags.c_contiguous and vectors.ndim == 2
+    measure = oraclebind.lib().uo_distance
+    metric_kind, scalar_kind = oraclebind.METRIC[metric], oraclebind.SCALAR[dtype]
+    base, stride, rows = vectors.ctypes.data, vectors.strides[0], len(vectors)
+    dimensions = ctypes.c_uint64(ndim)
+
+    def dist(a: int, b: int, _keep=vectors) -> float:
+        assert 0 <= a < rows and 0 <= b < rows
+        return measure(metric_kind, scalar_kind, base + a * stride, base + b * stride, dimensions, lanes)
+    return dist
+
+
 def same_float_bits(a: np.ndarray, b: np.ndarray) -> bool:
     return np.array_equal(np.asarray(a, dtype=np.float32).view(np.uint32), np.asarray(b, dtype=np.float32).view(np.uint32))
 
