@@ -60,7 +60,10 @@ typedef struct usearch_amd_tuning_t {
                                 float-valued pairs, expansion ≤ 1024, no predicate / tombstones — refused otherwise).
                                 Auto = 2 where it applies, else 1. DESIGN.md §3.1 */
     uint32_t wave_clock;   /**< 1 = record when every persistent wave started and left (fills stats.tail_idle / span_ms) */
-    uint32_t reserved;
+    uint32_t sketch;       /**< the low-rank sketch of long cos rows (f32 / f16 / bf16, ≥ 1 536 bytes per vector), which lets the walk skip
+                                the rows of candidates it proves too far — same results, counters included: 0 = auto (the first
+                                batch of ≥ 1 024 queries judges it: under a quarter of the tested candidates pruned, and the snapshot frees it),
+                                1 = off for this call, 2 = on where the snapshot has one, and not judged. DESIGN.md §3.1 */
 } usearch_amd_tuning_t;
 
 /** What a batched search did, for profiling and tests. */
@@ -88,6 +91,8 @@ typedef struct usearch_amd_stats_t {
                                   tombstones, lists of ≤ 64 cells); USEARCH_AMD_NO_PLAIN=1 keeps the general build. Same results */
     uint32_t aside_cells;    /**< … and its LDS cells for the members whose home cell in the slab was taken (the slab is then probed at the
                                   home cell only: one round trip per hop) */
+    uint64_t sketch_tested;  /**< candidates of this call that were tested against the sketch (0 = the call walked without it) … */
+    uint64_t sketch_pruned;  /**< … and how many of them it proved too far: their rows were never fetched */
 } usearch_amd_stats_t;
 
 /** Number of visible HIP devices; 0 (and an error) when the runtime finds none. */
@@ -174,7 +179,7 @@ typedef struct usearch_amd_arrays_t {
     uint32_t row_stride;
     uint32_t level0_cells;
     int device;
-    uint32_t reserved;
+    uint32_t sketch; /**< 1 = the snapshot holds a sketch of its rows at the moment (usearch_amd_tuning_t::sketch) */
 } usearch_amd_arrays_t;
 USEARCH_AMD_EXPORT void usearch_amd_snapshot_arrays(usearch_amd_snapshot_t snapshot, usearch_amd_arrays_t* arrays);
 /** Storage scalar kind (C enumerator) and metric kind (`usearch_metric_kind_t` value, c/usearch.h:40-52). */
@@ -502,6 +507,14 @@ USEARCH_AMD_EXPORT usearch_amd_builder_t usearch_amd_build(void const* vectors, 
                                                            usearch_amd_build_config_t const* config, int device,
                                                            int vectors_on_device, usearch_amd_error_t* error);
 USEARCH_AMD_EXPORT void usearch_amd_build_free(usearch_amd_builder_t builder, usearch_amd_error_t* error);
+/** Adds `count` more members (host rows of the storage kind, `stride` bytes apart) to a built index and links them in place: the
+ *  arrays grow geometrically, the snapshot stays the same object. `keys` may be NULL only while every member is keyed by its row. */
+USEARCH_AMD_EXPORT void usearch_amd_build_extend(usearch_amd_builder_t builder, void const* vectors, size_t count, size_t stride,
+                                                 usearch_amd_key_t const* keys, usearch_amd_error_t* error);
+/** Overwrites the members in `slots[0 .. count)` with new rows and keys and links them anew where they stand (a recycled slot:
+ *  index.hpp:4087-4170). */
+USEARCH_AMD_EXPORT void usearch_amd_build_update(usearch_amd_builder_t builder, uint32_t const* slots, size_t count, void const* vectors,
+                                                 size_t stride, usearch_amd_key_t const* keys, usearch_amd_error_t* error);
 /** The snapshot the build produced; owned by the builder, valid until `usearch_amd_build_free`. */
 USEARCH_AMD_EXPORT usearch_amd_snapshot_t usearch_amd_build_snapshot(usearch_amd_builder_t builder);
 /** `usearch_serialized_length` / `usearch_save_buffer` (c/usearch.h:154, 195): a v2 image the reference loads. */

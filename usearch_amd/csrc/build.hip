@@ -203,6 +203,7 @@ const char* snapshot_t::overwrite_member(std::uint64_t slot, const void* vector,
                                     view_.bytes_per_vector, 1))
         return e;
     UA_HIP(hipMemcpy(static_cast<std::uint64_t*>(d_keys_) + slot, &key, 8, hipMemcpyHostToDevice));
+    view_.sketch = nullptr, sketch_stale_ = true; // the row's record no longer bounds it: the next finalize_layout makes the sketch anew
     ++mutations_;
     return nullptr;
 }

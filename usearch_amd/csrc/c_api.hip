@@ -93,6 +93,7 @@ search_tuning_t tuning_from_c(usearch_amd_tuning_t const* t) {
         out.waves_per_cu = t->waves_per_cu;
         out.frontier = t->frontier;
         out.wave_clock = t->wave_clock;
+        out.sketch = t->sketch;
     }
     return out;
 }
@@ -118,6 +119,8 @@ void stats_to_c(const search_stats_t& s, usearch_amd_stats_t* out) {
     out->early_rows = s.early_rows;
     out->plain = s.plain;
     out->aside_cells = s.aside_cells;
+    out->sketch_tested = s.sketch_tested;
+    out->sketch_pruned = s.sketch_pruned;
 }
 
 void fail(usearch_amd_error_t* error, const char* message) {
@@ -237,6 +240,7 @@ void usearch_amd_snapshot_arrays(usearch_amd_snapshot_t s, usearch_amd_arrays_t*
     out->vectors = view.vectors, out->level0 = view.nbr0, out->keys = view.keys;
     out->size = view.size, out->row_stride = view.row_stride, out->level0_cells = view.m0;
     out->device = as_snapshot(s)->device();
+    out->sketch = as_snapshot(s)->has_sketch() ? 1u : 0u;
 }
 void usearch_amd_snapshot_placement(usearch_amd_snapshot_t s, uint32_t* draws, uint32_t* kept, float* judge_ms, float* incumbent_ms,
                                     float* probe_ms) {
@@ -667,6 +671,22 @@ usearch_amd_builder_t usearch_amd_build(void const* vectors, size_t count, size_
 }
 
 void usearch_amd_build_free(usearch_amd_builder_t builder, usearch_amd_error_t*) { delete static_cast<builder_t*>(builder); }
+
+void usearch_amd_build_extend(usearch_amd_builder_t builder, void const* vectors, size_t count, size_t stride,
+                              usearch_amd_key_t const* keys, usearch_amd_error_t* error) try {
+    if (const char* e = static_cast<builder_t*>(builder)->extend(vectors, count, stride, false, keys, false))
+        fail(error, e);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+void usearch_amd_build_update(usearch_amd_builder_t builder, uint32_t const* slots, size_t count, void const* vectors, size_t stride,
+                              usearch_amd_key_t const* keys, usearch_amd_error_t* error) try {
+    if (const char* e = static_cast<builder_t*>(builder)->update(slots, count, vectors, stride, keys))
+        fail(error, e);
+} catch (...) {
+    fail_from_exception(error);
+}
 
 usearch_amd_snapshot_t usearch_amd_build_snapshot(usearch_amd_builder_t builder) {
     return &static_cast<builder_t*>(builder)->snapshot();

@@ -81,6 +81,8 @@ constexpr std::size_t default_expansion_search_k = 64;         ///< index.hpp:30
  *    upper_ref [size] u32                 index of the node's level-1 list inside `upper`, none_slot_k for level-0 nodes
  *    upper     [lists][m] u32             lists of levels 1..L of one node are consecutive; same cell convention
  *    keys      [size] u64                 node_t::key (index.hpp:2116-2137)
+ *    sketch    [size][128] bytes          optional, cos over f32 / f16 / bf16 rows of ≥ 1 536 bytes: 62 f16 coefficients of the
+ *                                         normalised row on fixed directions + the f32 norm of what they leave out (sketch.hpp)
  *    nbr0_rows [size][m0][16] bytes       optional, rows of ≤ 16 bytes (b1 × 128 …): the stored rows of a node's level-0
  *                                         neighbours next to each other, in list order — the per-hop gather of up to M0
  *                                         scattered 16-byte rows becomes one contiguous 16·M0-byte read (docs/format.md:7-28
@@ -103,6 +105,8 @@ struct snapshot_view_t {
     std::uint32_t max_level;
     std::uint32_t entry_slot;
     std::uint32_t has_tombstones; ///< any key == free_key_k: the `allow` predicate of index_dense.hpp:2071-2081 must run
+    const std::uint8_t* sketch;     ///< optional [size][128]: one record per member that can prove it too far (sketch.hpp); null = none
+    const float* sketch_directions; ///< [dimensions][64] f32: the directions of the sketch, transposed (column j = direction j)
 };
 
 /** One batch of queries, everything device-resident. */
@@ -160,6 +164,9 @@ struct search_args_t {
     std::uint32_t claim_bits;       ///< ≤ hash_cap; one bit per cell when equal, else cell & (bits − 1))
     std::uint32_t aside_offset;     ///< the cut for plain batches (`plain_ak`): where in the wave's LDS the members sit whose home cell in the
     std::uint32_t aside_cells;      ///< slab was taken, and how many cells (a power of two) — the slab is probed at the home cell only
+    unsigned long long* sketch_counters; ///< [2]: candidates tested against the sketch / pruned by it, summed over the launch; null = this
+                                         ///< launch walks without the sketch whatever the snapshot holds
+    std::uint32_t sketch_offset;    ///< where in the wave's LDS the query's 64 coefficients on the directions sit
 };
 
 enum : std::uint32_t { status_done_k = 0, status_overflow_k = 1 };

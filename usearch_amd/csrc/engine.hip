@@ -257,6 +257,8 @@ void snapshot_t::release() {
     if (!d_vectors_ && !d_nbr0_ && workspaces_.empty() && !stream_)
         return;
     (void)hipSetDevice(device_);
+    drop_sketch();
+    sketch_refused_ = false;
     for (void** p : {&d_vectors_, &d_nbr0_, &d_nbr0_rows_}) { // the gathered arrays may be mapped memory (placement.hpp)
         placed_free(*p);
         *p = nullptr;
@@ -389,6 +391,8 @@ const char* snapshot_t::try_matrix_placement(std::uint32_t expansion, const std:
 }
 
 const char* snapshot_t::finalize_layout() {
+    if (const char* e = finalize_sketch()) // the sketch of long cos rows (sketch.hpp); everything else gets none
+        return e;
     if (d_nbr0_rows_) {
         placed_free(d_nbr0_rows_);
         device_bytes_ -= std::min<std::size_t>(device_bytes_, (std::size_t)view_.size * view_.m0 * 16);
@@ -825,12 +829,21 @@ const char* snapshot_t::search_begin(search_call_t& call, const void* queries, s
                                                         : (std::uint32_t)env_size("USEARCH_AMD_WAVES_PER_CU", 32);
     call.waves_cap = std::min(waves_cap, variant_waves_per_cu);
 
+    // the sketch (sketch.hpp): plain and filtered searches of the finished graph walked by one wave per query in a build with twelve
+    // loads in flight (the others have no registers to spare: kernels.hpp); `tuning.sketch` = 1 turns it off for this call, 2 keeps
+    // auto mode from judging it by this call. Its 256 bytes of LDS per wave (plus alignment) count in every residency decision below.
+    if (tuning.sketch > 2)
+        return "Unknown sketch mode";
+    const bool sketch_use = view_.sketch && tuning.sketch != 1 && !team && mode_request != 3 &&
+                            (variant == variant_u12_w2_k || variant == variant_u12x2_w2_k) &&
+                            !(extras && (extras->query_ids || extras->beam_level || extras->descent_only || extras->reference_frontier));
+    const std::uint32_t sketch_lds = sketch_use ? sketch_columns_k * 4 + 16 : 0;
     auto lds_bytes_for = [&](int mode, std::uint32_t cap_next, std::uint32_t cap_hash) -> std::uint64_t {
         if (mode == scratch_global_k)
             return query_lds;
         const scratch_layout_t l = scratch_layout(entries_per_lane ? 0 : ef, cap_next,
                                                   mode == scratch_lds_k ? (std::uint64_t)cap_hash * 4 : 0);
-        return query_lds + l.total;
+        return query_lds + l.total + sketch_lds;
     };
     auto waves_for = [&](std::uint64_t lds_bytes) -> std::uint32_t {
         const std::uint64_t granule = (lds_bytes + lds_granule_k - 1) / lds_granule_k * lds_granule_k; // LDS is allocated in coarse granules
@@ -928,6 +941,10 @@ const char* snapshot_t::search_begin(search_call_t& call, const void* queries, s
         UA_HIP(hipMemsetAsync(args.phases, 0, 128, stream));
     }
     call.want_clock = tuning.wave_clock || env_size("USEARCH_AMD_WAVE_CLOCK", 0) != 0;
+    if (sketch_use) {
+        args.sketch_counters = reinterpret_cast<unsigned long long*>(ws.d_queue) + 1; // bytes 8 … 23 of the queue block
+        call.sketch_auto = tuning.sketch == 0;
+    }
 
     // ---- first launch: persistent waves, heaps in LDS. Nobody waits here.
     call.passes = 0;
@@ -961,7 +978,7 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
     auto timed_launch = [&](bool keep_overflows = false) -> const char* {
         // [0] the ticket counter, [1] how many queries outgrew their scratch — the latter is read once per rung, so the chunks of
         // the global rung must not erase what an earlier chunk counted
-        UA_HIP(hipMemsetAsync(ws.d_queue, 0, keep_overflows ? 4 : 8, stream));
+        UA_HIP(hipMemsetAsync(ws.d_queue, 0, keep_overflows ? 4 : 24, stream)); // (… [2 … 5] the sketch's two counters)
         if (call.timed)
             UA_HIP(hipEventRecord(ws.event_begin, stream));
         UA_HIP(launch_search(metric_, scalar_, params, view_, args));
@@ -1092,6 +1109,17 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
         }
         call.stats.plain = params.plain;
         call.stats.aside_cells = args.aside_cells;
+        // the query's 64 coefficients on the sketch's directions: 256 bytes behind the wave's other areas
+        args.sketch_offset = 0;
+        if (args.sketch_counters) {
+            const std::uint64_t offset = (wave_lds_bytes + 15) / 16 * 16;
+            if (!params.team && offset + sketch_columns_k * 4 <= lds_budget) {
+                args.sketch_offset = (std::uint32_t)offset;
+                wave_lds_bytes = offset + sketch_columns_k * 4;
+            } else {
+                args.sketch_counters = nullptr;
+            }
+        }
         const std::uint64_t lds_bytes = params.team ? (wave_lds_bytes + 15) / 16 * 16 + team_bytes : wave_lds_bytes;
         args.team_offset = params.team ? (std::uint32_t)((wave_lds_bytes + 15) / 16 * 16) : 0u;
         const std::uint32_t grid = params.team ? pending
@@ -1298,6 +1326,7 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
         args.scratch = ws.d_scratch;
         args.scratch_stride = slab;
         args.wave_clock = nullptr;
+        args.sketch_counters = nullptr;
         params.mode = scratch_global_k;
         params.team = 0;
         params.plain = 0;
@@ -1341,8 +1370,13 @@ const char* snapshot_t::search_finish(search_call_t& call, search_stats_t* stats
     //      fetched when the answer is yes. Second rung: visited set in the global hash, 4× the room for both structures.
     //      Third rung: global-memory scratch of exact size.
     for (int rung = 0;; ++rung) {
-        UA_HIP(hipMemcpyAsync(ws.h_status, ws.d_queue, 8, hipMemcpyDeviceToHost, stream));
+        UA_HIP(hipMemcpyAsync(ws.h_status, ws.d_queue, 24, hipMemcpyDeviceToHost, stream)); // the sketch's counters ride along
         UA_HIP(hipStreamSynchronize(stream));
+        if (call.args.sketch_counters) {
+            std::uint64_t counters[2];
+            std::memcpy(counters, ws.h_status + 2, 16);
+            call.stats.sketch_tested += counters[0], call.stats.sketch_pruned += counters[1];
+        }
         if (call.params.mode == scratch_global_k) {
             if (ws.h_status[1])
                 return "Search scratch overflow in the global-memory pass";
@@ -1434,6 +1468,8 @@ const char* snapshot_t::search_finish(search_call_t& call, search_stats_t* stats
     call.stats.lds_bytes = first_lds;
     if (stats)
         *stats = call.stats;
+    if (call.sketch_auto && call.count >= 1024)
+        judge_sketch(call.stats.sketch_tested, call.stats.sketch_pruned);
     return nullptr;
 }
 

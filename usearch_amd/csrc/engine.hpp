@@ -33,6 +33,7 @@ struct search_tuning_t {
     std::uint32_t frontier = 0;     ///< 0 = auto, 1 = the reference's heap (its pop order among equal distances), 2 = the open
                                     ///< cells of `top` (kernels.hpp frontier_top_k; refused where it does not apply)
     std::uint32_t wave_clock = 0;   ///< 1 = record every persistent wave's start / exit time (batch-tail telemetry)
+    std::uint32_t sketch = 0;       ///< 0 = auto (use the snapshot's sketch until it proves useless), 1 = off, 2 = on where eligible
 };
 
 struct search_stats_t {
@@ -55,6 +56,8 @@ struct search_stats_t {
     std::uint32_t early_rows = 0;        ///< rows of ≤ 128 bytes: 1 = gathered next to the probe of the visited set, not behind it
     std::uint32_t plain = 0;             ///< short rows: 1 = the last launch ran the build cut for plain batches (kernels.hpp `plain_ak`)
     std::uint32_t aside_cells = 0;       ///< … and its LDS cells for the members whose home cell in the slab was taken
+    std::uint64_t sketch_tested = 0;     ///< candidates of this call tested against the sketch (sketch.hpp) …
+    std::uint64_t sketch_pruned = 0;     ///< … and how many of them it proved too far: their rows were not fetched
 };
 
 /// What index construction asks of the search on top of a plain query batch (see search_args_t).
@@ -194,6 +197,7 @@ class snapshot_t {
         int mode = 0;
         bool timed = false, want_phases = false, want_clock = false, done = false, reran = false;
         bool plain_possible = false; ///< short rows: nothing known at search_begin rules the build cut for plain batches out (`plain_ak`)
+        bool sketch_auto = false;    ///< this call used the sketch in auto mode: its counters judge it (`judge_sketch`)
         bool keep_workspace = false; ///< search_finish leaves the workspace with the caller (who gives it back)
         float total_ms = 0.f;
         std::uint32_t passes = 0;
@@ -239,7 +243,12 @@ class snapshot_t {
     /// (`snapshot_view_t::nbr0_rows`) when rows are a single 16-byte chunk — b1 × 128, haversine … — so that a hop reads one
     /// contiguous block. Costs size × M0 × 16 bytes of HBM; USEARCH_AMD_INLINE_ROWS=0 turns it off.
     const char* finalize_layout();
-    void suspend_layout() { view_.nbr0_rows = nullptr; } ///< while the lists are being rewritten (construction)
+    void suspend_layout() { view_.nbr0_rows = nullptr, view_.sketch = nullptr; } ///< while the lists are being rewritten (construction)
+    /// The sketch of the stored rows (sketch.hpp), made or extended for the members the snapshot holds now: called by `finalize_layout`.
+    /// Members appended since get records under the same directions; an overwritten row makes everything anew. Not eligible: none.
+    const char* finalize_sketch();
+    const char* make_sketch();
+    bool has_sketch() const { return view_.sketch != nullptr; }
     std::uint32_t* mutable_nbr0() { return static_cast<std::uint32_t*>(d_nbr0_); }
     std::uint32_t* mutable_upper() { return static_cast<std::uint32_t*>(d_upper_); }
     hipStream_t stream() const { return stream_; }
@@ -302,6 +311,10 @@ class snapshot_t {
     /// times them), the faster one stays. Needs the matrix to itself (no other batch in flight); does nothing otherwise.
     const char* try_matrix_placement(std::uint32_t expansion, const std::function<const char*(const snapshot_view_t&, float&)>& launch, hipStream_t stream);
     void release();
+    void drop_sketch();
+    /// Auto mode: the first call of at least 1 024 queries that has the snapshot to itself judges the sketch; if it pruned less than a
+    /// quarter of what it tested, the snapshot frees the sketch and walks without one from then on.
+    void judge_sketch(std::uint64_t tested, std::uint64_t pruned);
 
     snapshot_view_t view_{};
     metric_kind_t metric_ = metric_unknown_k;
@@ -317,6 +330,13 @@ class snapshot_t {
     void* d_upper_ = nullptr;
     void* d_keys_ = nullptr;
     void* d_nbr0_rows_ = nullptr;
+    void* d_sketch_ = nullptr;            ///< [sketch_capacity_][128] records, the first sketch_rows_ of them filled
+    void* d_sketch_directions_ = nullptr; ///< [dimensions][64] f32
+    std::uint64_t sketch_rows_ = 0, sketch_capacity_ = 0;
+    double sketch_gram_defect_ = 0.0;
+    bool sketch_stale_ = false;   ///< a stored row was overwritten: its record no longer bounds it
+    bool sketch_refused_ = false; ///< auto mode found the sketch useless on this snapshot's data
+    bool sketch_judged_ = false;  ///< auto mode has passed its verdict on the sketch this snapshot holds (guarded by pool_mutex_)
     std::uint64_t build_capacity_ = 0, build_lists_capacity_ = 0; ///< room in the arrays above while an index is under construction
 
     placement_t placement_{};

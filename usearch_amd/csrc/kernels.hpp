@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "sketch.hpp"
 
 namespace usearch_amd {
 
@@ -1353,6 +1354,41 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
         }
     }
 
+    // ---- the sketch (sketch.hpp): cos over long float rows, one wave per query. The query's coefficients on the directions,
+    //      p̂ = (D a) / √Σa², go to LDS once: lane j owns direction j, the directions come transposed ([dimensions][64], 190 KB out of
+    //      L2 per query against megabytes of rows), sixteen loads in flight. A query whose Σa² is zero or not finite walks without it.
+    //      Only the builds with a whole row of twelve loads in flight carry the path (`u12`, `u12x2`: 241 and 256 registers of 256, no
+    //      spill); under the 128- and 168-register caps of the 4- and 8-load builds it tripled their spills (14 → 48, 2 → 16 VGPRs).
+    constexpr bool sketch_ak = metric_ak == metric_cos_k && f32_math<scalar_ak>() && lanes_ak == 8 && team_ak == 1 && !global_ak && !plain_ak &&
+                               unroll_ak % 100 == 12;
+    bool sketch_on = false;
+    float sketch_margin = 0.f;
+    std::uint32_t sketch_tested = 0, sketch_pruned = 0;
+    if constexpr (sketch_ak) {
+        if (ix.sketch && args.sketch_counters) {
+            const float* a = reinterpret_cast<const float*>(query_lds); // f16 / bf16 were widened when the query was staged
+            const float* column = ix.sketch_directions + lane;
+            float sums[4] = {0.f, 0.f, 0.f, 0.f};
+            std::uint32_t i = 0;
+            for (; i + 16 <= ix.dimensions; i += 16) {
+                float d[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u)
+                    d[u] = column[(std::size_t)(i + u) * sketch_columns_k];
+#pragma unroll
+                for (int u = 0; u < 16; ++u)
+                    sums[u & 3] = __builtin_fmaf(a[i + u], d[u], sums[u & 3]);
+            }
+            for (; i < ix.dimensions; ++i)
+                sums[0] = __builtin_fmaf(a[i], column[(std::size_t)i * sketch_columns_k], sums[0]);
+            const float projected = (sums[0] + sums[1]) + (sums[2] + sums[3]);
+            sketch_on = uniform_u32(sketch_norm_in_range((double)a2.f) ? 1u : 0u) != 0u; // (NaN: out of range)
+            reinterpret_cast<float*>(query_lds + args.sketch_offset)[lane] = sketch_on ? projected / __builtin_sqrtf(a2.f) : 0.f;
+            sketch_margin = sketch_slack(ix.dimensions);
+            wave_sync<false>();
+        }
+    }
+
     std::uint32_t computed = 0, cycles = 0; // context_t counters, index.hpp:2208-2211
     // `unroll_ak` carries the rows a lane group takes per round in its hundreds (search_kernel packs it that way)
     constexpr int loads_ak = unroll_ak % 100, rows_ak = unroll_ak / 100 + 1;
@@ -1361,7 +1397,77 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                                                                             count);
         computed += count;
     };
-    auto measure_hop = [&](std::uint32_t count) { // the beam: up to M0 fresh neighbours per hop
+    auto measure_hop = [&](std::uint32_t count, float radius_now) { // the beam: up to M0 fresh neighbours per hop
+        if constexpr (sketch_ak) {
+            // Once `top` is full a newcomer at d ≥ radius changes nothing — not `top`, not the frontier, not the radius — and its exact
+            // distance is never read: a PROOF of d ≥ radius does as well. The record of a candidate (one 128-byte line, eight lanes of
+            // 16 bytes) gives a lower bound of the distance this kernel would compute (sketch.hpp); a candidate whose bound reaches the
+            // radius of the hop's start (commits inside the hop only shrink it) keeps the bound as its distance — the commit test
+            // rejects it exactly as it would reject the true one — and only the others' rows are fetched. Same commits, same counters.
+            if (sketch_on && top.size == ef) {
+                const std::uint32_t sub = lane & 7u, group = lane >> 3;
+                const float* coefficients = reinterpret_cast<const float*>(query_lds + args.sketch_offset) + sub * 8;
+                const float4 q0 = *reinterpret_cast<const float4*>(coefficients), q1 = *reinterpret_cast<const float4*>(coefficients + 4);
+                const std::uint32_t my_slot = lane < count ? mem::load(cand_slots + lane) : 0u;
+                for (std::uint32_t base = 0; base < count; base += 32) {
+                    uint4 record[4]; // every record of the round is requested before the first one is used: one round trip
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const std::uint32_t ci = base + (std::uint32_t)r * 8 + group;
+                        record[r] = uint4{0u, 0u, 0u, 0u};
+                        if (ci < count)
+                            record[r] = *reinterpret_cast<const uint4*>(ix.sketch + (std::uint64_t)mem::load(cand_slots + ci) * sketch_record_bytes_k + sub * 16);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const std::uint32_t ci = base + (std::uint32_t)r * 8 + group;
+                        const uint4 v = record[r];
+                        const std::uint32_t last = sub == 7u ? 0u : v.w; // the last lane's last word is ρ, not two coefficients
+                        float dot = 0.f;
+                        dot = __builtin_fmaf(half_bits_to_float(v.x & 0xFFFFu), q0.x, dot);
+                        dot = __builtin_fmaf(half_bits_to_float(v.x >> 16), q0.y, dot);
+                        dot = __builtin_fmaf(half_bits_to_float(v.y & 0xFFFFu), q0.z, dot);
+                        dot = __builtin_fmaf(half_bits_to_float(v.y >> 16), q0.w, dot);
+                        dot = __builtin_fmaf(half_bits_to_float(v.z & 0xFFFFu), q1.x, dot);
+                        dot = __builtin_fmaf(half_bits_to_float(v.z >> 16), q1.y, dot);
+                        dot = __builtin_fmaf(half_bits_to_float(last & 0xFFFFu), q1.z, dot);
+                        dot = __builtin_fmaf(half_bits_to_float(last >> 16), q1.w, dot);
+                        float residual = sub == 7u ? __builtin_bit_cast(float, v.w) : 0.f;
+#pragma unroll
+                        for (int offset = 1; offset < 8; offset <<= 1) {
+                            dot += xor_lane(dot, offset);
+                            residual += xor_lane(residual, offset);
+                        }
+                        if (sub == 0u && ci < count)
+                            mem::store(cand_distances + ci, sketch_lower_bound(dot, residual, sketch_margin));
+                    }
+                }
+                wave_sync<false>();
+                const float bound = lane < count ? mem::load(cand_distances + lane) : 0.f;
+                const std::uint64_t survivors = ballot(lane < count && !(bound >= radius_now)); // a NaN bound proves nothing
+                const std::uint32_t kept = popcount64(survivors);
+                sketch_tested += count, sketch_pruned += count - kept;
+                if (kept < count) {
+                    const bool survivor = lane_bit(survivors);
+                    const std::uint32_t rank = rank_below(survivors, lane);
+                    wave_sync<false>(); // every lane has read its slot and its bound
+                    if (survivor)
+                        mem::store(cand_slots + rank, my_slot); // compacted, list order kept
+                    wave_sync<false>();
+                    if (kept)
+                        measure_rows<metric_ak, scalar_ak, lanes_ak, loads_ak, global_ak, rows_ak>(ix, query_lds, a2, cand_slots, cand_distances, kept);
+                    const float mine = survivor ? mem::load(cand_distances + rank) : bound;
+                    wave_sync<false>();
+                    if (lane < count) { // back to the hop's list positions
+                        mem::store(cand_slots + lane, my_slot);
+                        mem::store(cand_distances + lane, mine);
+                    }
+                    wave_sync<false>();
+                    computed += count;
+                    return;
+                }
+            }
+        }
         if constexpr (team_ak > 1) {
             // the leader of a team: publish the gather list, take the first share, meet the helpers again when all of it is measured
             if (lane == 0)
@@ -1931,7 +2037,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 if (fresh)
                     mem::store(cand_slots + rank_below(fresh_mask, lane), neighbor); // keeps list order
                 wave_sync<global_ak>();
-                measure_hop(count);
+                measure_hop(count, radius);
                 mine = lane < count ? mem::load(cand_distances + lane) : 0.f;
                 mine_slot = lane < count ? mem::load(cand_slots + lane) : 0u;
                 candidate = lane < count;
@@ -2003,6 +2109,12 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
         atomicAdd(args.phases + 10, (unsigned long long)diagnostic_rechecks);
     }
 #endif
+    if constexpr (sketch_ak) {
+        if (sketch_tested && lane == 0) {
+            atomicAdd(args.sketch_counters, (unsigned long long)sketch_tested);
+            atomicAdd(args.sketch_counters + 1, (unsigned long long)sketch_pruned);
+        }
+    }
     if (lane == 0) {
         args.counts[q] = found;
         args.visited[q] = cycles;

@@ -4,6 +4,8 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -242,4 +244,42 @@ extern "C" __attribute__((visibility("default"))) float usearch_amd_test_latency
     if (e != hipSuccess)
         fail(error, hipGetErrorString(e));
     return nanoseconds;
+}
+
+// ---- the sketch (sketch.hpp): the host twins of the record builder and of the bound the walk evaluates, for tests/test_sketch_bound.py.
+//      `rows` [count][stride] and `queries` [query_count][stride] in the storage kind; the directions are drawn from the rows as the
+//      engine draws them. Writes `bounds[query_count][count]` (−∞ where a row or a query is never pruned) and the number of directions.
+extern "C" __attribute__((visibility("default"))) void usearch_amd_test_sketch_bounds(const void* rows, size_t count, const void* queries,
+                                                                                      size_t query_count, size_t dimensions, int scalar_kind,
+                                                                                      size_t stride, float* bounds, uint32_t* rank,
+                                                                                      usearch_amd_error_t* error) {
+    using namespace usearch_amd;
+    const scalar_kind_t scalar = (scalar_kind_t)scalar_kind;
+    if (scalar != scalar_f32_k && scalar != scalar_f16_k && scalar != scalar_bf16_k)
+        return fail(error, "The sketch covers f32, f16 and bf16 rows");
+    const std::uint8_t* row_bytes = static_cast<const std::uint8_t*>(rows);
+    const std::uint8_t* query_bytes = static_cast<const std::uint8_t*>(queries);
+    const std::uint32_t samples = (std::uint32_t)std::min<std::size_t>(sketch_rank_k, count);
+    std::vector<double> wide((std::size_t)samples * dimensions);
+    for (std::uint32_t s = 0; s < samples; ++s)
+        for (std::size_t i = 0; i < dimensions; ++i)
+            wide[(std::size_t)s * dimensions + i] = (double)sketch_scalar(row_bytes + sketch_sample_slot(s, count) * stride, (std::uint32_t)i, scalar);
+    const sketch_directions_t directions = sketch_orthonormalise(wide, samples, (std::uint32_t)dimensions);
+    if (rank)
+        *rank = directions.rank;
+    std::vector<std::uint8_t> records(count * sketch_record_bytes_k);
+    for (std::size_t r = 0; r < count; ++r)
+        sketch_record_host(row_bytes + r * stride, scalar, (std::uint32_t)dimensions, directions, records.data() + r * sketch_record_bytes_k);
+    std::vector<float> query(dimensions), coefficients(sketch_columns_k);
+    for (std::size_t q = 0; q < query_count; ++q) {
+        float a2 = 0.f; // any summation order does: only its sign and finiteness matter here
+        for (std::size_t i = 0; i < dimensions; ++i) {
+            query[i] = sketch_scalar(query_bytes + q * stride, (std::uint32_t)i, scalar);
+            a2 = fmaf(query[i], query[i], a2);
+        }
+        const bool on = sketch_query_host(query.data(), a2, (std::uint32_t)dimensions, directions, coefficients.data());
+        for (std::size_t r = 0; r < count; ++r)
+            bounds[q * count + r] = on ? sketch_bound_host(coefficients.data(), records.data() + r * sketch_record_bytes_k, (std::uint32_t)dimensions)
+                                       : -INFINITY;
+    }
 }

@@ -44,7 +44,7 @@ def _infer_dtype(array: np.ndarray) -> str:
 class Tuning(C.Structure):
     """`usearch_amd_tuning_t`."""
     _fields_ = [("hash_cap", C.c_uint32), ("next_cap", C.c_uint32), ("variant", C.c_uint32), ("mode", C.c_uint32),
-                ("waves_per_cu", C.c_uint32), ("frontier", C.c_uint32), ("wave_clock", C.c_uint32), ("reserved", C.c_uint32)]
+                ("waves_per_cu", C.c_uint32), ("frontier", C.c_uint32), ("wave_clock", C.c_uint32), ("sketch", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -53,13 +53,14 @@ class Stats(C.Structure):
                 ("kernel_ms", C.c_float), ("mode", C.c_uint32), ("grid", C.c_uint32), ("lds_bytes", C.c_uint32),
                 ("frontier", C.c_uint32), ("variant", C.c_uint32), ("tail_idle", C.c_float), ("span_ms", C.c_float),
                 ("top_cells", C.c_uint32), ("probe_mode", C.c_uint32), ("seen_cells", C.c_uint32), ("claim_bits", C.c_uint32),
-                ("early_rows", C.c_uint32), ("plain", C.c_uint32), ("aside_cells", C.c_uint32)]
+                ("early_rows", C.c_uint32), ("plain", C.c_uint32), ("aside_cells", C.c_uint32),
+                ("sketch_tested", C.c_uint64), ("sketch_pruned", C.c_uint64)]
 
 
 class Arrays(C.Structure):
     """`usearch_amd_arrays_t`: device pointers and shapes of a snapshot's HBM arrays."""
     _fields_ = [("vectors", C.c_void_p), ("level0", C.c_void_p), ("keys", C.c_void_p), ("size", C.c_uint64),
-                ("row_stride", C.c_uint32), ("level0_cells", C.c_uint32), ("device", C.c_int), ("reserved", C.c_uint32)]
+                ("row_stride", C.c_uint32), ("level0_cells", C.c_uint32), ("device", C.c_int), ("sketch", C.c_uint32)]
 
 
 class JoinConfig(C.Structure):
@@ -118,7 +119,7 @@ EXPORTED_SYMBOLS = [
     "usearch_amd_filter_allowed", "usearch_amd_filter_device_bits", "usearch_amd_filter_free",
     "usearch_amd_filtered_search_many", "usearch_amd_filtered_search_many_device", "usearch_amd_filtered_exact_search_many",
     "usearch_amd_cast",
-    "usearch_amd_build", "usearch_amd_build_free", "usearch_amd_build_snapshot",
+    "usearch_amd_build", "usearch_amd_build_free", "usearch_amd_build_snapshot", "usearch_amd_build_extend", "usearch_amd_build_update",
     "usearch_amd_build_serialized_length", "usearch_amd_build_save_buffer", "usearch_amd_build_stats",
     "usearch_amd_join",
     # sharded search across GPUs (usearch_amd/sharded.py binds these)
@@ -240,6 +241,10 @@ def library() -> C.CDLL:
     L.usearch_amd_build.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_void_p,
                                     C.POINTER(BuildConfig), C.c_int, C.c_int, err_p]
     L.usearch_amd_build_free.argtypes = [C.c_void_p, err_p]
+    L.usearch_amd_build_extend.restype = None
+    L.usearch_amd_build_extend.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, err_p]
+    L.usearch_amd_build_update.restype = None
+    L.usearch_amd_build_update.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, err_p]
     L.usearch_amd_build_snapshot.restype = C.c_void_p
     L.usearch_amd_build_snapshot.argtypes = [C.c_void_p]
     L.usearch_amd_build_serialized_length.restype = C.c_size_t
@@ -797,6 +802,25 @@ class BuiltIndex:
     def serialized_length(self) -> int:
         return library().usearch_amd_build_serialized_length(self._builder)
 
+    def extend(self, vectors: np.ndarray, keys: Optional[np.ndarray] = None) -> None:
+        """Adds more members (rows of the storage kind) and links them in place (`usearch_amd_build_extend`)."""
+        vectors = np.ascontiguousarray(vectors)
+        keys = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
+        err = C.c_char_p()
+        library().usearch_amd_build_extend(C.c_void_p(self._builder), _pointer(vectors), len(vectors), vectors.strides[0], _pointer(keys),
+                                           C.byref(err))
+        _raise(err, "usearch_amd_build_extend")
+
+    def update(self, slots: np.ndarray, vectors: np.ndarray, keys: np.ndarray) -> None:
+        """Overwrites the members in `slots` with new rows and keys and links them anew in place (`usearch_amd_build_update`)."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        vectors, keys = np.ascontiguousarray(vectors), np.ascontiguousarray(keys, dtype=np.uint64)
+        assert len(slots) == len(vectors) == len(keys)
+        err = C.c_char_p()
+        library().usearch_amd_build_update(C.c_void_p(self._builder), _pointer(slots), len(slots), _pointer(vectors), vectors.strides[0],
+                                           _pointer(keys), C.byref(err))
+        _raise(err, "usearch_amd_build_update")
+
     def save_buffer(self) -> np.ndarray:
         image = np.empty(self.serialized_length, dtype=np.uint8)
         err = C.c_char_p()
@@ -949,7 +973,24 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_containers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                                             C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t),
                                                             C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_sketch_bounds.restype = None
+        _test_hooks.usearch_amd_test_sketch_bounds.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
+                                                               C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p)]
     return _test_hooks
+
+
+def test_sketch_bounds(rows: np.ndarray, queries: np.ndarray, dtype: str):
+    """Host twins of the sketch (csrc/sketch.hpp): records of `rows` under directions drawn from them, and for every (query, row)
+    the lower bound of the cos distance the walk would compare with its radius → (bounds [queries, rows] f32, number of directions)."""
+    rows, queries = np.ascontiguousarray(rows), np.ascontiguousarray(queries)
+    assert rows.ndim == 2 and queries.ndim == 2 and rows.shape[1] == queries.shape[1] and rows.dtype == queries.dtype
+    kind = {"f32": 11, "f16": 12, "bf16": 4}[dtype]  # scalar_kind_t of csrc/common.hpp
+    bounds = np.zeros((len(queries), len(rows)), dtype=np.float32)
+    rank, err = C.c_uint32(), C.c_char_p()
+    test_hooks().usearch_amd_test_sketch_bounds(_pointer(rows), len(rows), _pointer(queries), len(queries), rows.shape[1], kind,
+                                                rows.strides[0], _pointer(bounds), C.byref(rank), C.byref(err))
+    _raise(err, "usearch_amd_test_sketch_bounds")
+    return bounds, int(rank.value)
 
 
 def test_containers(kinds: np.ndarray, keys: np.ndarray, slots: np.ndarray, limit: int):
