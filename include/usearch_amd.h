@@ -549,6 +549,55 @@ USEARCH_AMD_EXPORT float usearch_amd_last_distances_ms(usearch_amd_snapshot_t sn
  */
 USEARCH_AMD_EXPORT int usearch_amd_cast(int from_kind, int to_kind, void const* input, size_t dimensions, void* output);
 
+/* ---- k-means clustering on the device ---------------------------------------------------------------------------------------
+ *  `kmeans_clustering_gt` (index_plugins.hpp:2199-2500; `usearch.index.kmeans`, python/usearch/index.py:1618-1712) with its
+ *  observable behaviour: points are cast to `quantization_kind`, seeds are `std::mt19937_64(seed)() % count` (the reference's
+ *  uniqueness test compares an assignment with a point index and does not keep them distinct), every point takes the nearest
+ *  centroid (lowest index among equals), centroids are f64 means (l2sq) / f64 sums scaled to unit norm (cos) / f64 sums (ip) of
+ *  their members cast back to `quantization_kind`, an empty cluster becomes the all-zero row. `last_iteration_inertia` is the
+ *  reference's |Σ − DBL_MAX| / DBL_MAX (its previous aggregate is never updated), so `inertia_threshold` below 1 never ends a run.
+ * -------------------------------------------------------------------------------------------------------------------------- */
+
+typedef struct usearch_amd_kmeans_config_t {
+    uint64_t struct_bytes;      /**< sizeof(usearch_amd_kmeans_config_t) */
+    int metric_kind;            /**< `usearch_metric_kind_t`: l2sq, cos or ip */
+    int quantization_kind;      /**< scalar kind the loop runs in: bf16, f16, i8 or f32 (f64 and b1 are refused) */
+    uint64_t max_iterations;    /**< at least 1 */
+    double inertia_threshold;   /**< 0 = no such exit */
+    double max_seconds;         /**< 0 = no such exit */
+    double min_shifts;          /**< a run ends when at most this share of the points changed centroid */
+    uint64_t seed;
+    int device;
+} usearch_amd_kmeans_config_t;
+
+typedef struct usearch_amd_kmeans_stats_t {
+    uint64_t iterations, last_iteration_points_shifted, computed_distances; /**< computed = count · clusters · iterations */
+    double last_iteration_inertia, aggregate_distance, runtime_seconds;
+    float assign_ms, update_ms; /**< HIP-event time of the assignment / update kernels, summed over the iterations */
+} usearch_amd_kmeans_stats_t;
+
+/**
+ *  Clusters `count` host rows of `scalar_kind` (`stride` bytes apart) into `clusters` groups. Writes the centroids in
+ *  `scalar_kind` (`centroids_stride` bytes apart), per point its centroid and the distance to it. `config` may be NULL: the
+ *  reference's defaults (l2sq, bf16, 300 iterations, 1e-4, 60 s, 0.01, seed 0, device 0). Refused with the reference's messages:
+ *  `max_iterations` < 1, `clusters` < 2, `clusters` >= `count`; by name: quantisation to f64 or b1, 2^32 points or more, sums
+ *  that do not fit in free device memory.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_kmeans(void const* points, size_t count, size_t stride, int scalar_kind, size_t dimensions,
+                                           size_t clusters, usearch_amd_kmeans_config_t const* config, void* centroids,
+                                           size_t centroids_stride, uint64_t* assignments, float* distances,
+                                           usearch_amd_kmeans_stats_t* stats, usearch_amd_error_t* error);
+
+/**
+ *  The assignment step alone: both host matrices (one `scalar_kind`) are cast to `quantization_kind` (0 = `scalar_kind`) on the
+ *  device, then every point gets the nearest centroid row under `metric_kind` — the lowest index among equals, index 0 with
+ *  FLT_MAX when every distance is a NaN.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_kmeans_assign(void const* points, size_t count, size_t stride, void const* centroids,
+                                                  size_t clusters, size_t centroids_stride, int scalar_kind, size_t dimensions,
+                                                  int metric_kind, int quantization_kind, int device, uint64_t* assignments,
+                                                  float* distances, usearch_amd_error_t* error);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@
 #include "filter.hpp"
 #include "join.hpp"
 #include "kernels.hpp"
+#include "kmeans.hpp"
 #include "sharded.hpp"
 
 using namespace usearch_amd;
@@ -759,6 +760,52 @@ size_t usearch_amd_join(usearch_amd_snapshot_t a, usearch_amd_snapshot_t b, usea
     return left.size();
 } catch (...) {
     return fail_from_exception(error), 0;
+}
+
+// ---- k-means clustering (kmeans.hpp)
+void usearch_amd_kmeans(void const* points, size_t count, size_t stride, int scalar_kind, size_t dimensions, size_t clusters,
+                        usearch_amd_kmeans_config_t const* config, void* centroids, size_t centroids_stride, uint64_t* assignments,
+                        float* distances, usearch_amd_kmeans_stats_t* stats, usearch_amd_error_t* error) try {
+    kmeans_config_t c; // the reference's defaults (index_plugins.hpp:2203-2209)
+    if (config) {
+        if (config->struct_bytes != sizeof(usearch_amd_kmeans_config_t))
+            return fail(error, "usearch_amd_kmeans_config_t::struct_bytes does not match this library");
+        c.metric = metric_from_c(config->metric_kind);
+        c.quantization = scalar_from_c(config->quantization_kind);
+        c.max_iterations = config->max_iterations;
+        c.inertia_threshold = config->inertia_threshold;
+        c.max_seconds = config->max_seconds;
+        c.min_shifts = config->min_shifts;
+        c.seed = config->seed;
+        c.device = config->device;
+    }
+    if (!points || !centroids || !assignments || !distances)
+        return fail(error, "k-means needs the points and all three output buffers");
+    kmeans_stats_t s;
+    if (const char* e = kmeans_run(static_cast<const std::uint8_t*>(points), count, stride, scalar_from_c(scalar_kind), dimensions, clusters,
+                                   c, static_cast<std::uint8_t*>(centroids), centroids_stride, assignments, distances, &s))
+        return fail(error, e);
+    if (stats) {
+        stats->iterations = s.iterations, stats->last_iteration_points_shifted = s.last_iteration_points_shifted;
+        stats->computed_distances = s.computed_distances, stats->last_iteration_inertia = s.last_iteration_inertia;
+        stats->aggregate_distance = s.aggregate_distance, stats->runtime_seconds = s.runtime_seconds;
+        stats->assign_ms = s.assign_ms, stats->update_ms = s.update_ms;
+    }
+} catch (...) {
+    fail_from_exception(error);
+}
+
+void usearch_amd_kmeans_assign(void const* points, size_t count, size_t stride, void const* centroids, size_t clusters,
+                               size_t centroids_stride, int scalar_kind, size_t dimensions, int metric_kind, int quantization_kind,
+                               int device, uint64_t* assignments, float* distances, usearch_amd_error_t* error) try {
+    if (!points || !centroids || !assignments || !distances)
+        return fail(error, "The assignment needs the points, the centroids and both output buffers");
+    const scalar_kind_t kind = scalar_from_c(scalar_kind);
+    fail(error, kmeans_assign(static_cast<const std::uint8_t*>(points), count, stride, static_cast<const std::uint8_t*>(centroids), clusters,
+                              centroids_stride, kind, dimensions, metric_from_c(metric_kind),
+                              quantization_kind ? scalar_from_c(quantization_kind) : kind, device, assignments, distances));
+} catch (...) {
+    fail_from_exception(error);
 }
 
 } // extern "C"

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "kmeans.hpp"
 #include "placement.hpp"
 
 typedef char const* usearch_amd_error_t;
@@ -282,4 +283,14 @@ extern "C" __attribute__((visibility("default"))) void usearch_amd_test_sketch_b
             bounds[q * count + r] = on ? sketch_bound_host(coefficients.data(), records.data() + r * sketch_record_bytes_k, (std::uint32_t)dimensions)
                                        : -INFINITY;
     }
+}
+
+// ---- k-means (kmeans.hip): the matrix the loop clusters — the caller's rows after the device cast, for tests/test_gpu_kmeans.py.
+//      `scalar_kind` / `quantization_kind`: scalar_kind_t of common.hpp.
+extern "C" __attribute__((visibility("default"))) void usearch_amd_test_kmeans_quantize(const void* points, size_t count, size_t stride,
+                                                                                        int scalar_kind, size_t dimensions,
+                                                                                        int quantization_kind, int device, void* out,
+                                                                                        size_t out_stride, usearch_amd_error_t* error) {
+    fail(error, kmeans_quantize(static_cast<const std::uint8_t*>(points), count, stride, (scalar_kind_t)scalar_kind, dimensions,
+                                (scalar_kind_t)quantization_kind, device, static_cast<std::uint8_t*>(out), out_stride));
 }

@@ -79,6 +79,23 @@ class JoinStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class KMeansConfig(C.Structure):
+    """`usearch_amd_kmeans_config_t`."""
+    _fields_ = [("struct_bytes", C.c_uint64), ("metric_kind", C.c_int), ("quantization_kind", C.c_int), ("max_iterations", C.c_uint64),
+                ("inertia_threshold", C.c_double), ("max_seconds", C.c_double), ("min_shifts", C.c_double), ("seed", C.c_uint64),
+                ("device", C.c_int)]
+
+
+class KMeansStats(C.Structure):
+    """`usearch_amd_kmeans_stats_t`."""
+    _fields_ = [("iterations", C.c_uint64), ("last_iteration_points_shifted", C.c_uint64), ("computed_distances", C.c_uint64),
+                ("last_iteration_inertia", C.c_double), ("aggregate_distance", C.c_double), ("runtime_seconds", C.c_double),
+                ("assign_ms", C.c_float), ("update_ms", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class BuildConfig(C.Structure):
     """`usearch_amd_build_config_t`; zeros = the reference's defaults."""
     _fields_ = [("connectivity", C.c_uint32), ("connectivity_base", C.c_uint32), ("expansion_add", C.c_uint32),
@@ -122,6 +139,7 @@ EXPORTED_SYMBOLS = [
     "usearch_amd_build", "usearch_amd_build_free", "usearch_amd_build_snapshot", "usearch_amd_build_extend", "usearch_amd_build_update",
     "usearch_amd_build_serialized_length", "usearch_amd_build_save_buffer", "usearch_amd_build_stats",
     "usearch_amd_join",
+    "usearch_amd_kmeans", "usearch_amd_kmeans_assign",
     # sharded search across GPUs (usearch_amd/sharded.py binds these)
     "usearch_amd_comm_unique_id", "usearch_amd_comm_init_rccl", "usearch_amd_comm_init_custom", "usearch_amd_comm_free",
     "usearch_amd_comm_rank", "usearch_amd_comm_world", "usearch_amd_comm_broadcast", "usearch_amd_sharded_search_many",
@@ -254,6 +272,12 @@ def library() -> C.CDLL:
     L.usearch_amd_join.restype = C.c_size_t
     L.usearch_amd_join.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(JoinConfig), C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.POINTER(JoinStats), err_p]
+    L.usearch_amd_kmeans.restype = None
+    L.usearch_amd_kmeans.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(KMeansConfig),
+                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(KMeansStats), err_p]
+    L.usearch_amd_kmeans_assign.restype = None
+    L.usearch_amd_kmeans_assign.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t,
+                                            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, err_p]
     _library = L
     return L
 
@@ -952,6 +976,68 @@ def cast(vector: np.ndarray, from_dtype: str, to_dtype: str, ndim: int) -> Optio
     return out if done else None
 
 
+METRIC_KINDS = {name: kind for kind, name in METRIC_NAMES.items()}
+
+
+def _matrix_to_cluster(X, dtype: Optional[str], what: str):
+    """The checks of the reference's binding (python/lib.cpp:580-583): a rank-2 array whose rows are contiguous."""
+    if not isinstance(X, np.ndarray) or X.ndim != 2:
+        raise ValueError(f"Expects a matrix (rank-2 tensor) of {what}!")
+    if X.strides[1] != X.itemsize:
+        raise ValueError(f"{what.capitalize()} rows must be contiguous, try `ascontiguousarray`.")
+    kind = "bf16" if X.dtype == np.uint16 else _infer_dtype(X)  # bf16 rows travel as their uint16 bit patterns
+    if dtype not in SCALAR_KINDS:
+        raise ValueError(f"Unsupported dtype {dtype}")
+    return kind
+
+
+def kmeans(X: np.ndarray, k: int, metric: str = "l2sq", dtype: str = "bf16", max_iterations: int = 300, inertia_threshold: float = 1e-4,
+           max_seconds: float = 60.0, min_shifts: float = 0.01, seed: Optional[int] = None, *, device: int = 0,
+           return_stats: bool = False):
+    """`usearch.index.kmeans` (python/usearch/index.py:1618-1712) on the device: clusters the rows of `X` into `k` groups, the loop
+    running in the scalar kind `dtype`. → (assignments uint64[N], distances float32[N], centroids [k, ndim] in X's dtype), and the
+    run's `KMeansStats` as a fourth element with `return_stats`. `seed=None` draws one from `os.urandom`. The reference's behaviour
+    is kept as it is, seeds that may repeat and an inertia exit that cannot fire included (csrc/kmeans.hip)."""
+    kind = _matrix_to_cluster(X, dtype, "dataset to cluster")
+    if metric not in METRIC_KINDS:
+        raise ValueError(f"Unsupported metric {metric}")
+    if seed is None:
+        seed = int.from_bytes(os.urandom(8), "little")
+    count, ndim = X.shape
+    config = KMeansConfig(C.sizeof(KMeansConfig), METRIC_KINDS[metric], SCALAR_KINDS[dtype], int(max_iterations), float(inertia_threshold),
+                          float(max_seconds), float(min_shifts), int(seed) & (2**64 - 1), int(device))
+    assignments = np.zeros(count, dtype=np.uint64)
+    distances = np.zeros(count, dtype=np.float32)
+    centroids = np.zeros((max(int(k), 0), ndim), dtype=X.dtype)
+    stats, err = KMeansStats(), C.c_char_p()
+    library().usearch_amd_kmeans(_pointer(X), count, X.strides[0], SCALAR_KINDS[kind], ndim, max(int(k), 0), C.byref(config),
+                                 _pointer(centroids), centroids.strides[0], _pointer(assignments), _pointer(distances), C.byref(stats),
+                                 C.byref(err))
+    if err.value:
+        raise ValueError(err.value.decode())  # the reference's binding raises the class's message as a ValueError (python/lib.cpp:159)
+    return (assignments, distances, centroids, stats) if return_stats else (assignments, distances, centroids)
+
+
+def kmeans_assign(X: np.ndarray, centroids: np.ndarray, metric: str = "l2sq", dtype: str = "bf16", *, device: int = 0):
+    """The assignment step of `kmeans` alone: rows of `X` and of `centroids` (one numpy dtype) are cast to `dtype` on the device and
+    every point gets its nearest centroid, the lowest index among equals → (assignments uint64[N], distances float32[N])."""
+    kind = _matrix_to_cluster(X, dtype, "dataset to assign")
+    if _matrix_to_cluster(centroids, dtype, "centroids") != kind or centroids.shape[1] != X.shape[1]:
+        raise ValueError("The points and the centroids must have one dtype and one number of dimensions")
+    if metric not in METRIC_KINDS:
+        raise ValueError(f"Unsupported metric {metric}")
+    count, ndim = X.shape
+    assignments = np.zeros(count, dtype=np.uint64)
+    distances = np.zeros(count, dtype=np.float32)
+    err = C.c_char_p()
+    library().usearch_amd_kmeans_assign(_pointer(X), count, X.strides[0], _pointer(centroids), len(centroids), centroids.strides[0],
+                                        SCALAR_KINDS[kind], ndim, METRIC_KINDS[metric], SCALAR_KINDS[dtype], int(device),
+                                        _pointer(assignments), _pointer(distances), C.byref(err))
+    if err.value:
+        raise ValueError(err.value.decode())
+    return assignments, distances
+
+
 TEST_HOOKS_PATH = os.path.join(os.path.dirname(LIBRARY_PATH), "libusearch_amd_testhooks.so")
 _test_hooks = None
 
@@ -976,7 +1062,24 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_sketch_bounds.restype = None
         _test_hooks.usearch_amd_test_sketch_bounds.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
                                                                C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_kmeans_quantize.restype = None
+        _test_hooks.usearch_amd_test_kmeans_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int,
+                                                                 C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
     return _test_hooks
+
+
+def test_kmeans_quantize(X: np.ndarray, from_dtype: str, to_dtype: str, device: int = 0) -> np.ndarray:
+    """The matrix `kmeans` clusters: the rows of `X` after the device cast (csrc/kmeans.hip) → uint8 [N, bytes per quantised row]."""
+    X = np.ascontiguousarray(X)
+    kinds = {"bf16": 4, "f64": 10, "f32": 11, "f16": 12, "i8": 23}  # scalar_kind_t of csrc/common.hpp
+    count, ndim = X.shape
+    width = {"i8": ndim, "f16": 2 * ndim, "bf16": 2 * ndim, "f32": 4 * ndim}[to_dtype]
+    out = np.zeros((count, width), dtype=np.uint8)
+    err = C.c_char_p()
+    test_hooks().usearch_amd_test_kmeans_quantize(_pointer(X), count, X.strides[0], kinds[from_dtype], ndim, kinds[to_dtype], device,
+                                                  _pointer(out), out.strides[0], C.byref(err))
+    _raise(err, "usearch_amd_test_kmeans_quantize")
+    return out
 
 
 def test_sketch_bounds(rows: np.ndarray, queries: np.ndarray, dtype: str):
