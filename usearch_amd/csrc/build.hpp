@@ -80,6 +80,22 @@ class builder_t {
     /// matching). No relinking.
     const char* set_key(std::uint64_t slot, std::uint64_t key);
 
+    /**
+     *  Takes over an index somebody else built: `image` is uploaded as it stands (snapshot_t::build — the graph is the image's,
+     *  nothing is linked) and levels, keys, size, entry point and top level are read from it, so that `isolate`, `compact`,
+     *  `save_buffer`, `extend` and `update` work on it as on an index built here. `config` supplies what an image does not record
+     *  (expansion_add, seed, batch shape); connectivity comes from the image and must be within the device builder's limits.
+     */
+    const char* adopt(const image_t& image, const build_config_t& config, int device);
+
+    /// `set_key(slot, free_key_k)` for many members at once: they keep routing and stop matching.
+    const char* remove(const std::uint32_t* slots, std::uint64_t count);
+    /// `snapshot_t::isolate` on the index under construction.
+    const char* isolate(compact_stats_t* stats);
+    /// `snapshot_t::compact`, with levels, keys, size, list count, entry point and top level of the builder brought in line:
+    /// `save_buffer`, `extend` and `update` go on working over the survivors.
+    const char* compact(const compact_config_t& config, std::uint32_t* slot_map, compact_stats_t* stats);
+
     snapshot_t& snapshot() { return snapshot_; }
     const build_stats_t& stats() const { return stats_; }
     std::uint64_t size() const { return size_; }

@@ -17,6 +17,7 @@
 
 #include "build.hpp"
 #include "casts.hpp"
+#include "compact.hpp"
 #include "engine.hpp"
 #include "filter.hpp"
 #include "join.hpp"
@@ -716,6 +717,75 @@ void usearch_amd_build_stats(usearch_amd_builder_t builder, usearch_amd_build_st
     out->seconds_link = s.seconds_link, out->seconds_upload = s.seconds_upload;
     out->max_level = s.max_level;
     out->refiled_requests = s.refiled_requests;
+}
+
+// ---- isolate and compact (compact.hpp)
+namespace {
+
+compact_config_t compact_config_from_c(usearch_amd_compact_config_t const* config) {
+    compact_config_t c;
+    if (config && config->struct_bytes >= offsetof(usearch_amd_compact_config_t, staging_bytes) + sizeof(config->staging_bytes))
+        c.staging_bytes = config->staging_bytes;
+    return c;
+}
+
+void compact_stats_to_c(const compact_stats_t& s, usearch_amd_compact_stats_t* out) {
+    if (!out)
+        return;
+    *out = usearch_amd_compact_stats_t{};
+    out->pruned_edges = s.pruned_edges, out->removed_members = s.removed_members, out->survivors = s.survivors;
+    out->moved_bytes = s.moved_bytes, out->chunks = s.chunks;
+    out->new_entry_slot = s.new_entry_slot, out->new_max_level = s.new_max_level;
+    out->scan_ms = s.scan_ms, out->lists_ms = s.lists_ms, out->rows_ms = s.rows_ms;
+}
+
+} // namespace
+
+void usearch_amd_snapshot_isolate(usearch_amd_snapshot_t snapshot, usearch_amd_compact_stats_t* stats, usearch_amd_error_t* error) try {
+    compact_stats_t s;
+    if (const char* e = as_snapshot(snapshot)->isolate(&s))
+        return fail(error, e);
+    compact_stats_to_c(s, stats);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+void usearch_amd_snapshot_compact(usearch_amd_snapshot_t snapshot, usearch_amd_compact_config_t const* config, uint32_t* slot_map,
+                                  usearch_amd_compact_stats_t* stats, usearch_amd_error_t* error) try {
+    compact_stats_t s;
+    if (const char* e = as_snapshot(snapshot)->compact(compact_config_from_c(config), slot_map, &s))
+        return fail(error, e);
+    compact_stats_to_c(s, stats);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+uint32_t usearch_amd_compact_scan_chunk(void) { return compact_scan_chunk_k; }
+
+void usearch_amd_build_remove(usearch_amd_builder_t builder, uint32_t const* slots, size_t count, usearch_amd_error_t* error) try {
+    if (const char* e = static_cast<builder_t*>(builder)->remove(slots, count))
+        fail(error, e);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+void usearch_amd_build_isolate(usearch_amd_builder_t builder, usearch_amd_compact_stats_t* stats, usearch_amd_error_t* error) try {
+    compact_stats_t s;
+    if (const char* e = static_cast<builder_t*>(builder)->isolate(&s))
+        return fail(error, e);
+    compact_stats_to_c(s, stats);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+void usearch_amd_build_compact(usearch_amd_builder_t builder, usearch_amd_compact_config_t const* config, uint32_t* slot_map,
+                               usearch_amd_compact_stats_t* stats, usearch_amd_error_t* error) try {
+    compact_stats_t s;
+    if (const char* e = static_cast<builder_t*>(builder)->compact(compact_config_from_c(config), slot_map, &s))
+        return fail(error, e);
+    compact_stats_to_c(s, stats);
+} catch (...) {
+    fail_from_exception(error);
 }
 
 int usearch_amd_cast(int from_kind, int to_kind, void const* input, size_t dimensions, void* output) {

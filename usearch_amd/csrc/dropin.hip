@@ -38,6 +38,7 @@
 #include "build.hpp"
 #include "casts.hpp"
 #include "combiner.hpp"
+#include "compact.hpp"
 #include "engine.hpp"
 #include "filter.hpp"
 #include "host_util.hpp"
@@ -298,6 +299,37 @@ struct index_t {
         drop_device();
         drop_image();
         lookup_valid = false;
+    }
+
+    /// `usearch_isolate` / `usearch_compact` on an index that is still its image: the image's graph goes to the device as it
+    /// stands and a builder takes it over (`builder_t::adopt` — nothing is linked anew), keys and vectors move into the staging
+    /// arrays, and the image is left behind: from here on the index is served and saved from its device state.
+    const char* adopt_image() {
+        if (staged || !has_image)
+            return nullptr;
+        builder_t* fresh = new (std::nothrow) builder_t();
+        if (!fresh)
+            return "Out of memory!";
+        delete snapshot, snapshot = nullptr; // the HBM copy of the image: the builder uploads its own
+        build_config_t config;
+        config.expansion_add = (std::uint32_t)expansion_add;
+        if (const char* e = fresh->adopt(image, config, device)) {
+            delete fresh;
+            return e;
+        }
+        image_keys(keys);
+        vectors.assign(image.vectors, image.vectors + (std::size_t)image.size * image.cols);
+        free_slots.clear(), free_head = 0, recycled.clear();
+        for (std::size_t slot = 0; slot < keys.size(); ++slot)
+            if (keys[slot] == free_key_k)
+                free_slots.push_back((std::uint32_t)slot);
+        staged = true;
+        ++version;
+        memos.clear();
+        delete builder, builder = fresh;
+        drop_image();
+        lookup_valid = false;
+        return nullptr;
     }
 
     const std::unordered_multimap<std::uint64_t, std::uint32_t>& key_lookup() {
@@ -1443,6 +1475,82 @@ void usearch_gpu_sync(usearch_index_t handle, usearch_error_t* error) {
         snapshot_t* device_index = nullptr;
         if (const char* e = index.ready(&device_index))
             fail(error, e);
+    });
+}
+
+size_t usearch_isolate(usearch_index_t handle, usearch_error_t* error) {
+    index_t& index = *as_index(handle);
+    return guarded(error, std::size_t(0), [&] {
+        unique_lock_t lock(index.mutex);
+        if (!index.staged) {
+            if (!index.has_image || !index.image.count_deleted)
+                return std::size_t(0); // nobody was removed: no list names a removed member
+            if (const char* e = index.adopt_image()) { // the lists change: the image no longer describes the index
+                fail(error, e);
+                return std::size_t(0);
+            }
+        }
+        snapshot_t* device_index = nullptr;
+        if (const char* e = index.ready(&device_index)) { // links what `usearch_add` deferred, as a save does
+            fail(error, e);
+            return std::size_t(0);
+        }
+        if (!index.builder)
+            return std::size_t(0);
+        compact_stats_t stats;
+        if (const char* e = index.builder->isolate(&stats)) {
+            fail(error, e);
+            return std::size_t(0);
+        }
+        return (std::size_t)stats.pruned_edges;
+    });
+}
+
+size_t usearch_compact(usearch_index_t handle, usearch_error_t* error) {
+    index_t& index = *as_index(handle);
+    return guarded(error, std::size_t(0), [&] {
+        unique_lock_t lock(index.mutex);
+        if (!index.staged) {
+            if (!index.has_image || !index.image.count_deleted)
+                return std::size_t(0);
+            if (const char* e = index.adopt_image()) { // from here on the index is served and saved from its device state
+                fail(error, e);
+                return std::size_t(0);
+            }
+        }
+        snapshot_t* device_index = nullptr;
+        if (const char* e = index.ready(&device_index)) {
+            fail(error, e);
+            return std::size_t(0);
+        }
+        if (!index.builder)
+            return std::size_t(0);
+        std::vector<std::uint32_t> slot_map(index.keys.size());
+        compact_stats_t stats;
+        if (const char* e = index.builder->compact(compact_config_t{}, slot_map.data(), &stats)) {
+            fail(error, e);
+            return std::size_t(0);
+        }
+        if (!stats.removed_members)
+            return std::size_t(0);
+        // the staging arrays follow the same map: new slot ≤ old slot, so everything moves down in place
+        const std::size_t bytes = index.bpv();
+        for (std::size_t slot = 0; slot < slot_map.size(); ++slot) {
+            const std::uint32_t to = slot_map[slot];
+            if (to == none_slot_k || to == slot)
+                continue;
+            index.keys[to] = index.keys[slot];
+            std::memmove(index.vectors.data() + (std::size_t)to * bytes, index.vectors.data() + slot * bytes, bytes);
+        }
+        index.keys.resize((std::size_t)stats.survivors);
+        index.vectors.resize((std::size_t)stats.survivors * bytes);
+        index.free_slots.clear(), index.free_head = 0, index.recycled.clear();
+        index.lookup_valid = false;
+        ++index.version; // a `usearch_filter_t` made before describes the old numbering
+        index.memos.clear();
+        if (!stats.survivors)
+            delete index.builder, index.builder = nullptr; // staged and empty: the next add builds anew
+        return (std::size_t)stats.removed_members;
     });
 }
 

@@ -22,6 +22,9 @@
 
 namespace usearch_amd {
 
+struct compact_config_t; // compact.hpp
+struct compact_stats_t;
+
 /// Tunables of one search launch; zeros mean "choose for me".
 struct search_tuning_t {
     std::uint32_t hash_cap = 0;     ///< visited-set cells per query (power of two)
@@ -234,6 +237,9 @@ class snapshot_t {
     std::uint64_t mutations() const { return mutations_; }
     std::uint64_t build_capacity() const { return build_capacity_; }
     std::uint64_t build_lists_capacity() const { return build_lists_capacity_; }
+    /// A snapshot loaded from an image becomes the arrays of an index under construction (builder_t::adopt): they are exactly
+    /// full, which is what `grow_for_build` has to know to keep what is linked when more members arrive.
+    void adopt_for_build() { build_capacity_ = view_.size, build_lists_capacity_ = upper_lists_ > 1 ? upper_lists_ : 1; }
     void set_upper_lists(std::uint64_t lists) { upper_lists_ = lists; }
     void set_frontier(std::uint64_t size, std::uint32_t entry_slot, std::uint32_t max_level) {
         view_.size = size, view_.entry_slot = entry_slot, view_.max_level = max_level;
@@ -289,6 +295,19 @@ class snapshot_t {
     /// out[q][j] = metric(query q, stored row slots[q][j]); host buffers, queries in storage kind.
     const char* distances_host(const void* queries, std::size_t count, std::size_t stride_bytes,
                                const std::uint32_t* slots, std::size_t slots_per_query, float* out);
+
+    /**
+     *  `index_dense_gt::isolate` (index_dense.hpp:1709-1720 → index.hpp:3700-3728) on the device: every neighbour whose key is
+     *  `free_key_k` leaves every list of every member, the rest of a list keeps its order. Nothing else moves. Refused while search
+     *  workspaces are leased. compact.hip.
+     */
+    const char* isolate(compact_stats_t* stats);
+    /**
+     *  `isolate`, then the removed members leave for good: survivors are renumbered by their rank (stable), lists, keys and rows
+     *  follow, `has_tombstones` is cleared (compact.hpp has the rules). `slot_map` (host, optional): [old size] old slot → new slot,
+     *  `none_slot_k` for removed members. Refused while search workspaces are leased.
+     */
+    const char* compact(const compact_config_t& config, std::uint32_t* slot_map, compact_stats_t* stats);
 
     /// Leases a workspace (waits while `concurrency()` of them are out); `give_back` returns it. RAII: `lease_t`.
     const char* take(workspace_t*& out);

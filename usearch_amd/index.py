@@ -115,6 +115,22 @@ class BuildStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class CompactConfig(C.Structure):
+    """`usearch_amd_compact_config_t`."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("staging_bytes", C.c_size_t)]
+
+
+class CompactStats(C.Structure):
+    """`usearch_amd_compact_stats_t`."""
+    _fields_ = [("pruned_edges", C.c_uint64), ("removed_members", C.c_uint64), ("survivors", C.c_uint64),
+                ("moved_bytes", C.c_uint64), ("chunks", C.c_uint64), ("new_entry_slot", C.c_uint32),
+                ("new_max_level", C.c_uint32), ("scan_ms", C.c_float), ("lists_ms", C.c_float), ("rows_ms", C.c_float),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 _library = None
 
 EXPORTED_SYMBOLS = [
@@ -138,6 +154,8 @@ EXPORTED_SYMBOLS = [
     "usearch_amd_cast",
     "usearch_amd_build", "usearch_amd_build_free", "usearch_amd_build_snapshot", "usearch_amd_build_extend", "usearch_amd_build_update",
     "usearch_amd_build_serialized_length", "usearch_amd_build_save_buffer", "usearch_amd_build_stats",
+    "usearch_amd_snapshot_isolate", "usearch_amd_snapshot_compact", "usearch_amd_compact_scan_chunk",
+    "usearch_amd_build_remove", "usearch_amd_build_isolate", "usearch_amd_build_compact",
     "usearch_amd_join",
     "usearch_amd_kmeans", "usearch_amd_kmeans_assign",
     # sharded search across GPUs (usearch_amd/sharded.py binds these)
@@ -269,6 +287,18 @@ def library() -> C.CDLL:
     L.usearch_amd_build_serialized_length.argtypes = [C.c_void_p]
     L.usearch_amd_build_save_buffer.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, err_p]
     L.usearch_amd_build_stats.argtypes = [C.c_void_p, C.POINTER(BuildStats)]
+    L.usearch_amd_snapshot_isolate.restype = None
+    L.usearch_amd_snapshot_isolate.argtypes = [C.c_void_p, C.POINTER(CompactStats), err_p]
+    L.usearch_amd_snapshot_compact.restype = None
+    L.usearch_amd_snapshot_compact.argtypes = [C.c_void_p, C.POINTER(CompactConfig), C.c_void_p, C.POINTER(CompactStats), err_p]
+    L.usearch_amd_compact_scan_chunk.restype = C.c_uint32
+    L.usearch_amd_compact_scan_chunk.argtypes = []
+    L.usearch_amd_build_remove.restype = None
+    L.usearch_amd_build_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, err_p]
+    L.usearch_amd_build_isolate.restype = None
+    L.usearch_amd_build_isolate.argtypes = [C.c_void_p, C.POINTER(CompactStats), err_p]
+    L.usearch_amd_build_compact.restype = None
+    L.usearch_amd_build_compact.argtypes = [C.c_void_p, C.POINTER(CompactConfig), C.c_void_p, C.POINTER(CompactStats), err_p]
     L.usearch_amd_join.restype = C.c_size_t
     L.usearch_amd_join.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(JoinConfig), C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.POINTER(JoinStats), err_p]
@@ -793,6 +823,40 @@ class Index:
         stats = getattr(self, "_join_stats", None)
         return stats.as_dict() if stats is not None else {}
 
+    def isolate(self) -> int:
+        """`index_dense_gt::isolate`: members whose key is the tombstone value leave every neighbour list, the rest of each list keeps
+        its order. Returns the number of list cells erased; `compact_stats` has the rest."""
+        stats, err = CompactStats(), C.c_char_p()
+        if self._owner is not None:
+            library().usearch_amd_build_isolate(self._owner._builder, C.byref(stats), C.byref(err))
+        else:
+            library().usearch_amd_snapshot_isolate(self._handle, C.byref(stats), C.byref(err))
+        _raise(err, "usearch_amd_snapshot_isolate")
+        self._compact_stats = stats
+        return int(stats.pruned_edges)
+
+    def compact(self, staging_bytes: int = 0, slot_map: bool = False):
+        """`isolate`, then the removed members leave the index for good: survivors keep their order and are renumbered by rank, and
+        the index has no tombstones afterwards (not the reference's `compact`, which permutes slots and keeps them). The stored
+        rows move in place through a staging buffer of `staging_bytes` (0 = 64 MiB). Filters made before are refused afterwards.
+        Returns the number of members dropped, or with `slot_map` the u32 array old slot → new slot (0xFFFFFFFF = removed)."""
+        stats, err = CompactStats(), C.c_char_p()
+        config = CompactConfig(C.sizeof(CompactConfig), staging_bytes)
+        mapping = np.empty(self.size, dtype=np.uint32) if slot_map else None
+        if self._owner is not None:  # the builder's levels and keys follow
+            library().usearch_amd_build_compact(self._owner._builder, C.byref(config), _pointer(mapping), C.byref(stats), C.byref(err))
+        else:
+            library().usearch_amd_snapshot_compact(self._handle, C.byref(config), _pointer(mapping), C.byref(stats), C.byref(err))
+        _raise(err, "usearch_amd_snapshot_compact")
+        self._compact_stats = stats
+        return mapping if slot_map else int(stats.removed_members)
+
+    @property
+    def compact_stats(self) -> dict:
+        """Numbers of the last `isolate` / `compact` on this index (`usearch_amd_compact_stats_t`)."""
+        stats = getattr(self, "_compact_stats", None)
+        return stats.as_dict() if stats is not None else {}
+
     def distances(self, queries: np.ndarray, slots: np.ndarray) -> np.ndarray:
         """out[q, j] = metric(queries[q], stored vector of slot slots[q, j]); queries in the storage kind."""
         queries = np.ascontiguousarray(queries)
@@ -844,6 +908,25 @@ class BuiltIndex:
         library().usearch_amd_build_update(C.c_void_p(self._builder), _pointer(slots), len(slots), _pointer(vectors), vectors.strides[0],
                                            _pointer(keys), C.byref(err))
         _raise(err, "usearch_amd_build_update")
+
+    def remove(self, slots, compact: bool = False) -> int:
+        """Turns the members in `slots` into tombstones (`usearch_amd_build_remove`): they keep routing and stop matching. `compact`
+        is the reference's keyword (python/lib.cpp:811-818): True calls `isolate` afterwards. Returns the number removed."""
+        slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.uint32)
+        err = C.c_char_p()
+        library().usearch_amd_build_remove(C.c_void_p(self._builder), _pointer(slots), len(slots), C.byref(err))
+        _raise(err, "usearch_amd_build_remove")
+        if compact:
+            self.isolate()
+        return len(slots)
+
+    def isolate(self) -> int:
+        """`Index.isolate` on the built index."""
+        return self.index.isolate()
+
+    def compact(self, staging_bytes: int = 0, slot_map: bool = False):
+        """`Index.compact` on the built index: `save_buffer`, `extend` and `update` go on working over the survivors."""
+        return self.index.compact(staging_bytes, slot_map)
 
     def save_buffer(self) -> np.ndarray:
         image = np.empty(self.serialized_length, dtype=np.uint8)
