@@ -188,17 +188,23 @@ static const uint8_t* vector_at(const uo_index_t* ix, uint64_t slot) { return ix
  *  Metrics (index_plugins.hpp:1309-1657, dispatch 1930-2008). Float accumulation layout is explicit — see header.
  *
  *  Which struct the reference instantiates per (metric, scalar) — `configure_with_autovec`, 1930-2008:
- *    ip / cos / l2sq / pearson   bf16, f16, f32 → result f32;  f64 → result f64;  i8 → metric_{cos,l2sq}_i8_t (int32) or
- *                                metric_{ip,pearson}_gt<i8_t, f32_t> (float accumulation of small integers)
- *    divergence                  bf16, f16, f32 (f32 arithmetic), f64;   haversine  f32, f64 (first two scalars)
+ *    ip / cos / l2sq             bf16, f16, f32 → result f32;  f64 → result f64;  i8 → metric_{cos,l2sq}_i8_t (int32) or
+ *                                metric_ip_gt<i8_t, f32_t> (float accumulation of small integers)
+ *    pearson, divergence         result f32 for EVERY scalar in the reference, f64 included: `result_at` defaults to float (1511,
+ *                                1555) and the dispatch passes no other (1973, 1997), so f64 elements are narrowed one by one and
+ *                                every sum is a float. divergence is restated so; pearson over f64 still in DOUBLE (like the
+ *                                kernels: DESIGN.md §3.4). pearson also takes i8 (metric_pearson_gt<i8_t, f32_t>).
+ *    haversine                   f32, f64 (first two scalars), result = scalar
  *    hamming / tanimoto (= jaccard) / sorensen   b1x8 bytes
  *  Every result is narrowed to `float` (distance_punned_t, 1660; `equidimensional_`, 2010-2014).
  * ---------------------------------------------------------------------------------------------------------------- */
 #define UO_CHUNK 16 /* bytes dealt to one lane at a time */
 #define UO_MAX_LANES 64
 
+static double load_f64(const uint8_t* p, uint64_t i) { double d; memcpy(&d, p + 8 * i, 8); return d; }
 static float load_float(uint8_t scalar_kind, const uint8_t* p, uint64_t i) {
     switch (scalar_kind) {
+    case UO_SCALAR_F64: return (float)load_f64(p, i); /* `static_cast<result_t>` of divergence (1570) */
     case UO_SCALAR_F32: { float f; memcpy(&f, p + 4 * i, 4); return f; }
     case UO_SCALAR_F16: return f16_to_f32(ld16(p + 2 * i));
     case UO_SCALAR_BF16: { uint32_t b = (uint32_t)ld16(p + 2 * i) << 16; float f; memcpy(&f, &b, 4); return f; }
@@ -206,11 +212,10 @@ static float load_float(uint8_t scalar_kind, const uint8_t* p, uint64_t i) {
     default: return 0.f;
     }
 }
-static double load_f64(const uint8_t* p, uint64_t i) { double d; memcpy(&d, p + 8 * i, 8); return d; }
 
 /* The running sums of every equidimensional metric: ab = Σab, a2 = Σa², b2 = Σb², l2 = Σ(a-b)² (ip, cos, l2sq);
- * sa = Σa, sb = Σb (pearson, 1478-1520); kp, kq = the two Kullback-Leibler sums of divergence (1526-1551). Generated
- * twice: f32 arithmetic (result_t = f32_t) and f64 arithmetic (result_t = f64_t).
+ * sa = Σa, sb = Σb (pearson, 1511-1550); kp, kq = the two Kullback-Leibler sums of divergence (1555-1578). Generated
+ * twice: f32 arithmetic (result_t = f32_t) and f64 arithmetic (result_t = f64_t; ip, cos, l2sq and, for now, pearson over f64).
  *
  * lanes <= 0: the reference loop order — one chain per accumulator in element order, unfused multiply-add. The
  * reference lets the compiler reassociate (`omp simd reduction`), so last-bit agreement with one particular build of
@@ -270,8 +275,15 @@ enum { UO_AB, UO_A2, UO_B2, UO_L2, UO_SA, UO_SB, UO_KP, UO_KQ, UO_SUMS };
             total.sum[f] = NAME##_butterfly(v, lanes);                                                                  \
         }                                                                                                               \
         return total;                                                                                                   \
-    }                                                                                                                   \
-    /* pearson: metric_pearson_gt 1478-1520 */                                                                          \
+    }
+
+#define UO_FLOAT_PER_CHUNK (UO_CHUNK / (uo_bytes_per_vector(scalar_kind, 8) / 8))
+UO_DEFINE_SUMS(f32, float, fmaf, logf, 1.1920928955078125e-7f, load_float(scalar_kind, a, i), load_float(scalar_kind, b, i),
+               UO_FLOAT_PER_CHUNK)
+UO_DEFINE_SUMS(f64, double, fma, log, 2.220446049250313e-16, load_f64(a, i), load_f64(b, i), 2)
+
+/* pearson: metric_pearson_gt 1511-1550 */
+#define UO_DEFINE_PEARSON(NAME, T)                                                                                      \
     static T NAME##_pearson(const NAME##_acc_t* acc, uint64_t dims) {                                                   \
         const T* s = acc->sum;                                                                                          \
         if (dims <= 1)                                                                                                  \
@@ -283,11 +295,8 @@ enum { UO_AB, UO_A2, UO_B2, UO_L2, UO_SA, UO_SB, UO_KP, UO_KQ, UO_SUMS };
         T corr = n * s[UO_AB] - s[UO_SA] * s[UO_SB];                                                                    \
         return 1 - corr / (T)sqrt((double)denom); /* sqrt in double then narrowed = the correctly rounded sqrtf */       \
     }
-
-#define UO_FLOAT_PER_CHUNK (UO_CHUNK / (uo_bytes_per_vector(scalar_kind, 8) / 8))
-UO_DEFINE_SUMS(f32, float, fmaf, logf, 1.1920928955078125e-7f, load_float(scalar_kind, a, i), load_float(scalar_kind, b, i),
-               UO_FLOAT_PER_CHUNK)
-UO_DEFINE_SUMS(f64, double, fma, log, 2.220446049250313e-16, load_f64(a, i), load_f64(b, i), 2)
+UO_DEFINE_PEARSON(f32, float)
+UO_DEFINE_PEARSON(f64, double)
 
 /* metric_haversine_gt 1636-1657: latitude, longitude in degrees; angle_to_radians 203 */
 static float haversine_f32(const uint8_t* a, const uint8_t* b) {
@@ -352,7 +361,10 @@ float uo_distance(uint8_t metric_kind, uint8_t scalar_kind, const void* av, cons
     }
     if (scalar_kind == UO_SCALAR_I8 && metric_kind == UO_METRIC_DIVERGENCE)
         return NAN; /* no such instantiation (1991-2001) */
-    if (scalar_kind == UO_SCALAR_F64) {
+    /* divergence over f64 runs in f32 arithmetic (its `result_at` defaults to float, 1555; the dispatch names no other, 1997):
+     * it takes the f32 sums below, each element narrowed as it is loaded. (pearson over f64 is f32 in the reference in the same
+     * way, 1511 and 1973, and still double here and in the kernels: DESIGN.md §3.4.) */
+    if (scalar_kind == UO_SCALAR_F64 && metric_kind != UO_METRIC_DIVERGENCE) {
         f64_acc_t s = f64_sums(scalar_kind, a, b, dims, lanes, metric_kind == UO_METRIC_DIVERGENCE);
         switch (metric_kind) {
         case UO_METRIC_IP: return (float)(1 - s.sum[UO_AB]);
@@ -362,7 +374,6 @@ float uo_distance(uint8_t metric_kind, uint8_t scalar_kind, const void* av, cons
             return (float)(1 - s.sum[UO_AB] / (sqrt(s.sum[UO_A2]) * sqrt(s.sum[UO_B2])));
         case UO_METRIC_L2SQ: return (float)s.sum[UO_L2];
         case UO_METRIC_PEARSON: return (float)f64_pearson(&s, dims);
-        case UO_METRIC_DIVERGENCE: return (float)((s.sum[UO_KP] + s.sum[UO_KQ]) / 2);
         default: return NAN;
         }
     }
@@ -376,7 +387,7 @@ float uo_distance(uint8_t metric_kind, uint8_t scalar_kind, const void* av, cons
     }
     case UO_METRIC_L2SQ: return s.sum[UO_L2]; /* metric_l2sq_gt 1365-1385 */
     case UO_METRIC_PEARSON: return f32_pearson(&s, dims);
-    case UO_METRIC_DIVERGENCE: return (s.sum[UO_KP] + s.sum[UO_KQ]) / 2; /* metric_divergence_gt 1526-1551 */
+    case UO_METRIC_DIVERGENCE: return (s.sum[UO_KP] + s.sum[UO_KQ]) / 2; /* metric_divergence_gt 1555-1578 */
     default: return NAN;
     }
 }

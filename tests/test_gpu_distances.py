@@ -7,6 +7,9 @@ from tests import util
 
 pytestmark = pytest.mark.gpu
 
+# One dimension count per (metric, scalar) pair on `util.make_vectors` data: ordinary values. The edges of the value domain (i8 at
+# -128 / 127, ±inf, NaN, subnormals, zero and constant rows, empty bit sets, …) and the row lengths that put the tail of the row loop
+# at each of its edges are tests/test_gpu_distance_edges.py, over the table of tests/distance_edges.py.
 CASES = [
     ("cos", "f32", 128), ("ip", "f32", 97), ("l2sq", "f32", 3), ("cos", "f32", 768), ("l2sq", "f32", 20),
     ("cos", "f16", 768), ("ip", "f16", 64), ("l2sq", "f16", 100), ("cos", "f16", 7),

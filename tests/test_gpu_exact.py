@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from tests import util
+from tests import distance_edges, util
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -68,9 +68,12 @@ def test_exact_search_of_a_raw_dataset():
 
 
 @pytest.mark.parametrize("tile", [64, 256])
-@pytest.mark.parametrize("metric,dtype,ndim,n,k", [("l2sq", "i8", 96, 20011, 10), ("cos", "i8", 40, 9000, 64),
-                                                   ("ip", "i8", 130, 5003, 7), ("cos", "i8", 200, 9000, 16)])
-def test_tiled_exact_search_is_bit_identical_for_i8(reference, monkeypatch, metric, dtype, ndim, n, k, tile):
+@pytest.mark.parametrize("metric,dtype,ndim,n,k,full_range",
+                         [("l2sq", "i8", 96, 20011, 10, False), ("cos", "i8", 40, 9000, 64, False), ("ip", "i8", 130, 5003, 7, False),
+                          ("cos", "i8", 200, 9000, 16, False), ("cos", "i8", 130, 5003, 16, True)],
+                         ids=["l2sq-i8-96-20011-10", "cos-i8-40-9000-64", "ip-i8-130-5003-7", "cos-i8-200-9000-16",
+                              "cos-i8-130-5003-16-full-range"])
+def test_tiled_exact_search_is_bit_identical_for_i8(reference, monkeypatch, metric, dtype, ndim, n, k, full_range, tile):
     """The matrix-unit kernels (exact_tiled.hip: 64 queries per workgroup, and the wide tile of 256 for batches that fill the
     chip with it — forced here either way) sum integers exactly and close with the same arithmetic as the wave-per-query
     kernel, so keys, distance bits and counts are identical — ties resolved as lower_bound insertion in slot order does —
@@ -78,8 +81,12 @@ def test_tiled_exact_search_is_bit_identical_for_i8(reference, monkeypatch, metr
     from usearch_amd import Index
     monkeypatch.setenv("USEARCH_AMD_EXACT_TILE", str(tile))
     removed = np.arange(5, n, 13) + 1000
-    image, vectors, _ = util.build_image(n, ndim, metric, dtype, seed=93, remove=removed[:200], expansion_add=16, connectivity=4)
-    queries = util.make_vectors(131 if tile == 64 else 700, ndim, dtype, seed=94)
+    # `full_range`: rows and queries over the whole of int8, -128 included (tests/distance_edges.py), where make_vectors stops at ±100
+    vectors = distance_edges.full_range_i8(n, ndim, 93) if full_range else None
+    image, vectors, _ = util.build_image(n, ndim, metric, dtype, seed=93, remove=removed[:200], expansion_add=16, connectivity=4,
+                                         vectors=vectors)
+    count = 131 if tile == 64 else 700
+    queries = distance_edges.full_range_i8(count, ndim, 94) if full_range else util.make_vectors(count, ndim, dtype, seed=94)
     queries[:20] = vectors[:20]
     index = Index.restore(image)
     exact = index.search(queries, k, exact=True)

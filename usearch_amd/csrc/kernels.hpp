@@ -638,6 +638,18 @@ template <int scalar_ak> constexpr bool f32_math() {
 }
 template <int scalar_ak> constexpr bool narrow_float() { return scalar_ak == scalar_f16_k || scalar_ak == scalar_bf16_k; }
 
+/// divergence over f64: the reference's `metric_divergence_gt` defaults `result_at = float` (index_plugins.hpp:1555) and the
+/// dispatch passes no other (1997), so every element is narrowed with `static_cast<float>` and every sum is f32. The row and the
+/// staged query stay doubles; the narrowing happens where an element is read. (`metric_pearson_gt<f64_t>` is f32 in the reference
+/// in the same way, 1511 and 1973; pearson over f64 still runs in double here — DESIGN.md §3.4.)
+template <int metric_ak, int scalar_ak> constexpr bool f64_in_f32_math() {
+    return scalar_ak == scalar_f64_k && metric_ak == metric_divergence_k;
+}
+/// Whether the pair's sums are the float members of `partial_t` / `query_norm_t`.
+template <int metric_ak, int scalar_ak> constexpr bool float_sums() {
+    return f32_math<scalar_ak>() || f64_in_f32_math<metric_ak, scalar_ak>();
+}
+
 /// 16 stored bits → f32: IEEE binary16 (f16_to_f32, index_plugins.hpp:398-410) or bfloat16 = the upper half of an f32
 /// (bf16_to_f32, 434-446).
 template <int scalar_ak> UA_DEVICE float narrow_bits_to_float(std::uint32_t bits16) {
@@ -651,7 +663,7 @@ template <int scalar_ak> UA_DEVICE float narrow_bits_to_float(std::uint32_t bits
 /// their initial constant and cost nothing.
 ///   f32 math  ip: fx = Σab · cos: fx = Σab, fy = Σb² · l2sq: fx = Σ(a-b)² · pearson: fx = Σab, fy = Σb², fz = Σb ·
 ///             divergence: fx, fy = the two Kullback-Leibler sums · haversine: fx = the haversine term of the pair
-///   f64       the same in dx, dy, dz
+///   f64       the same in dx, dy, dz — except divergence, which the reference runs in f32 (`f64_in_f32_math`)
 ///   i8        ix = Σab, iy = Σb², iz = Σb (pearson)
 ///   b1        hamming: ix = Σpopcount(a^b) · tanimoto: ix = Σpopcount(a&b), iy = Σpopcount(a|b) ·
 ///             sorensen: ix = Σpopcount(a&b), iy = Σ(popcount(a) + popcount(b))
@@ -664,7 +676,7 @@ struct partial_t {
 UA_DEVICE float fma_real(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 UA_DEVICE double fma_real(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
-/// One element pair of an equidimensional metric, `real_ak` = float or double (index_plugins.hpp:1309-1385, 1478-1551).
+/// One element pair of an equidimensional metric, `real_ak` = float or double (index_plugins.hpp:1309-1385, 1511-1578).
 template <int metric_ak, typename real_ak>
 UA_DEVICE void accumulate_real(real_ak& x, real_ak& y, real_ak& z, real_ak a, real_ak b) {
     if constexpr (metric_ak == metric_cos_k) {
@@ -675,11 +687,11 @@ UA_DEVICE void accumulate_real(real_ak& x, real_ak& y, real_ak& z, real_ak a, re
     } else if constexpr (metric_ak == metric_l2sq_k) {
         const real_ak t = a - b;
         x = fma_real(t, t, x);
-    } else if constexpr (metric_ak == metric_pearson_k) { // metric_pearson_gt 1478-1520; Σa, Σa² are query constants
+    } else if constexpr (metric_ak == metric_pearson_k) { // metric_pearson_gt 1511-1550; Σa, Σa² are query constants
         x = fma_real(a, b, x);
         y = fma_real(b, b, y);
         z = z + b;
-    } else if constexpr (metric_ak == metric_divergence_k) { // metric_divergence_gt 1526-1551, p = query, q = stored
+    } else if constexpr (metric_ak == metric_divergence_k) { // metric_divergence_gt 1555-1578, p = query, q = stored
         real_ak epsilon, log_p, log_q;
         if constexpr (sizeof(real_ak) == 4)
             epsilon = 1.1920928955078125e-7f;
@@ -750,6 +762,10 @@ UA_DEVICE void accumulate_chunk(partial_t& p, const std::uint8_t* query_lds, std
         accumulate_float<metric_ak>(p, a1.y, narrow_bits_to_float<scalar_ak>(v.z >> 16));
         accumulate_float<metric_ak>(p, a1.z, narrow_bits_to_float<scalar_ak>(v.w & 0xFFFFu));
         accumulate_float<metric_ak>(p, a1.w, narrow_bits_to_float<scalar_ak>(v.w >> 16));
+    } else if constexpr (f64_in_f32_math<metric_ak, scalar_ak>()) {
+        const double2 a = *reinterpret_cast<const double2*>(q);
+        accumulate_float<metric_ak>(p, (float)a.x, (float)__builtin_bit_cast(double, ((std::uint64_t)v.y << 32) | v.x));
+        accumulate_float<metric_ak>(p, (float)a.y, (float)__builtin_bit_cast(double, ((std::uint64_t)v.w << 32) | v.z));
     } else if constexpr (scalar_ak == scalar_f64_k) {
         const double2 a = *reinterpret_cast<const double2*>(q);
         accumulate_real<metric_ak, double>(p.dx, p.dy, p.dz, a.x,
@@ -795,7 +811,7 @@ template <int metric_ak, int scalar_ak, int lanes_ak> UA_DEVICE void reduce_part
     constexpr bool third = metric_ak == metric_pearson_k;
 #pragma unroll
     for (int offset = lanes_ak / 2; offset >= 1; offset >>= 1) {
-        if constexpr (f32_math<scalar_ak>()) {
+        if constexpr (float_sums<metric_ak, scalar_ak>()) {
             p.fx += xor_lane(p.fx, offset);
             if constexpr (second)
                 p.fy += xor_lane(p.fy, offset);
@@ -824,7 +840,7 @@ struct query_norm_t {
     int i = 0, j = 0;
 };
 
-/// metric_pearson_gt's closing arithmetic (index_plugins.hpp:1508-1519) from the five sums.
+/// metric_pearson_gt's closing arithmetic (index_plugins.hpp:1541-1548) from the five sums.
 template <typename real_ak>
 UA_DEVICE real_ak pearson_distance(std::uint32_t dimensions, real_ak ab, real_ak a2, real_ak b2, real_ak sa, real_ak sb) {
     if (dimensions <= 1)
@@ -842,7 +858,7 @@ UA_DEVICE real_ak pearson_distance(std::uint32_t dimensions, real_ak ab, real_ak
 
 template <int metric_ak, int scalar_ak>
 UA_DEVICE float finalize_distance(partial_t p, query_norm_t a2, std::uint32_t dimensions) {
-    if constexpr (f32_math<scalar_ak>()) {
+    if constexpr (float_sums<metric_ak, scalar_ak>()) { // divergence over f64 included: f32 like the reference's
         if constexpr (metric_ak == metric_cos_k) { // metric_cos_gt, index_plugins.hpp:1334-1359
             if (a2.f == 0.f && p.fy == 0.f)
                 return 0.f;
@@ -871,8 +887,6 @@ UA_DEVICE float finalize_distance(partial_t p, query_norm_t a2, std::uint32_t di
             return (float)(1.0 - p.dx);
         } else if constexpr (metric_ak == metric_pearson_k) {
             return (float)pearson_distance<double>(dimensions, p.dx, a2.d, p.dy, a2.e, p.dz);
-        } else if constexpr (metric_ak == metric_divergence_k) {
-            return (float)((p.dx + p.dy) / 2);
         } else if constexpr (metric_ak == metric_haversine_k) {
             return (float)(2 * asin(__builtin_sqrt(p.dx)));
         } else {
@@ -885,7 +899,8 @@ UA_DEVICE float finalize_distance(partial_t p, query_norm_t a2, std::uint32_t di
         } else if constexpr (metric_ak == metric_ip_k) { // metric_ip_gt<i8_t, f32_t>: exact while |Σ| < 2^24
             return 1.f - (float)p.ix;
         } else if constexpr (metric_ak == metric_pearson_k) { // metric_pearson_gt<i8_t, f32_t>: its f32 sums of small
-            // integers are exact while they stay below 2^24 (dimensions ≤ 1040), which is where these equal them
+            // integers are exact while they stay below 2^24 (dimensions ≤ 1024 with a -128 among the values, ≤ 1040 without),
+            // which is where these equal them
             return pearson_distance<float>(dimensions, (float)p.ix, (float)a2.i, (float)p.iy, (float)a2.j, (float)p.iz);
         } else { // metric_l2sq_i8_t 1613-1630: Σ(a-b)² = Σa² + Σb² - 2Σab, exact in int32
             return (float)(a2.i + p.iy - 2 * p.ix);
