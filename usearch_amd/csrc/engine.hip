@@ -17,13 +17,9 @@
 #include "casts.hpp"
 #include "host_util.hpp"
 #include "kernels.hpp"
+#include "search_plan.hpp"
 
 namespace usearch_amd {
-
-/// How the short-row walks probe their visited-set slabs unless USEARCH_AMD_PROBE_MODE says otherwise (common.hpp `probe_mode_t`).
-static constexpr std::uint32_t default_probe_mode_k = probe_swap_k;
-/// Rows of ≤ 128 bytes gathered next to the probe of the visited set (USEARCH_AMD_EARLY_ROWS = 0 | 1 overrides).
-static constexpr std::size_t default_early_rows_k = 1; // 20M x 96 i8: +6.4 % at ef 80, +5.1 % at ef 64, same keys / bits / counters (profiles/r06_short_rows/early_rows.log)
 
 /// The block of per-wave visited-set slabs. (Round 5's experiment — the block in uncached or fine-grained device memory, to see whether
 /// the two-microsecond trip of a probe belongs to the memory type: it does not, profiles/r05_short_rows/ — compiles in only with
@@ -87,13 +83,6 @@ const char* upload_rows(std::uint8_t* device, std::uint32_t row_stride, const st
     }
     return nullptr;
 }
-
-/// Jaccard over bit sets IS Tanimoto in the reference's dispatch (index_plugins.hpp:2003-2004): one kernel serves both.
-/// gfx950 hands LDS out in blocks of 320 dwords (160 KB = 128 of them). Round 6 measured it the hard way: a wave of 8 160 bytes "fits" 20
-/// times by a 1 024-byte count and runs as 18 (i8 × 96 at expansion 80 with 1 024 `seen` cells: 10.99 ms against 9.97 with 512).
-constexpr std::uint64_t lds_granule_k = 1280;
-
-static metric_kind_t kernel_metric(metric_kind_t metric) { return metric == metric_jaccard_k ? metric_tanimoto_k : metric; }
 
 bool kernel_available(metric_kind_t metric, scalar_kind_t scalar) {
     metric = kernel_metric(metric);
@@ -699,9 +688,6 @@ __global__ void fill_empty_kernel(std::uint64_t* keys, std::uint32_t* distance_b
         counts[i] = 0, visited[i] = 0, computed[i] = 0;
 }
 
-/// The float-valued pairs may keep their frontier as the open cells of a register `top` (kernels.hpp frontier_top_k).
-static bool frontier_in_top_capable(scalar_kind_t scalar) { return scalar != scalar_b1x8_k && scalar != scalar_i8_k; }
-
 const char* snapshot_t::search_begin(search_call_t& call, const void* queries, std::size_t count,
                                      std::size_t stride_bytes, std::size_t wanted, std::size_t expansion,
                                      std::uint64_t* keys, float* distances, std::uint64_t* counts, std::uint64_t* visited,
@@ -734,163 +720,22 @@ const char* snapshot_t::search_begin(search_call_t& call, const void* queries, s
         return nullptr;
     }
 
-    if (!expansion)
-        expansion = default_expansion_search_k;
-    const std::uint32_t ef = (std::uint32_t)std::max(expansion, wanted); // index.hpp:3052
-    call.ef = ef;
-
-    // ---- scratch sizing, from measurements with the reference's own traversal (DESIGN.md "scratch sizing"): the frontier
-    // peaks at 2.4-3.9 × ef; the visited set ends at 18-30 × ef entries plus what the first hops of a big index cost
-    // whatever the expansion (10M × 768, ef = 64: 3 137 entries = 49 × ef) — hence the constant term. Outliers go through
-    // the retry ladder.
-    const std::uint32_t query_lds = view_.chunks * (query_chunk_bytes_of(scalar_));
-    call.query_lds = query_lds;
-    const std::uint32_t lds_budget = (std::uint32_t)env_size("USEARCH_AMD_LDS_BUDGET", 160 * 1024);
-    std::uint32_t hash_cap = tuning.hash_cap ? tuning.hash_cap : (std::uint32_t)env_size("USEARCH_AMD_HASH_CAP", 0);
-    if (!hash_cap) {
-        // entries expected ÷ the load the set is sized for: 75 % (the kernel's limit) for short rows, whose slabs must stay
-        // cache-resident (profiles/r02_visited_set.log); 50 % for rows of ≥ 128 bytes — every probe round is a two-microsecond trip
-        // to the memory side for the whole wave, and the headline batch runs 1.9 % faster with 65 536 cells than with 32 768
-        // (46.2 against 47.1 ms on fresh blocks, profiles/r04_placement/scratch_footprint.log); USEARCH_AMD_HASH_LOAD_PCT overrides
-        const std::uint32_t load_pct = (std::uint32_t)std::min<std::size_t>(75, std::max<std::size_t>(10, env_size("USEARCH_AMD_HASH_LOAD_PCT", lanes_ >= 8 ? 50 : 75)));
-        hash_cap = std::max<std::uint32_t>(1024, (std::uint32_t)((std::uint64_t)(ef * 30 + 1600) * 100 / load_pct));
+    // ---- what to launch: the planner's business (search_plan.hpp), from plain values; the environment is read once per call
+    search_shape_t& shape = call.shape;
+    shape = search_shape_t{};
+    shape.size = view_.size, shape.count = count, shape.wanted = wanted, shape.expansion = expansion;
+    shape.metric = (std::int32_t)kernel_metric(metric_), shape.scalar = (std::int32_t)scalar_;
+    shape.lanes = lanes_, shape.chunks = view_.chunks, shape.m0 = view_.m0, shape.compute_units = (std::uint32_t)compute_units_;
+    shape.has_tombstones = view_.has_tombstones != 0, shape.nbr0 = view_.nbr0 != nullptr, shape.nbr0_rows = view_.nbr0_rows != nullptr, shape.sketch = view_.sketch != nullptr;
+    if (extras) {
+        shape.query_ids = extras->query_ids != nullptr, shape.beam_level = extras->beam_level != 0, shape.descent_only = extras->descent_only;
+        shape.allow_bits = extras->allow_bits != nullptr, shape.exclude_own = extras->exclude_own;
+        shape.reference_frontier = extras->reference_frontier;
     }
-    hash_cap = pow2_ceil(hash_cap);
-    std::uint32_t next_cap = tuning.next_cap ? tuning.next_cap : (std::uint32_t)env_size("USEARCH_AMD_NEXT_CAP", 0);
-    if (!next_cap) // (peaks measured on 20M-vector slices, 100 000 queries: b1 × 128 at 64: median 158, maximum 317; i8 × 96 at 80: 220 / 360)
-        next_cap = std::max<std::uint32_t>(448, ef * 3 + 256);
-    // never larger than the index could possibly need
-    hash_cap = std::min<std::uint32_t>(hash_cap, pow2_ceil((std::uint32_t)std::min<std::uint64_t>(view_.size * 2 + 128, 1u << 30)));
-    next_cap = (std::uint32_t)std::min<std::uint64_t>(next_cap, view_.size + 64);
-
-    std::uint32_t mode_request = tuning.mode ? tuning.mode : (std::uint32_t)env_size("USEARCH_AMD_MODE", 0);
-    if (mode_request > 3)
-        return "Unknown scratch mode";
-    // `top` lives in registers (1 / 4 / 8 / 16 entries per lane) while the expansion allows it
-    const bool top_in_memory = tuning.top_in_memory || env_size("USEARCH_AMD_TOP_IN_MEMORY", 0) != 0;
-    const bool two_cells = lanes_ <= 2 && ef <= 128 && !env_size("USEARCH_AMD_NO_TWO_CELLS", 0); // short rows: see kernel_waves()
-    const std::uint32_t entries_per_lane = top_in_memory ? 0u : ef <= 64 ? 1u : two_cells ? 2u : ef <= 256 ? 4u : ef <= 512 ? 8u : ef <= 1024 ? 16u : 0u;
-    call.entries_per_lane = entries_per_lane;
-
-    // ---- who holds the frontier (kernels.hpp frontier_mode_t): the open cells of `top` wherever that is exact up to ties —
-    // float-valued pair, `top` in registers, every member a result candidate, slots below 2^31 — else the reference's heap
-    const std::uint32_t frontier_request = tuning.frontier ? tuning.frontier : (std::uint32_t)env_size("USEARCH_AMD_FRONTIER", 0);
-    const bool filtered = view_.has_tombstones || (extras && (extras->allow_bits || extras->exclude_own));
-    const bool in_top_possible = frontier_in_top_capable(scalar_) && entries_per_lane && !filtered && mode_request != 3 &&
-                                 view_.size < 0x80000000ull && !(extras && (extras->reference_frontier || extras->descent_only));
-    if (frontier_request == 2 && !in_top_possible)
-        return "The frontier cannot ride in `top` for this search (integer-valued pair, filter, tombstones or expansion > 1024)";
-    const int frontier = (frontier_request == 1 || !in_top_possible) ? frontier_heap_k : frontier_top_k;
-    if (frontier == frontier_top_k)
-        next_cap = 0;
-
-    // register/latency trade-off of the kernel (kernels.hpp kernel_variant_t); rows shorter than 8 chunks per lane have
-    // nothing to unroll
-    const std::uint32_t chunks_per_lane = view_.chunks / lanes_;
-    std::uint32_t variant_request = tuning.variant ? tuning.variant : (std::uint32_t)env_size("USEARCH_AMD_VARIANT", 0);
-    int variant = variant_u4_w4_k;
-    const bool every_build = lanes_ == 8 && all_kernel_builds(kernel_metric(metric_), scalar_);
-    if (every_build && chunks_per_lane >= 8) {
-        // measured on 10M x 768 f16 (profiles/): a whole row per round trip (12 loads per lane, 8 waves per CU) beats 8 loads
-        // at 12 waves per CU at every expansion — the traversal is latency-bound, fewer round trips per hop win
-        variant = chunks_per_lane >= 12 ? variant_u12_w2_k : variant_u8_w3_k;
-        // Without the heap (profiles/r02_sweep_variants.log, ef = 608): every build lands within 3 % of the others — the
-        // kernel moves 4.6-4.9 TB/s of rows plus the visited-set traffic, which is what random 1.5-KB gathers reach on this
-        // memory system at all — and what separates them is the DRAIN of the batch: with one wave per query the last queries
-        // run alone, for about 0.65 × waves / queries of the launch. Few waves with many bytes in flight each (two rows per
-        // lane group per round, 8 waves per CU) win while that matters; 16 waves per CU win once the batch is long enough.
-        if (frontier == frontier_top_k && chunks_per_lane >= 12)
-            variant = count >= 40000 ? variant_u4_w4_k : variant_u12x2_w2_k;
-    }
-    if (variant_request && variant_request - 1 < (std::uint32_t)variant_count_k && every_build) {
-        const int requested = (int)variant_request - 1;
-        if (requested == variant_u12x2_w2_k && frontier != frontier_top_k)
-            return "That kernel build exists for the in-`top` frontier only";
-        variant = requested;
-    }
-    // A batch that cannot give every CU two queries to walk (a `usearch_search` caller's single query above all) over long rows: four
-    // helper waves per query take the rows of every hop, the leader walks and commits (kernels.hpp team_search_kernel)
-    const bool team = every_build && chunks_per_lane >= 8 && !variant_request && mode_request != 3 &&
-                      count <= 2ull * compute_units_ && !(extras && extras->descent_only) && !env_size("USEARCH_AMD_NO_TEAM", 0) &&
-                      !tuning.waves_per_cu;
-    if (team)
-        variant = variant_u12_w2_k;
-    // whether this call can run the short-row build cut for plain batches (kernels.hpp `plain_ak`) as far as that is known here; the
-    // scratch mode, the `seen` cells and the early rows are settled per rung in run_ladder, which has the last word (`params.plain`)
-    call.plain_possible = !team && !view_.has_tombstones && view_.m0 <= 64 && view_.nbr0 &&
-                          !(extras && (extras->query_ids || extras->beam_level || extras->descent_only || extras->allow_bits || extras->exclude_own)) &&
-                          (lanes_ == 1 ? view_.nbr0_rows != nullptr && view_.chunks == 1 : lanes_ == 2) &&
-                          plain_build_exists(kernel_metric(metric_), scalar_, (int)lanes_, variant == variant_u4_w4_k, true, (int)entries_per_lane,
-                                             frontier == frontier_heap_k) &&
-                          !env_size("USEARCH_AMD_NO_PLAIN", 0);
-    const std::uint32_t variant_waves_per_cu =
-        4u * (std::uint32_t)kernel_waves(variant, (int)entries_per_lane, frontier, (int)lanes_, call.plain_possible);
-    const std::uint32_t waves_cap = tuning.waves_per_cu ? tuning.waves_per_cu
-                                                        : (std::uint32_t)env_size("USEARCH_AMD_WAVES_PER_CU", 32);
-    call.waves_cap = std::min(waves_cap, variant_waves_per_cu);
-
-    // the sketch (sketch.hpp): plain and filtered searches of the finished graph walked by one wave per query in a build with twelve
-    // loads in flight (the others have no registers to spare: kernels.hpp); `tuning.sketch` = 1 turns it off for this call, 2 keeps
-    // auto mode from judging it by this call. Its 256 bytes of LDS per wave (plus alignment) count in every residency decision below.
-    if (tuning.sketch > 2)
-        return "Unknown sketch mode";
-    const bool sketch_use = view_.sketch && tuning.sketch != 1 && !team && mode_request != 3 &&
-                            (variant == variant_u12_w2_k || variant == variant_u12x2_w2_k) &&
-                            !(extras && (extras->query_ids || extras->beam_level || extras->descent_only || extras->reference_frontier));
-    const std::uint32_t sketch_lds = sketch_use ? sketch_columns_k * 4 + 16 : 0;
-    auto lds_bytes_for = [&](int mode, std::uint32_t cap_next, std::uint32_t cap_hash) -> std::uint64_t {
-        if (mode == scratch_global_k)
-            return query_lds;
-        const scratch_layout_t l = scratch_layout(entries_per_lane ? 0 : ef, cap_next,
-                                                  mode == scratch_lds_k ? (std::uint64_t)cap_hash * 4 : 0);
-        return query_lds + l.total + sketch_lds;
-    };
-    auto waves_for = [&](std::uint64_t lds_bytes) -> std::uint32_t {
-        const std::uint64_t granule = (lds_bytes + lds_granule_k - 1) / lds_granule_k * lds_granule_k; // LDS is allocated in coarse granules
-        return (std::uint32_t)std::max<std::uint64_t>(
-            1, std::min<std::uint64_t>(call.waves_cap, lds_budget / std::max<std::uint64_t>(granule, 1)));
-    };
-    // the frontier's default room has 256 cells of slack; when giving up to half of it back lets one more wave share the
-    // compute unit's LDS, do (the retry ladder still catches a query that would have needed them)
-    const bool default_next_cap = !tuning.next_cap && !env_size("USEARCH_AMD_NEXT_CAP", 0);
-    if (default_next_cap && next_cap && mode_request != 1 && mode_request != 3) {
-        const std::uint32_t now = waves_for(lds_bytes_for(scratch_hash_k, next_cap, hash_cap));
-        if (now < call.waves_cap) {
-            const std::uint64_t room = lds_budget / (now + 1) / lds_granule_k * lds_granule_k;
-            const std::uint64_t fixed = lds_bytes_for(scratch_hash_k, 0, hash_cap);
-            if (room > fixed) {
-                const std::uint32_t trimmed = (std::uint32_t)((room - fixed) / 8 / 2 * 2);
-                if (trimmed < next_cap && trimmed + 128 >= next_cap)
-                    next_cap = trimmed;
-            }
-        }
-    }
-    // auto: keep the visited set in LDS only while that does not cost a resident wave; otherwise move it to the global hash. A batch
-    // so small that every query gets a wave of its own even at the LDS residency (a `usearch_search` caller's single query above
-    // all) also takes LDS: residency buys it nothing, and every probe round of the global hash is a two-microsecond trip to the
-    // memory side — half of such a query's latency (profiles/r03_short_rows/README.md §1)
-    std::uint64_t lds_mode_bytes = lds_bytes_for(scratch_lds_k, next_cap, hash_cap);
-    // a set sized for half load that does not fit LDS where the one sized for 75 % would (expansion 608 over long rows: 256 KB
-    // against 128 KB): a small batch takes the smaller set in LDS rather than the larger one in global memory — a lone query walks
-    // 3.1 ms that way and 3.5 ms the other
-    if (!tuning.hash_cap && !env_size("USEARCH_AMD_HASH_CAP", 0) && mode_request == 0 && lds_mode_bytes > lds_budget) {
-        const std::uint32_t tighter = std::min<std::uint32_t>(
-            pow2_ceil(std::max<std::uint32_t>(1024, (ef * 30 + 1600) / 3 * 4)),
-            pow2_ceil((std::uint32_t)std::min<std::uint64_t>(view_.size * 2 + 128, 1u << 30)));
-        const std::uint64_t tighter_bytes = lds_bytes_for(scratch_lds_k, next_cap, tighter);
-        if (tighter < hash_cap && tighter_bytes <= lds_budget && count <= (std::uint64_t)waves_for(tighter_bytes) * compute_units_ &&
-            !env_size("USEARCH_AMD_NO_SMALL_BATCH_LDS", 0)) {
-            hash_cap = tighter;
-            lds_mode_bytes = tighter_bytes;
-        }
-    }
-    const bool small_batch = lds_mode_bytes <= lds_budget && count <= (std::uint64_t)waves_for(lds_mode_bytes) * compute_units_ &&
-                             !env_size("USEARCH_AMD_NO_SMALL_BATCH_LDS", 0);
-    int mode = mode_request == 1 ? scratch_lds_k : mode_request == 2 ? scratch_hash_k : mode_request == 3 ? scratch_global_k
-               : (small_batch || waves_for(lds_mode_bytes) >= std::min<std::uint32_t>(8, call.waves_cap) ? scratch_lds_k : scratch_hash_k);
-    call.mode = mode;
-    call.hash_cap = hash_cap;
-    call.next_cap = next_cap;
+    call.knobs = read_search_knobs(lanes_);
+    search_plan_t& plan = call.plan;
+    if (const char* e = plan_search(shape, tuning, call.knobs, plan))
+        return e;
 
     if (const char* e = ws.reserve(count, 0))
         return e;
@@ -900,7 +745,7 @@ const char* snapshot_t::search_begin(search_call_t& call, const void* queries, s
     args.queries = static_cast<const std::uint8_t*>(queries);
     args.query_stride = stride_bytes;
     args.wanted = (std::uint32_t)wanted;
-    args.ef = ef;
+    args.ef = plan.ef;
     args.keys = keys;
     args.distances = distances;
     args.counts = counts;
@@ -925,14 +770,8 @@ const char* snapshot_t::search_begin(search_call_t& call, const void* queries, s
     params = launch_params_t{};
     params.metric = metric_;
     params.lanes = lanes_;
-    params.variant = variant;
-    params.frontier = frontier;
-    params.team = team ? 1u : 0u;
+    params.variant = plan.variant;
     params.stream = stream;
-    call.stats = search_stats_t{};
-    call.stats.frontier = frontier == frontier_top_k ? 2u : 1u;
-    call.stats.variant = team ? 5u : (std::uint32_t)variant + 1; // 5 = the team build (five waves per query)
-    call.stats.top_cells = entries_per_lane;
 
     // diagnostic: per-phase shader-clock ticks of the search kernel, printed to stderr (USEARCH_AMD_PHASES=1)
     call.want_phases = env_size("USEARCH_AMD_PHASES", 0) != 0;
@@ -941,7 +780,7 @@ const char* snapshot_t::search_begin(search_call_t& call, const void* queries, s
         UA_HIP(hipMemsetAsync(args.phases, 0, 128, stream));
     }
     call.want_clock = tuning.wave_clock || env_size("USEARCH_AMD_WAVE_CLOCK", 0) != 0;
-    if (sketch_use) {
+    if (plan.sketch) {
         args.sketch_counters = reinterpret_cast<unsigned long long*>(ws.d_queue) + 1; // bytes 8 … 23 of the queue block
         call.sketch_auto = tuning.sketch == 0;
     }
@@ -955,176 +794,57 @@ const char* snapshot_t::search_begin(search_call_t& call, const void* queries, s
     return run_ladder(call);
 }
 
-/// One launch of the ladder's current rung over `pending` queries (all of them, or `call.todo`).
+/// Zeroes the first `counter_bytes` of the queue block — [0] the ticket counter, [1] how many queries outgrew their scratch, [2 … 5] the
+/// sketch's two counters — and launches over `view`; with `ms`, times the launch between the two events and waits for it.
+static const char* counted_launch(metric_kind_t metric, scalar_kind_t scalar, const launch_params_t& params, const snapshot_view_t& view,
+                                  const search_args_t& args, std::size_t counter_bytes, hipEvent_t begin, hipEvent_t end, float* ms) {
+    UA_HIP(hipMemsetAsync(args.queue, 0, counter_bytes, params.stream));
+    if (ms)
+        UA_HIP(hipEventRecord(begin, params.stream));
+    UA_HIP(launch_search(metric, scalar, params, view, args));
+    if (ms) {
+        UA_HIP(hipEventRecord(end, params.stream));
+        UA_HIP(hipEventSynchronize(end));
+        UA_HIP(hipEventElapsedTime(ms, begin, end));
+    }
+    return nullptr;
+}
+
+/// One launch of the ladder's current rung over `pending` queries (all of them, or `call.todo`), as `plan_rung` shapes it.
 const char* snapshot_t::run_ladder(search_call_t& call) {
     workspace_t& ws = *call.workspace;
     search_args_t& args = call.args;
     launch_params_t& params = call.params;
     hipStream_t stream = call.stream;
-    const std::uint32_t ef = call.ef;
-    const std::uint32_t lds_budget = (std::uint32_t)env_size("USEARCH_AMD_LDS_BUDGET", 160 * 1024);
-    auto lds_bytes_for = [&](int mode, std::uint32_t cap_next, std::uint32_t cap_hash) -> std::uint64_t {
-        if (mode == scratch_global_k)
-            return call.query_lds;
-        const scratch_layout_t l = scratch_layout(call.entries_per_lane ? 0 : ef, cap_next,
-                                                  mode == scratch_lds_k ? (std::uint64_t)cap_hash * 4 : 0);
-        return call.query_lds + l.total;
-    };
-    auto waves_for = [&](std::uint64_t lds_bytes) -> std::uint32_t {
-        const std::uint64_t granule = (lds_bytes + lds_granule_k - 1) / lds_granule_k * lds_granule_k;
-        return (std::uint32_t)std::max<std::uint64_t>(
-            1, std::min<std::uint64_t>(call.waves_cap, lds_budget / std::max<std::uint64_t>(granule, 1)));
+    search_plan_t& plan = call.plan;
+    // every launch below zeroes `counter_bytes` of the queue block first and, with `ms`, is timed between the workspace's two events: the
+    // launch proper 24 bytes (the overflow count is read once per rung, so the later chunks of the global rung zero 4 and keep what an
+    // earlier chunk counted); a placement trial 8
+    auto launch = [&](const snapshot_view_t& view, std::size_t counter_bytes, float* ms) {
+        return counted_launch(metric_, scalar_, params, view, args, counter_bytes, ws.event_begin, ws.event_end, ms);
     };
     auto timed_launch = [&](bool keep_overflows = false) -> const char* {
-        // [0] the ticket counter, [1] how many queries outgrew their scratch — the latter is read once per rung, so the chunks of
-        // the global rung must not erase what an earlier chunk counted
-        UA_HIP(hipMemsetAsync(ws.d_queue, 0, keep_overflows ? 4 : 24, stream)); // (… [2 … 5] the sketch's two counters)
-        if (call.timed)
-            UA_HIP(hipEventRecord(ws.event_begin, stream));
-        UA_HIP(launch_search(metric_, scalar_, params, view_, args));
-        if (call.timed) {
-            UA_HIP(hipEventRecord(ws.event_end, stream));
-            UA_HIP(hipEventSynchronize(ws.event_end));
-            float ms = 0.f;
-            UA_HIP(hipEventElapsedTime(&ms, ws.event_begin, ws.event_end));
-            call.total_ms += ms;
-        }
-        return nullptr;
+        float ms = 0.f;
+        const char* e = launch(view_, keep_overflows ? 4 : 24, call.timed ? &ms : nullptr);
+        call.total_ms += ms;
+        return e;
     };
 
     const std::uint32_t pending = call.have_todo ? (std::uint32_t)call.todo.size() : (std::uint32_t)call.count;
-    // a team's workgroup adds its shared control block (16-byte alignment + 64 bytes) to the leader's areas: a size that only just
-    // fits the budget alone must not become a launch failure — such a batch walks with one wave per query
-    const std::uint32_t team_bytes = team_block_bytes_k;
-    if (params.team && call.mode != scratch_global_k &&
-        (lds_bytes_for(call.mode, call.next_cap, call.hash_cap) + 15) / 16 * 16 + team_bytes > lds_budget) {
-        params.team = 0;
-        call.stats.variant = (std::uint32_t)params.variant + 1;
-    }
-    if (call.mode != scratch_global_k) {
-        if (lds_bytes_for(call.mode, call.next_cap, call.hash_cap) > lds_budget) {
-            if (call.mode == scratch_lds_k)
-                call.mode = scratch_hash_k;
-            while (call.next_cap > 64 && lds_bytes_for(call.mode, call.next_cap, call.hash_cap) > lds_budget)
-                call.next_cap /= 2;
-            if (lds_bytes_for(call.mode, call.next_cap, call.hash_cap) > lds_budget)
-                call.mode = scratch_global_k; // `top` alone does not fit LDS: straight to the global fallback
-        }
-    }
-    if (call.mode != scratch_global_k) {
-        // a team's workgroup carries the leader's LDS areas plus the shared block; one workgroup per query of the small batch
-        std::uint64_t wave_lds_bytes = lds_bytes_for(call.mode, call.next_cap, call.hash_cap);
-        // short rows over a global visited set: `seen` cells in LDS in front of it (kernels.hpp `search_one`) — as many as cost no
-        // resident wave (the walk lives on its residency), at most 2 048; USEARCH_AMD_SEEN_CELLS forces a number (0 = none)
-        args.seen_offset = 0, args.seen_cells = 0;
-        args.aside_offset = 0, args.aside_cells = 0;
-        args.probe_mode = probe_swap_k, args.claim_offset = 0, args.claim_bits = 0;
-        // rows of ≤ 128 bytes gathered next to the probe of the visited set instead of behind it (kernels.hpp, the hop loop)
-        args.early_rows = call.mode == scratch_hash_k && !params.team && lanes_ == 2 && env_size("USEARCH_AMD_EARLY_ROWS", default_early_rows_k) ? 1u : 0u;
-        call.stats.early_rows = args.early_rows;
-        if (call.mode == scratch_hash_k && !params.team && lanes_ <= 2) {
-            // how the slab is probed (common.hpp `probe_mode_t`): USEARCH_AMD_PROBE_MODE = 0 | 1 | 2
-            // (USEARCH_AMD_PROBE_LOAD_FIRST=1, round 5's name for mode 1, still answers)
-            std::size_t probe_mode = default_probe_mode_k;
-#ifdef USEARCH_AMD_EXPERIMENT_PROBE_MODES // `make EXTRA=-DUSEARCH_AMD_EXPERIMENT_PROBE_MODES OUT=… OBJ=…`: the copy scripts/probe_mode_check.py loads
-            probe_mode = env_size("USEARCH_AMD_PROBE_MODE", default_probe_mode_k);
-            if (env_size("USEARCH_AMD_PROBE_LOAD_FIRST", 0))
-                probe_mode = probe_load_first_k;
-#endif
-            if (probe_mode == probe_plain_k) {
-                // one claim bit per cell of the slab where that costs no resident wave, else as many as do not (a smaller bitmap only
-                // adds false alarms: a lane that loses a claim looks at its cell again); USEARCH_AMD_CLAIM_BITS forces a number
-                std::uint32_t bits = call.hash_cap;
-                const std::size_t forced = env_size("USEARCH_AMD_CLAIM_BITS", 0);
-                if (forced)
-                    for (bits = 64; bits * 2 <= forced && bits < call.hash_cap; bits *= 2) {}
-                else
-                    while (bits > 512 && waves_for((wave_lds_bytes + 15) / 16 * 16 + bits / 8) < waves_for(wave_lds_bytes))
-                        bits /= 2;
-                if ((wave_lds_bytes + 15) / 16 * 16 + bits / 8 <= lds_budget) {
-                    args.probe_mode = (std::uint32_t)probe_mode;
-                    args.claim_offset = (std::uint32_t)((wave_lds_bytes + 15) / 16 * 16);
-                    args.claim_bits = bits;
-                    wave_lds_bytes = args.claim_offset + bits / 8ull;
-                }
-            } else if (probe_mode == probe_load_first_k) {
-                args.probe_mode = probe_load_first_k;
-            }
-            // a plain `search` batch runs the build without the features it never uses (kernels.hpp `plain_ak`); the engine vouches here
-            // for everything that build takes for granted (USEARCH_AMD_NO_PLAIN=1 keeps the general build). That build never probes the
-            // slab past a member's home cell and sets what collides aside in LDS: about visits² / (2 · cells of the slab) members,
-            // visits ≈ 20 · expansion + 800 on the measured shapes (20M × 128 b1 at 64: median 1 521, maximum 2 225 of 100 000 queries;
-            // 20M × 96 i8 at 80: 1 742 / 2 281) — 512 cells at three quarters' load must take them, and must cost no resident wave;
-            // a query that outgrows them all the same is run again by the retry ladder
-            args.aside_offset = 0, args.aside_cells = 0;
-            const bool plain_wanted = call.plain_possible && !args.query_ids && !args.beam_level && !args.descent_only && !args.allow_bits &&
-                                      !args.exclude_own && args.probe_mode == probe_swap_k && (lanes_ == 1 || args.early_rows != 0);
-#ifdef USEARCH_AMD_EXPERIMENT_NO_ASIDE
-            const bool aside_wanted = false;
-#else
-            const bool aside_wanted = plain_wanted && lanes_ == 2; // (rows that travel with the lists gain nothing from it: kernels.hpp)
-#endif
-            if (aside_wanted) {
-                std::uint32_t aside_cells = 512;
-                if (const std::size_t forced_cells = env_size("USEARCH_AMD_ASIDE_CELLS", 0)) // tests: a table that is sure to fill up
-                    for (aside_cells = 64; aside_cells * 2 <= forced_cells && aside_cells < 2048; aside_cells *= 2) {}
-                const std::uint64_t expected_visits = std::min<std::uint64_t>((std::uint64_t)call.ef * 20 + 800, view_.size);
-                const bool room = expected_visits * expected_visits / (2ull * call.hash_cap) <= aside_cells * 3ull / 4 ||
-                                  env_size("USEARCH_AMD_PLAIN_WHATEVER_THE_ROOM", 0); // tests: a query that outgrows `aside` goes up the retry ladder
-                const std::uint64_t with_aside = (wave_lds_bytes + 15) / 16 * 16 + aside_cells * 4ull;
-                if (room && waves_for(with_aside) >= waves_for(wave_lds_bytes) && with_aside <= lds_budget) {
-                    args.aside_offset = (std::uint32_t)((wave_lds_bytes + 15) / 16 * 16);
-                    args.aside_cells = aside_cells;
-                    wave_lds_bytes = with_aside;
-                }
-            }
-            const std::size_t forced = env_size("USEARCH_AMD_SEEN_CELLS", (std::size_t)-1);
-            std::uint32_t cells = 0;
-            if (forced != (std::size_t)-1) {
-                for (cells = 1; cells * 2 <= forced && cells < 8192; cells *= 2) {}
-                cells = forced ? cells : 0;
-            } else {
-                for (std::uint32_t candidate = 2048; candidate >= 128 && !cells; candidate /= 2)
-                    if (waves_for((wave_lds_bytes + 15) / 16 * 16 + candidate * 4ull) >= waves_for(wave_lds_bytes))
-                        cells = candidate;
-            }
-            if (cells && (wave_lds_bytes + 15) / 16 * 16 + cells * 4ull <= lds_budget) {
-                args.seen_offset = (std::uint32_t)((wave_lds_bytes + 15) / 16 * 16);
-                args.seen_cells = cells;
-                wave_lds_bytes = args.seen_offset + cells * 4ull;
-            }
-            call.stats.probe_mode = args.probe_mode;
-            call.stats.seen_cells = args.seen_cells;
-            call.stats.claim_bits = args.claim_bits;
-        }
-        // decided with the LDS areas above (short rows over the global hash only): what the instantiation takes for granted must be there
-        params.plain = 0;
-        if (call.mode == scratch_hash_k && !params.team && lanes_ <= 2 && call.plain_possible && !args.query_ids && !args.beam_level &&
-            !args.descent_only && !args.allow_bits && !args.exclude_own && args.probe_mode == probe_swap_k && (lanes_ == 1 || args.early_rows != 0)) {
-#ifdef USEARCH_AMD_EXPERIMENT_NO_ASIDE
-            params.plain = args.seen_cells ? 1u : 0u;
-#else
-            params.plain = (lanes_ == 2 ? args.aside_cells : args.seen_cells) ? 1u : 0u;
-#endif
-        }
-        call.stats.plain = params.plain;
-        call.stats.aside_cells = args.aside_cells;
-        // the query's 64 coefficients on the sketch's directions: 256 bytes behind the wave's other areas
-        args.sketch_offset = 0;
-        if (args.sketch_counters) {
-            const std::uint64_t offset = (wave_lds_bytes + 15) / 16 * 16;
-            if (!params.team && offset + sketch_columns_k * 4 <= lds_budget) {
-                args.sketch_offset = (std::uint32_t)offset;
-                wave_lds_bytes = offset + sketch_columns_k * 4;
-            } else {
-                args.sketch_counters = nullptr;
-            }
-        }
-        const std::uint64_t lds_bytes = params.team ? (wave_lds_bytes + 15) / 16 * 16 + team_bytes : wave_lds_bytes;
-        args.team_offset = params.team ? (std::uint32_t)((wave_lds_bytes + 15) / 16 * 16) : 0u;
-        const std::uint32_t grid = params.team ? pending
-                                               : (std::uint32_t)std::min<std::uint64_t>(pending, (std::uint64_t)waves_for(lds_bytes) * compute_units_);
-        const std::uint64_t slab = call.mode == scratch_hash_k ? (std::uint64_t)call.hash_cap * 4 : 0;
+    search_rung_t rung;
+    plan_rung(call.shape, call.knobs, plan, pending, rung);
+    params.mode = rung.mode, params.team = rung.team, params.plain = rung.plain, params.entries_per_lane = rung.entries_per_lane;
+    params.frontier = rung.frontier, params.grid = rung.grid, params.lds_bytes = rung.lds_bytes;
+    args.hash_cap = rung.hash_cap, args.next_cap = rung.next_cap, args.wave_clock = nullptr;
+    if (!plan.sketch)
+        args.sketch_counters = nullptr;
+    if (rung.mode != scratch_global_k) {
+        args.seen_offset = rung.seen_offset, args.seen_cells = rung.seen_cells;
+        args.aside_offset = rung.aside_offset, args.aside_cells = rung.aside_cells;
+        args.probe_mode = rung.probe_mode, args.claim_offset = rung.claim_offset, args.claim_bits = rung.claim_bits;
+        args.early_rows = rung.early_rows, args.sketch_offset = rung.sketch_offset, args.team_offset = rung.team_offset;
+        const std::uint32_t grid = rung.grid;
+        const std::uint64_t slab = rung.slab;
         // WHERE the block of visited-set slabs lands decides which of the walk's speeds this batch runs at (with the index arrays
         // untouched, a fresh 268-MB block flips the headline batch between 45.5 and 51.6 ms; profiles/r03_placement/), and no
         // synthetic probe tells the placements apart — only the walk itself does. So when a new block is needed for a launch that
@@ -1136,25 +856,9 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
                                   !env_size("USEARCH_AMD_SCRATCH_REDRAW", 0);
         if (const char* e = ws.reserve(call.count, draw_scratch ? 0 : slab * grid))
             return e;
-        args.status = ws.d_status, args.peaks = ws.d_peaks;
-        args.hash_cap = call.hash_cap;
-        args.next_cap = call.next_cap;
-        args.todo = call.have_todo ? ws.d_todo : nullptr;
-        args.count = pending;
-        args.scratch = ws.d_scratch;
-        args.scratch_stride = slab;
-        args.wave_clock = nullptr;
+        args.status = ws.d_status, args.peaks = ws.d_peaks, args.todo = call.have_todo ? ws.d_todo : nullptr;
+        args.count = pending, args.scratch = ws.d_scratch, args.scratch_stride = slab;
         if (draw_scratch) {
-            params.mode = call.mode;
-            params.entries_per_lane = call.entries_per_lane;
-            params.grid = grid;
-            params.lds_bytes = (std::uint32_t)lds_bytes;
-            hipEvent_t begin = nullptr, end = nullptr;
-            UA_HIP(hipEventCreate(&begin));
-            if (hipError_t created = hipEventCreate(&end); created != hipSuccess) {
-                (void)hipEventDestroy(begin);
-                return hip_message(created);
-            }
             void* candidates[8] = {nullptr};
             float trial_ms[8] = {0};
             std::size_t drawn = 0;
@@ -1162,22 +866,8 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
             auto trial = [&](void* block, float& ms) -> const char* { // the launch's first `grid` queries over this block, second run timed
                 args.scratch = static_cast<std::uint8_t*>(block);
                 args.count = grid;
-                for (int repeat = 0; repeat < 2; ++repeat) {
-                    hipError_t e = hipMemsetAsync(ws.d_queue, 0, 8, stream);
-                    if (e == hipSuccess)
-                        e = hipEventRecord(begin, stream);
-                    if (e == hipSuccess)
-                        e = launch_search(metric_, scalar_, params, view_, args);
-                    if (e == hipSuccess)
-                        e = hipEventRecord(end, stream);
-                    if (e == hipSuccess)
-                        e = hipEventSynchronize(end);
-                    if (e == hipSuccess)
-                        e = hipEventElapsedTime(&ms, begin, end);
-                    if (e != hipSuccess)
-                        return hip_message(e);
-                }
-                return nullptr;
+                const char* e = launch(view_, 8, &ms);
+                return e ? e : launch(view_, 8, &ms);
             };
             // diagnostic (USEARCH_AMD_SCRATCH_REMAP = n): ONE physical block mapped at n fresh virtual ranges, each view timed the
             // same way — does the speed follow the physical pages or the mapping (its page tables)?
@@ -1200,8 +890,6 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
                 // its first touch
                 failure = trial(candidates[drawn], trial_ms[drawn]);
             }
-            (void)hipEventDestroy(begin);
-            (void)hipEventDestroy(end);
             std::size_t kept = 0;
             for (std::size_t i = 1; i < drawn; ++i)
                 if (trial_ms[i] < trial_ms[kept])
@@ -1225,20 +913,20 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
                 std::fprintf(stderr, " ms\n");
             }
         }
-        // ---- the matrix of stored rows: up to `placement_max_draws_k` trials over the first launches that fill the chip, judged like
-        //      the scratch block — by this launch's own first queries at the caller's expansion (placement.hpp)
-        //      OFF unless USEARCH_AMD_PLACEMENT_DRAWS = 2 … 8 asks for them (round 6): the matrix is placed once, at load time, after
-        //      the settle window (placement.hpp) — deterministic, no second copy of the matrix in HBM during a search call, nothing
-        //      swapped under a reader. The trials stay for hosts whose matrix was allocated while other gigabytes were held.
+    // ---- the matrix of stored rows: up to `placement_max_draws_k` trials over the first launches that fill the chip, judged like
+    //      the scratch block — by this launch's own first queries at the caller's expansion (placement.hpp)
+    //      OFF unless USEARCH_AMD_PLACEMENT_DRAWS = 2 … 8 asks for them (round 6): the matrix is placed once, at load time, after
+    //      the settle window (placement.hpp) — deterministic, no second copy of the matrix in HBM during a search call, nothing
+    //      swapped under a reader. The trials stay for hosts whose matrix was allocated while other gigabytes were held.
         const std::uint32_t matrix_draws = tuning_trials_ ? tuning_trials_ + 1u + placement_.draws
                                                           : (std::uint32_t)std::min<std::size_t>(placement_max_draws_k, env_size("USEARCH_AMD_PLACEMENT_DRAWS", 1));
-        // A host that tunes its expansion walks up through the regimes (bench.py's recall sweep: 64, 96, 128 … 608): trials judged at a
-        // small expansion — differences of hundredths of a millisecond — must not be the last word for launches several times as
-        // wide. A launch more than twice as wide as the last trial's reopens a search that has ended, for three trials, twice at most.
+    // A host that tunes its expansion walks up through the regimes (bench.py's recall sweep: 64, 96, 128 … 608): trials judged at a
+    // small expansion — differences of hundredths of a millisecond — must not be the last word for launches several times as
+    // wide. A launch more than twice as wide as the last trial's reopens a search that has ended, for three trials, twice at most.
         bool try_placement = false;
         if (matrix_draws > 1) { // the trials' bookkeeping is shared by every batch in flight: under the pool's mutex
             std::lock_guard<std::mutex> lock(pool_mutex_);
-            if (!placement_trials_left_ && placement_reopens_ < 2 && placement_last_ef_ && call.ef > 2u * placement_last_ef_ &&
+            if (!placement_trials_left_ && placement_reopens_ < 2 && placement_last_ef_ && plan.ef > 2u * placement_last_ef_ &&
                 call.passes == 0 && !call.have_todo && pending >= 2ull * grid)
                 placement_trials_left_ = 3, placement_losses_ = 0, ++placement_reopens_;
             try_placement = placement_trials_left_ != 0;
@@ -1247,37 +935,9 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
             !params.team && pending >= 2ull * grid && grid >= 2u * (std::uint32_t)compute_units_ && !view_.nbr0_rows && d_vectors_ &&
             vectors_bytes_ >= env_size("USEARCH_AMD_PLACEMENT_MIN_BYTES", (std::size_t)1 << 30) && !args.query_ids && !args.allow_bits &&
             !args.descent_only && !args.beam_level && !env_size("USEARCH_AMD_SCRATCH_REDRAW", 0)) {
-            params.mode = call.mode;
-            params.entries_per_lane = call.entries_per_lane;
-            params.grid = grid;
-            params.lds_bytes = (std::uint32_t)lds_bytes;
-            hipEvent_t begin = nullptr, end = nullptr;
-            UA_HIP(hipEventCreate(&begin));
-            if (hipError_t created = hipEventCreate(&end); created != hipSuccess) {
-                (void)hipEventDestroy(begin);
-                return hip_message(created);
-            }
             args.count = grid; // one query per wave: the launch's steady state; their results are computed again by the launch proper
-            const char* failure = try_matrix_placement(
-                call.ef,
-                [&](const snapshot_view_t& view, float& ms) -> const char* {
-                    hipError_t e = hipMemsetAsync(ws.d_queue, 0, 8, stream);
-                    if (e == hipSuccess)
-                        e = hipEventRecord(begin, stream);
-                    if (e == hipSuccess)
-                        e = launch_search(metric_, scalar_, params, view, args);
-                    if (e == hipSuccess)
-                        e = hipEventRecord(end, stream);
-                    if (e == hipSuccess)
-                        e = hipEventSynchronize(end);
-                    if (e == hipSuccess)
-                        e = hipEventElapsedTime(&ms, begin, end);
-                    return e == hipSuccess ? nullptr : hip_message(e);
-                },
-                stream);
+            const char* failure = try_matrix_placement(plan.ef, [&](const snapshot_view_t& view, float& ms) { return launch(view, 8, &ms); }, stream);
             args.count = pending;
-            (void)hipEventDestroy(begin);
-            (void)hipEventDestroy(end);
             if (failure)
                 return failure;
         }
@@ -1286,29 +946,21 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
                 return e;
             args.wave_clock = ws.d_wave_clock;
         }
-        params.mode = call.mode;
-        params.entries_per_lane = call.entries_per_lane;
-        params.grid = grid;
-        params.lds_bytes = (std::uint32_t)lds_bytes;
         if (const char* e = timed_launch())
             return e;
         ++call.passes;
         return nullptr;
     }
 
-    // ---- last rung: global-memory scratch — exact sizes (one bit per slot, one frontier cell per slot), cannot overflow;
-    //      the reference's heap (a frontier in `top` needs `top` in registers)
+    // ---- last rung: global-memory scratch of exact size (`plan_rung`), as many waves at a time as the memory budget takes
     if (!call.have_todo) {
         call.todo.resize(call.count);
         for (std::uint32_t q = 0; q < call.count; ++q)
             call.todo[q] = q;
         call.have_todo = true;
     }
-    call.stats.retried_global = (std::uint32_t)call.todo.size();
-    const std::uint64_t bitmap_bytes = ((view_.size + 31) / 32) * 4;
-    const std::uint32_t frontier_cells = (std::uint32_t)std::min<std::uint64_t>(view_.size + 64, 0xFFFFFFF0u);
-    const scratch_layout_t layout = scratch_layout(ef, frontier_cells, bitmap_bytes);
-    const std::size_t slab = (layout.total + 255) & ~(std::size_t)255;
+    plan.stats.retried_global = (std::uint32_t)call.todo.size();
+    const std::size_t slab = rung.slab;
     const std::size_t budget = env_size("USEARCH_AMD_GLOBAL_SCRATCH_BYTES", (std::size_t)2 << 30);
     const std::size_t waves = std::max<std::size_t>(1, std::min<std::size_t>(call.todo.size(), budget / slab));
     if (const char* e = ws.reserve(call.count, waves * slab))
@@ -1317,23 +969,9 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
         const std::size_t chunk = std::min(waves, call.todo.size() - begin);
         UA_HIP(hipMemcpyAsync(ws.d_todo, call.todo.data() + begin, chunk * 4, hipMemcpyHostToDevice, stream));
         // only the bitmaps need zeroing
-        UA_HIP(hipMemset2DAsync(ws.d_scratch + layout.visits, slab, 0, bitmap_bytes, chunk, stream));
-        args.status = ws.d_status, args.peaks = ws.d_peaks;
-        args.hash_cap = 0;
-        args.next_cap = frontier_cells;
-        args.todo = ws.d_todo;
-        args.count = (std::uint32_t)chunk;
-        args.scratch = ws.d_scratch;
-        args.scratch_stride = slab;
-        args.wave_clock = nullptr;
-        args.sketch_counters = nullptr;
-        params.mode = scratch_global_k;
-        params.team = 0;
-        params.plain = 0;
-        params.entries_per_lane = 0;
-        params.frontier = frontier_heap_k;
-        params.grid = (std::uint32_t)chunk;
-        params.lds_bytes = call.query_lds;
+        UA_HIP(hipMemset2DAsync(ws.d_scratch + rung.visits_offset, slab, 0, rung.bitmap_bytes, chunk, stream));
+        args.status = ws.d_status, args.peaks = ws.d_peaks, args.todo = ws.d_todo;
+        args.count = params.grid = (std::uint32_t)chunk, args.scratch = ws.d_scratch, args.scratch_stride = slab;
         if (const char* e = timed_launch(/*keep_overflows=*/begin != 0))
             return e;
         ++call.passes;
@@ -1375,7 +1013,7 @@ const char* snapshot_t::search_finish(search_call_t& call, search_stats_t* stats
         if (call.args.sketch_counters) {
             std::uint64_t counters[2];
             std::memcpy(counters, ws.h_status + 2, 16);
-            call.stats.sketch_tested += counters[0], call.stats.sketch_pruned += counters[1];
+            call.plan.stats.sketch_tested += counters[0], call.plan.stats.sketch_pruned += counters[1];
         }
         if (call.params.mode == scratch_global_k) {
             if (ws.h_status[1])
@@ -1401,21 +1039,10 @@ const char* snapshot_t::search_finish(search_call_t& call, search_stats_t* stats
         call.reran = true;
         if (call.todo.empty())
             break;
-        if (rung == 0) {
-            call.stats.retried_lds = (std::uint32_t)call.todo.size();
-            call.mode = scratch_hash_k;
-            call.hash_cap = std::min<std::uint32_t>(call.hash_cap * 4, pow2_ceil((std::uint32_t)std::min<std::uint64_t>(view_.size * 2 + 128, 1u << 30)));
-            if (call.next_cap) {
-                const std::uint32_t lds_budget = (std::uint32_t)env_size("USEARCH_AMD_LDS_BUDGET", 160 * 1024);
-                call.next_cap = (std::uint32_t)std::min<std::uint64_t>((std::uint64_t)call.next_cap * 4, view_.size + 64);
-                while (call.next_cap > 64 &&
-                       call.query_lds + scratch_layout(call.entries_per_lane ? 0 : call.ef, call.next_cap, 0).total > lds_budget)
-                    call.next_cap = call.next_cap * 3 / 4;
-            }
-        } else {
-            call.mode = scratch_global_k;
-        }
-        if (call.mode != scratch_global_k)
+        if (rung == 0)
+            call.plan.stats.retried_lds = (std::uint32_t)call.todo.size();
+        escalate(call.shape, call.knobs, call.plan, rung);
+        if (call.plan.mode != scratch_global_k)
             UA_HIP(hipMemcpyAsync(ws.d_todo, call.todo.data(), call.todo.size() * 4, hipMemcpyHostToDevice, stream));
         if (const char* e = run_ladder(call))
             return e;
@@ -1430,7 +1057,7 @@ const char* snapshot_t::search_finish(search_call_t& call, search_stats_t* stats
         std::fprintf(stderr, "[usearch_amd] phases ef=%u grid=%u: setup %.1f%% pop+list %.1f%% visited %.1f%% distances %.1f%% "
                              "commit %.1f%% [heap push %.1f%% top insert %.1f%%, %llu candidates rechecked] dump %.1f%% (%.3g ticks); "
                              "frontier pushes %llu, lists ready ahead %llu\n",
-                     call.ef, first_grid, 100 * ticks[0] / total, 100 * ticks[1] / total, 100 * ticks[2] / total,
+                     call.plan.ef, first_grid, 100 * ticks[0] / total, 100 * ticks[1] / total, 100 * ticks[2] / total,
                      100 * ticks[3] / total, 100 * ticks[4] / total, 100 * ticks[8] / total, 100 * ticks[9] / total, ticks[10],
                      100 * ticks[5] / total, total, ticks[6], ticks[7]);
         if (ticks[15])
@@ -1449,27 +1076,27 @@ const char* snapshot_t::search_finish(search_call_t& call, search_stats_t* stats
         for (std::uint32_t w = 0; w < first_grid; ++w)
             gone += (double)(clock[2 * w] - first) + (double)(last - clock[2 * w + 1]);
         const double span = (double)(last - first);
-        call.stats.tail_idle = span > 0 ? (float)(gone / (span * first_grid)) : 0.f;
-        call.stats.span_ms = (float)(span / 1e5); // 100 MHz
+        call.plan.stats.tail_idle = span > 0 ? (float)(gone / (span * first_grid)) : 0.f;
+        call.plan.stats.span_ms = (float)(span / 1e5); // 100 MHz
         if (env_size("USEARCH_AMD_WAVE_CLOCK", 0) > 1) { // histogram of exit times, in tenths of the span
             unsigned long long bins[10] = {0};
             for (std::uint32_t w = 0; w < first_grid; ++w)
                 ++bins[std::min<std::size_t>(9, (std::size_t)(10.0 * (double)(clock[2 * w + 1] - first) / std::max(span, 1.0)))];
-            std::fprintf(stderr, "[usearch_amd] wave exits by tenth of the %.3f ms span (grid %u):", call.stats.span_ms, first_grid);
+            std::fprintf(stderr, "[usearch_amd] wave exits by tenth of the %.3f ms span (grid %u):", call.plan.stats.span_ms, first_grid);
             for (unsigned long long b : bins)
                 std::fprintf(stderr, " %llu", b);
-            std::fprintf(stderr, "; idle share %.4f\n", call.stats.tail_idle);
+            std::fprintf(stderr, "; idle share %.4f\n", call.plan.stats.tail_idle);
         }
     }
-    call.stats.passes = call.passes;
-    call.stats.kernel_ms = call.total_ms;
-    call.stats.mode = (std::uint32_t)first_mode + 1;
-    call.stats.grid = first_grid;
-    call.stats.lds_bytes = first_lds;
+    call.plan.stats.passes = call.passes;
+    call.plan.stats.kernel_ms = call.total_ms;
+    call.plan.stats.mode = (std::uint32_t)first_mode + 1;
+    call.plan.stats.grid = first_grid;
+    call.plan.stats.lds_bytes = first_lds;
     if (stats)
-        *stats = call.stats;
+        *stats = call.plan.stats;
     if (call.sketch_auto && call.count >= 1024)
-        judge_sketch(call.stats.sketch_tested, call.stats.sketch_pruned);
+        judge_sketch(call.plan.stats.sketch_tested, call.plan.stats.sketch_pruned);
     return nullptr;
 }
 

@@ -89,6 +89,51 @@ inline constexpr bool plain_build_exists(metric_kind_t metric, scalar_kind_t sca
     return all_kernel_builds(metric, scalar) && lanes <= 2 && four_deep && global_hash && (top_cells == 1 || top_cells == 2) && heap;
 }
 
+// ---- the launch planner's plain values (search_plan.hpp holds the functions that fill them: the ONE place that chooses a build)
+
+/// Every USEARCH_AMD_<NAME> override the planner looks at, read once per search call by `read_search_knobs` (0 = not set, unless
+/// noted). Numbers stay as wide as the environment gave them: the planner narrows them where it always did.
+struct search_knobs_t {
+    std::size_t lds_budget = 160 * 1024; ///< LDS_BUDGET: bytes of a compute unit's LDS the resident waves may share
+    std::size_t hash_cap = 0, hash_load_pct = 50; ///< HASH_LOAD_PCT: 10 … 75, by default 50 for rows of 8 lanes and 75 below
+    std::size_t next_cap = 0, mode = 0, top_in_memory = 0, no_two_cells = 0, frontier = 0, variant = 0, no_team = 0, no_plain = 0;
+    std::size_t waves_per_cu = 32, no_small_batch_lds = 0, early_rows = 1, claim_bits = 0, aside_cells = 0, plain_whatever_the_room = 0;
+    std::size_t seen_cells = (std::size_t)-1; ///< SEEN_CELLS: −1 = as many as cost no resident wave, 0 = none
+    std::size_t probe_mode = 0, probe_load_first = 0; ///< read under USEARCH_AMD_EXPERIMENT_PROBE_MODES only
+};
+
+/// What the planner needs to know about the index and the call.
+struct search_shape_t {
+    std::uint64_t size = 0, count = 0, wanted = 0, expansion = 0;
+    std::int32_t metric = 0, scalar = 0; ///< `kernel_metric` of the index's metric_kind_t; its scalar_kind_t
+    std::uint32_t lanes = 0, chunks = 0, m0 = 0, compute_units = 0;
+    std::uint32_t has_tombstones = 0, nbr0 = 0, nbr0_rows = 0, sketch = 0; ///< flags: which arrays of the view are there
+    std::uint32_t query_ids = 0, beam_level = 0, descent_only = 0, allow_bits = 0, exclude_own = 0, reference_frontier = 0; ///< search_extras_t
+};
+
+/// What `plan_search` settles for the whole call; `plan_rung` and `escalate` revise it on the way up the retry ladder.
+struct search_plan_t {
+    std::uint32_t ef = 0, query_lds = 0, entries_per_lane = 0, waves_cap = 0, hash_cap = 0, next_cap = 0;
+    std::int32_t mode = 0, variant = 0, frontier = 0; ///< scratch_mode_t, kernel_variant_t, frontier_mode_t of kernels.hpp
+    std::uint32_t team = 0;           ///< five waves per query (kernels.hpp team_search_kernel)
+    std::uint32_t plain_possible = 0; ///< short rows: nothing known before the first rung rules the build cut for plain batches out
+    std::uint32_t sketch = 0;         ///< the walk tests candidates against the sketch, until a rung finds no LDS for its coefficients
+    /// The decisions as `search_stats_t` reports them — `plan_search`: frontier, variant, top_cells; `plan_rung`: early_rows, plain,
+    /// aside_cells, over short rows probe_mode, seen_cells, claim_bits, and variant again when a team is demoted — next to which
+    /// the engine writes what the device did.
+    search_stats_t stats{};
+};
+
+/// One launch of the ladder as `plan_rung` shapes it: what goes into `launch_params_t` and `search_args_t`.
+struct search_rung_t {
+    std::int32_t mode = 0, frontier = 0;
+    std::uint32_t team = 0, plain = 0, entries_per_lane = 0, grid = 0, lds_bytes = 0, hash_cap = 0, next_cap = 0;
+    std::uint32_t early_rows = 0, probe_mode = 0, claim_offset = 0, claim_bits = 0, aside_offset = 0, aside_cells = 0, seen_offset = 0,
+        seen_cells = 0, sketch_offset = 0, team_offset = 0;
+    std::uint64_t slab = 0;                            ///< bytes of global scratch per wave
+    std::uint64_t visits_offset = 0, bitmap_bytes = 0; ///< the global rung: where in a slab the bitmap sits, which the host zeroes
+};
+
 /// Per-scalar-kind launchers, one translation unit each (compile time): defined in search_<kind>.hip.
 struct launch_params_t {
     metric_kind_t metric;
@@ -196,15 +241,14 @@ class snapshot_t {
         search_args_t args{};
         launch_params_t params{};
         std::size_t count = 0;
-        std::uint32_t ef = 0, hash_cap = 0, next_cap = 0, query_lds = 0, entries_per_lane = 0, waves_cap = 0;
-        int mode = 0;
+        search_shape_t shape{}; ///< what the planner (search_plan.hpp) was told, …
+        search_knobs_t knobs{}; ///< … the environment's overrides as they stood when the call began, …
+        search_plan_t plan{};   ///< … and what it decided; `plan.stats` is the call's statistics
         bool timed = false, want_phases = false, want_clock = false, done = false, reran = false;
-        bool plain_possible = false; ///< short rows: nothing known at search_begin rules the build cut for plain batches out (`plain_ak`)
         bool sketch_auto = false;    ///< this call used the sketch in auto mode: its counters judge it (`judge_sketch`)
         bool keep_workspace = false; ///< search_finish leaves the workspace with the caller (who gives it back)
         float total_ms = 0.f;
         std::uint32_t passes = 0;
-        search_stats_t stats{};
         std::vector<std::uint32_t> todo;
         bool have_todo = false;
     };

@@ -12,6 +12,8 @@
 #include "kernels.hpp"
 #include "kmeans.hpp"
 #include "placement.hpp"
+#include "search_plan.hpp"
+#include "usearch_amd.h"
 
 typedef char const* usearch_amd_error_t;
 namespace {
@@ -293,4 +295,39 @@ extern "C" __attribute__((visibility("default"))) void usearch_amd_test_kmeans_q
                                                                                         size_t out_stride, usearch_amd_error_t* error) {
     fail(error, kmeans_quantize(static_cast<const std::uint8_t*>(points), count, stride, (scalar_kind_t)scalar_kind, dimensions,
                                 (scalar_kind_t)quantization_kind, device, static_cast<std::uint8_t*>(out), out_stride));
+}
+
+// ---- the launch planner (search_plan.hpp) on plain values, for tests/test_search_plan.py: what `search_begin` settles for the call
+//      described by `shape` and `tuning`, then one rung of the retry ladder per entry of `pending` (the queries that rung runs over: all
+//      of them, then those that outgrew their scratch), `escalate` between them, until a rung is the global one. `knobs` null = the
+//      environment, read as the engine reads it. → rungs planned (0 and `error` set: the call is refused); `plan->stats` reports what
+//      `search_finish` would, as far as that is decided and not measured.
+static_assert(sizeof(usearch_amd::search_stats_t) == sizeof(usearch_amd_stats_t), "tests read `search_plan_t::stats` as the C ABI's struct");
+extern "C" __attribute__((visibility("default"))) size_t usearch_amd_test_plan_search(const usearch_amd::search_shape_t* shape,
+                                                                                      const usearch_amd::search_tuning_t* tuning,
+                                                                                      const uint32_t* pending, size_t pending_count,
+                                                                                      const usearch_amd::search_knobs_t* knobs,
+                                                                                      usearch_amd::search_plan_t* plan,
+                                                                                      usearch_amd::search_rung_t* rungs,
+                                                                                      usearch_amd_error_t* error) {
+    using namespace usearch_amd;
+    const search_knobs_t read = knobs ? *knobs : read_search_knobs(shape->lanes);
+    if (const char* e = plan_search(*shape, *tuning, read, *plan)) {
+        fail(error, e);
+        return 0;
+    }
+    size_t planned = 0;
+    for (; planned < pending_count && !(planned && rungs[planned - 1].mode == scratch_global_k); ++planned) {
+        if (planned == 1)
+            plan->stats.retried_lds = pending[planned];
+        if (planned)
+            escalate(*shape, read, *plan, (int)planned - 1);
+        plan_rung(*shape, read, *plan, pending[planned], rungs[planned]);
+        if (rungs[planned].mode == scratch_global_k)
+            plan->stats.retried_global = pending[planned];
+    }
+    plan->stats.passes = (std::uint32_t)planned;
+    if (planned)
+        plan->stats.mode = (std::uint32_t)rungs[0].mode + 1, plan->stats.grid = rungs[0].grid, plan->stats.lds_bytes = rungs[0].lds_bytes;
+    return planned;
 }

@@ -1145,10 +1145,59 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_sketch_bounds.restype = None
         _test_hooks.usearch_amd_test_sketch_bounds.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
                                                                C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_plan_search.restype = C.c_size_t
+        _test_hooks.usearch_amd_test_plan_search.argtypes = [C.POINTER(PlanShape), C.POINTER(PlanTuning), C.c_void_p, C.c_size_t,
+                                                             C.POINTER(PlanKnobs), C.POINTER(Plan), C.POINTER(PlanRung),
+                                                             C.POINTER(C.c_char_p)]
         _test_hooks.usearch_amd_test_kmeans_quantize.restype = None
         _test_hooks.usearch_amd_test_kmeans_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
     return _test_hooks
+
+
+class _PlainStruct(C.Structure):
+    def as_dict(self) -> dict:
+        values = ((name, getattr(self, name)) for name, _ in self._fields_)
+        return {name: ({field: getattr(value, field) for field, _ in value._fields_} if isinstance(value, C.Structure) else value)
+                for name, value in values}
+
+
+def _struct(name: str, *groups) -> type:
+    return type(name, (_PlainStruct,), {"_fields_": [(field, kind) for kind, fields in groups for field in fields.split()]})
+
+
+# the planner's plain structs (csrc/engine.hpp: search_shape_t, search_tuning_t, search_knobs_t, search_plan_t, search_rung_t)
+PlanShape = _struct("PlanShape", (C.c_uint64, "size count wanted expansion"), (C.c_int32, "metric scalar"),
+                    (C.c_uint32, "lanes chunks m0 compute_units has_tombstones nbr0 nbr0_rows sketch query_ids beam_level descent_only "
+                                 "allow_bits exclude_own reference_frontier"))
+PlanTuning = _struct("PlanTuning", (C.c_uint32, "hash_cap next_cap variant mode waves_per_cu top_in_memory frontier wave_clock sketch"))
+PlanKnobs = _struct("PlanKnobs", (C.c_size_t, "lds_budget hash_cap hash_load_pct next_cap mode top_in_memory no_two_cells frontier variant "
+                                              "no_team no_plain waves_per_cu no_small_batch_lds early_rows claim_bits aside_cells "
+                                              "plain_whatever_the_room seen_cells probe_mode probe_load_first"))
+Plan = _struct("Plan", (C.c_uint32, "ef query_lds entries_per_lane waves_cap hash_cap next_cap"), (C.c_int32, "mode variant frontier"),
+               (C.c_uint32, "team plain_possible sketch"), (Stats, "stats"))
+PlanRung = _struct("PlanRung", (C.c_int32, "mode frontier"),
+                   (C.c_uint32, "team plain entries_per_lane grid lds_bytes hash_cap next_cap early_rows probe_mode claim_offset claim_bits "
+                                "aside_offset aside_cells seen_offset seen_cells sketch_offset team_offset"),
+                   (C.c_uint64, "slab visits_offset bitmap_bytes"))
+
+
+def test_plan_search(shape: dict, tuning: dict, pending, knobs: Optional[dict] = None):
+    """The launch planner (csrc/search_plan.hpp) on plain values, no GPU involved: what a search of `shape` (fields of `PlanShape`;
+    `metric` and `dtype` by name) under `tuning` settles, and one rung of the retry ladder per entry of `pending` until one is the
+    global rung. `knobs` (fields of `PlanKnobs`) replace the environment's overrides; None reads USEARCH_AMD_* as the engine does.
+    → (plan, [rung, …]) as dicts, `plan["stats"]` holding what `Stats` would report of these decisions; a refusal raises."""
+    shape = dict(shape)  # metric_kind_t (jaccard walks as tanimoto) and scalar_kind_t of csrc/common.hpp
+    shape["metric"] = ord({"ip": "i", "cos": "c", "l2sq": "e", "hamming": "b", "pearson": "p", "haversine": "h", "divergence": "d",
+                           "jaccard": "t", "tanimoto": "t", "sorensen": "s"}[shape["metric"]])
+    shape["scalar"] = {"b1": 1, "bf16": 4, "f64": 10, "f32": 11, "f16": 12, "i8": 23}[shape.pop("dtype")]
+    pending = np.ascontiguousarray(pending, dtype=np.uint32)
+    plan, rungs, err = Plan(), (PlanRung * max(1, len(pending)))(), C.c_char_p()
+    planned = test_hooks().usearch_amd_test_plan_search(C.byref(PlanShape(**shape)), C.byref(PlanTuning(**tuning)), _pointer(pending),
+                                                        len(pending), C.byref(PlanKnobs(**knobs)) if knobs is not None else None,
+                                                        C.byref(plan), rungs, C.byref(err))
+    _raise(err, "usearch_amd_test_plan_search")
+    return plan.as_dict(), [rungs[i].as_dict() for i in range(planned)]
 
 
 def test_kmeans_quantize(X: np.ndarray, from_dtype: str, to_dtype: str, device: int = 0) -> np.ndarray:
