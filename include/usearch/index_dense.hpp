@@ -458,6 +458,16 @@ struct index_join_config_t {
     bool exact = false;
 };
 
+/// `index_dense_clustering_config_t` (index_dense.hpp:161-168); `mode` is carried and, as there, never read.
+struct index_dense_clustering_config_t {
+    std::size_t min_clusters = 0;
+    std::size_t max_clusters = 0;
+    enum mode_t {
+        merge_smallest_k,
+        merge_closest_k,
+    } mode = merge_smallest_k;
+};
+
 /// `join_result_t` (index.hpp:4321-4333). `engagements` and the two counters are the device's: parallel rounds make no
 /// intermediate engagements, and one search per proposer stands for the reference's one search per proposal.
 struct join_result_t {
@@ -788,6 +798,56 @@ template <typename key_at = default_key_t, typename compressed_slot_at = default
             return result.failed(error);
         std::size_t const total = size();
         progress(total, total);
+        return result;
+    }
+    struct clustering_result_t { // index_dense.hpp:1788-1799
+        error_t error{};
+        std::size_t clusters{};
+        std::size_t visited_members{};
+        std::size_t computed_distances{};
+
+        explicit operator bool() const noexcept { return !error; }
+        clustering_result_t failed(error_t message) noexcept {
+            error = std::move(message);
+            return std::move(*this);
+        }
+    };
+    /// `cluster(begin, end, config, cluster_keys, cluster_distances, executor, progress)` (index_dense.hpp:1819-1981) on the device:
+    /// the iterator dereferences to `scalar const*` or to `vector_key_t`, as there; the queries are gathered into one host buffer.
+    /// Equal popularities are ordered by centroid key; `min_clusters` > 0 with `max_clusters` == 0 is an error (the reference never
+    /// returns from it). The executor and `progress` are accepted and ignored.
+    template <typename queries_iterator_at, typename executor_at = dummy_executor_t, typename progress_at = dummy_progress_t>
+    clustering_result_t cluster(queries_iterator_at queries_begin, queries_iterator_at queries_end, index_dense_clustering_config_t config,
+                                vector_key_t* cluster_keys, distance_t* cluster_distances, executor_at&& = executor_at{},
+                                progress_at&& = progress_at{}) {
+        clustering_result_t result;
+        std::size_t const queries_count = static_cast<std::size_t>(queries_end - queries_begin);
+        std::vector<usearch_key_t> found(queries_count);
+        std::size_t stats[3] = {};
+        usearch_error_t error = nullptr;
+        using query_t = typename std::decay<decltype(queries_begin[0])>::type;
+        if constexpr (std::is_pointer<query_t>::value) {
+            using scalar_t = typename std::remove_cv<typename std::remove_pointer<query_t>::type>::type;
+            scalar_kind_t const kind = amd_detail::kind_of<scalar_t>::value;
+            std::size_t const row_bytes = metric_punned_t::builtin(dimensions(), metric_kind_t::ip_k, kind).bytes_per_vector();
+            std::vector<byte_t> rows(queries_count * row_bytes);
+            for (std::size_t i = 0; i != queries_count; ++i)
+                std::memcpy(rows.data() + i * row_bytes, queries_begin[i], row_bytes);
+            usearch_clustering(handle_, rows.data(), amd_detail::to_c(kind), queries_count, row_bytes, config.min_clusters,
+                               config.max_clusters, found.data(), cluster_distances, stats, &error);
+        } else {
+            std::vector<usearch_key_t> members(queries_count);
+            for (std::size_t i = 0; i != queries_count; ++i)
+                members[i] = static_cast<usearch_key_t>(queries_begin[i]);
+            usearch_key_t const none = 0;
+            usearch_clustering_members(handle_, queries_count ? members.data() : &none, queries_count, config.min_clusters,
+                                       config.max_clusters, found.data(), cluster_distances, stats, &error);
+        }
+        if (error)
+            return result.failed(error);
+        for (std::size_t i = 0; i != queries_count; ++i)
+            cluster_keys[i] = static_cast<vector_key_t>(found[i]);
+        result.clusters = stats[0], result.visited_members = stats[1], result.computed_distances = stats[2];
         return result;
     }
     std::size_t size() const noexcept { return get_(amd_detail::api().size); }

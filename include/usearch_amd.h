@@ -305,6 +305,53 @@ USEARCH_AMD_EXPORT void usearch_amd_cluster_many(usearch_amd_snapshot_t snapshot
                                                  usearch_amd_key_t* keys, usearch_amd_distance_t* distances,
                                                  uint64_t* visited, uint64_t* computed, usearch_amd_error_t* error);
 
+/* ---- clustering of a batch by the index's own levels ------------------------------------------------------------------ */
+
+/** Zero-initialise and set `struct_size = sizeof(usearch_amd_clustering_config_t)`. */
+typedef struct usearch_amd_clustering_config_t {
+    size_t struct_size;  /**< size of this struct as the caller knows it: later fields are read only when it covers them */
+    size_t min_clusters; /**< 0 = level 1 as it stands, nothing merged */
+    size_t max_clusters; /**< must be set when `min_clusters` is (the reference never returns from min > 0, max == 0) */
+} usearch_amd_clustering_config_t;
+
+typedef struct usearch_amd_clustering_stats_t {
+    uint64_t clusters;            /**< centroids left after the merges: `clustering_result_t::clusters` */
+    uint64_t unique_before_merge; /**< distinct centroids the last mapping pass reached */
+    uint64_t merge_cycles;
+    uint64_t mapping_passes;      /**< 1 + the refinements (a level down while fewer than `min_clusters` centroids are reached) */
+    uint64_t visited_members, computed_distances; /**< sums over every mapping pass; merges and closing distances do not count */
+    uint32_t level, reserved;     /**< the level of the last mapping pass */
+    float seconds_map, seconds_merge, seconds_trace;
+} usearch_amd_clustering_stats_t;
+
+/**
+ *  `index_dense_gt::cluster(begin, end, config, keys, distances)` (index_dense.hpp:1819-1981) on the device: the level with more
+ *  than `min_clusters` nodes, every query's greedy descent to it (`usearch_amd_cluster_many`), the centroids' popularity, a level
+ *  down while too few are reached, the least popular centroid merged into its nearest until `max_clusters` are left, every query
+ *  traced to the centroid that survived and measured against it again. Host buffers, queries in any scalar kind; `keys_out` and
+ *  `distances_out` hold one cell per query. Equal popularities are ordered by centroid key, ascending (the reference leaves them
+ *  to `std::sort`). Errors by name: "Index too small to cluster!" (`max_level` < 2), `min_clusters` > 0 with `max_clusters` == 0.
+ *  Refused while a search of the snapshot is in flight. `stats` may be NULL.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_clustering(usearch_amd_snapshot_t snapshot, void const* queries, int query_kind, size_t count,
+                                               size_t stride, usearch_amd_clustering_config_t const* config,
+                                               usearch_amd_key_t* keys_out, usearch_amd_distance_t* distances_out,
+                                               usearch_amd_clustering_stats_t* stats, usearch_amd_error_t* error);
+/**
+ *  The same with members as queries — their stored rows, in the storage kind (index_dense.hpp:869-899). `member_keys` NULL: every
+ *  member that was not removed, in slot order (`count` must be their number). A key the index does not hold: "Key missing!".
+ *  Refused for an index that lets members share a key.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_clustering_members(usearch_amd_snapshot_t snapshot, usearch_amd_key_t const* member_keys,
+                                                       size_t count, usearch_amd_clustering_config_t const* config,
+                                                       usearch_amd_key_t* keys_out, usearch_amd_distance_t* distances_out,
+                                                       usearch_amd_clustering_stats_t* stats, usearch_amd_error_t* error);
+
+/** Keys of the members that were not removed, in slot order: what `usearch_amd_clustering_members` clusters when it is given no
+ *  keys. Returns their number; `keys_out` (may be NULL) receives at most `capacity` of them. One read-back of the key array. */
+USEARCH_AMD_EXPORT size_t usearch_amd_snapshot_live_keys(usearch_amd_snapshot_t snapshot, usearch_amd_key_t* keys_out, size_t capacity,
+                                                         usearch_amd_error_t* error);
+
 /**
  *  The same exact search as a TILED MATRIX PRODUCT on the matrix units (usearch_amd/csrc/exact_tiled.hip) — what the reference's
  *  `exact_search_t` does with its distance matrix (index_plugins.hpp:2071-2164): dataset rows are read once per 64 queries

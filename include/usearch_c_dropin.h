@@ -259,6 +259,27 @@ USEARCH_COMPACTION_API size_t usearch_isolate(usearch_index_t index, usearch_err
  *  they stand, nothing is linked anew) and is served and saved from its device state from then on; the same holds for `usearch_isolate`.
  */
 USEARCH_COMPACTION_API size_t usearch_compact(usearch_index_t index, usearch_error_t* error);
+/* Clustering by the index's own levels: declared like the two above, and like them not in the function table (its 52 entries are
+ * pinned by tests/test_gpu_join.py); include/usearch/index_dense.hpp calls them by name, as it calls `usearch_isolate`. */
+#ifndef USEARCH_CLUSTERING_API
+#define USEARCH_CLUSTERING_API __attribute__((visibility("default")))
+#endif
+/**
+ *  `index_dense_gt::cluster(begin, end, config, keys, distances)` (index_dense.hpp:1819-1981) on the device: the queries descend to
+ *  the level with more than `min_clusters` nodes, the least popular centroids merge into their nearest until `max_clusters` are
+ *  left, every query is traced to the centroid that survived. `keys` / `distances`: one cell per query. `stats` (may be NULL):
+ *  {clusters, visited_members, computed_distances}. Equal popularities are ordered by centroid key, ascending. Errors by name:
+ *  "Index too small to cluster!"; `min_clusters` > 0 with `max_clusters` == 0 (the reference never returns from it). Pending adds
+ *  are linked first, as a search does.
+ */
+USEARCH_CLUSTERING_API void usearch_clustering(usearch_index_t index, void const* queries, usearch_scalar_kind_t query_kind,
+                                               size_t queries_count, size_t queries_stride, size_t min_clusters, size_t max_clusters,
+                                               usearch_key_t* keys, usearch_distance_t* distances, size_t* stats, usearch_error_t* error);
+/** The same with members as queries (index_dense.hpp:869-899): `member_keys` NULL = every member that was not removed, in slot
+ *  order (`count` must be their number: `usearch_size`). A key the index does not hold: "Key missing!". Refused for a multi-index. */
+USEARCH_CLUSTERING_API void usearch_clustering_members(usearch_index_t index, usearch_key_t const* member_keys, size_t count,
+                                                       size_t min_clusters, size_t max_clusters, usearch_key_t* keys,
+                                                       usearch_distance_t* distances, size_t* stats, usearch_error_t* error);
 /** Threads `usearch_change_threads_add / _search` recorded (the reference's `index_limits_t`, index.hpp:1338-1357). */
 USEARCH_EXPORT size_t usearch_threads_search(usearch_index_t index, usearch_error_t* error);
 /** Takes (or refreshes) the HBM snapshot now instead of at the next search. */

@@ -4,6 +4,6 @@
 walks it with hand-written gfx950 kernels. See DESIGN.md.
 """
 from .index import (BatchMatches, BuildConfig, BuildStats, BuiltIndex, Index, build, Matches, Stats, Tuning, cast, device_count, exact_search,  # noqa: F401
-                    CompactConfig, CompactStats, KMeansConfig, KMeansStats, kmeans, kmeans_assign, library, merge_many, note_device_free, settle, LIBRARY_PATH, EXPORTED_SYMBOLS)
+                    CompactConfig, CompactStats, Clustering, ClusteringConfig, ClusteringStats, KMeansConfig, KMeansStats, kmeans, kmeans_assign, library, merge_many, note_device_free, settle, LIBRARY_PATH, EXPORTED_SYMBOLS)
 
-__all__ = ["Index", "BuiltIndex", "build", "Matches", "BatchMatches", "Tuning", "Stats", "cast", "kmeans", "kmeans_assign", "device_count", "library", "note_device_free", "settle"]
+__all__ = ["Index", "BuiltIndex", "build", "Matches", "BatchMatches", "Clustering", "Tuning", "Stats", "cast", "kmeans", "kmeans_assign", "device_count", "library", "note_device_free", "settle"]

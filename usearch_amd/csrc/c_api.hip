@@ -13,10 +13,12 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <unordered_map>
 #include <vector>
 
 #include "build.hpp"
 #include "casts.hpp"
+#include "clustering.hpp"
 #include "compact.hpp"
 #include "engine.hpp"
 #include "filter.hpp"
@@ -786,6 +788,111 @@ void usearch_amd_build_compact(usearch_amd_builder_t builder, usearch_amd_compac
     compact_stats_to_c(s, stats);
 } catch (...) {
     fail_from_exception(error);
+}
+
+// ---- clustering by the index's own levels (clustering.hpp)
+namespace {
+
+void clustering_config_from_c(usearch_amd_clustering_config_t const* config, clustering_config_t& c) {
+    if (config && config->struct_size >= offsetof(usearch_amd_clustering_config_t, max_clusters) + sizeof(config->max_clusters))
+        c.min_clusters = config->min_clusters, c.max_clusters = config->max_clusters;
+}
+
+void clustering_stats_to_c(const clustering_stats_t& s, usearch_amd_clustering_stats_t* out) {
+    if (!out)
+        return;
+    *out = usearch_amd_clustering_stats_t{};
+    out->clusters = s.clusters, out->unique_before_merge = s.unique_before_merge, out->merge_cycles = s.merge_cycles;
+    out->mapping_passes = s.mapping_passes, out->visited_members = s.visited_members, out->computed_distances = s.computed_distances;
+    out->level = s.level;
+    out->seconds_map = s.seconds_map, out->seconds_merge = s.seconds_merge, out->seconds_trace = s.seconds_trace;
+}
+
+} // namespace
+
+void usearch_amd_clustering(usearch_amd_snapshot_t snapshot, void const* queries, int query_kind, size_t count, size_t stride,
+                            usearch_amd_clustering_config_t const* config, usearch_amd_key_t* keys_out,
+                            usearch_amd_distance_t* distances_out, usearch_amd_clustering_stats_t* stats, usearch_amd_error_t* error) try {
+    const scalar_kind_t kind = scalar_from_c(query_kind);
+    if (kind == scalar_unknown_k)
+        return fail(error, "Unknown scalar kind!");
+    if (count && !queries)
+        return fail(error, "Clustering needs the query buffer");
+    clustering_config_t c;
+    clustering_config_from_c(config, c);
+    clustering_stats_t s;
+    std::uint8_t nothing = 0; // an empty batch is still the vector form
+    if (const char* e = as_snapshot(snapshot)->clustering(queries ? queries : &nothing, kind, count, stride, nullptr, c, keys_out, distances_out, &s))
+        return fail(error, e);
+    clustering_stats_to_c(s, stats);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+void usearch_amd_clustering_members(usearch_amd_snapshot_t snapshot, usearch_amd_key_t const* member_keys, size_t count,
+                                    usearch_amd_clustering_config_t const* config, usearch_amd_key_t* keys_out,
+                                    usearch_amd_distance_t* distances_out, usearch_amd_clustering_stats_t* stats,
+                                    usearch_amd_error_t* error) try {
+    snapshot_t& index = *as_snapshot(snapshot);
+    clustering_config_t c;
+    clustering_config_from_c(config, c);
+    clustering_stats_t s;
+    std::vector<std::uint32_t> slots;
+    if (member_keys && count && !index.multi()) { // not the hot path: one read-back of the keys, one host map
+        const std::uint64_t n = index.view().size;
+        std::vector<std::uint64_t> keys(n);
+        if (n) {
+            hipError_t e = hipSetDevice(index.device());
+            if (e == hipSuccess)
+                e = hipMemcpy(keys.data(), index.view().keys, n * 8, hipMemcpyDeviceToHost);
+            if (e != hipSuccess)
+                return fail(error, hipGetErrorString(e));
+        }
+        std::unordered_map<std::uint64_t, std::uint32_t> slot_of;
+        slot_of.reserve(n);
+        for (std::uint64_t i = 0; i < n; ++i)
+            if (keys[i] != free_key_k)
+                slot_of.emplace(keys[i], (std::uint32_t)i);
+        slots.resize(count);
+        for (size_t q = 0; q < count; ++q) {
+            const auto found = slot_of.find(member_keys[q]);
+            if (found == slot_of.end())
+                return fail(error, "Key missing!");
+            slots[q] = found->second;
+        }
+    }
+    if (const char* e = index.clustering(nullptr, index.scalar(), count, 0, slots.empty() ? nullptr : slots.data(), c, keys_out, distances_out, &s))
+        return fail(error, e);
+    clustering_stats_to_c(s, stats);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+size_t usearch_amd_snapshot_live_keys(usearch_amd_snapshot_t snapshot, usearch_amd_key_t* keys_out, size_t capacity,
+                                      usearch_amd_error_t* error) try {
+    snapshot_t& index = *as_snapshot(snapshot);
+    const std::uint64_t n = index.view().size;
+    std::vector<std::uint64_t> keys(n);
+    if (n) {
+        hipError_t e = hipSetDevice(index.device());
+        if (e == hipSuccess)
+            e = hipMemcpy(keys.data(), index.view().keys, n * 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            fail(error, hipGetErrorString(e));
+            return 0;
+        }
+    }
+    size_t live = 0;
+    for (std::uint64_t i = 0; i < n; ++i)
+        if (keys[i] != free_key_k) {
+            if (keys_out && live < capacity)
+                keys_out[live] = keys[i];
+            ++live;
+        }
+    return live;
+} catch (...) {
+    fail_from_exception(error);
+    return 0;
 }
 
 int usearch_amd_cast(int from_kind, int to_kind, void const* input, size_t dimensions, void* output) {

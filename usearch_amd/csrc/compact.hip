@@ -304,6 +304,16 @@ const char* launch_lists(const u32* source, u32* destination, u32 width, u64 lis
 
 } // namespace
 
+const char* mark_list_starts(const std::uint32_t* upper_ref, std::uint64_t members, std::uint64_t lists, std::uint8_t* starts,
+                             hipStream_t stream) {
+    UA_HIP(hipMemsetAsync(starts, 0, std::max<std::size_t>(lists, 16), stream));
+    if (!members)
+        return nullptr;
+    hipLaunchKernelGGL(compact_starts_kernel, dim3((unsigned)((members + 255) / 256)), dim3(256), 0, stream, upper_ref, members, lists, starts);
+    UA_HIP(hipGetLastError());
+    return nullptr;
+}
+
 const char* snapshot_t::isolate(compact_stats_t* stats_out) {
     compact_stats_t stats{};
     {
@@ -393,12 +403,10 @@ const char* snapshot_t::compact(const compact_config_t& config, std::uint32_t* s
     totals.best = 0xFFFFFFFFull; // level 0, new slot 0: what an index of level-0 survivors elects
     totals.first_removed = none_slot_k;
     UA_HIP(hipMemcpyAsync(d_totals, &totals, sizeof(totals), hipMemcpyHostToDevice, stream_));
-    UA_HIP(hipMemsetAsync(d_starts, 0, std::max<std::size_t>(lists, 16), stream_));
     // a list no member owns (there should be none) goes nowhere instead of wherever the fresh allocation points
     UA_HIP(hipMemsetAsync(d_list_target, 0xFF, std::max<std::size_t>(lists * 4, 16), stream_));
-    const unsigned member_blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(compact_starts_kernel, dim3(member_blocks), dim3(256), 0, stream_, view_.upper_ref, n, lists, d_starts);
-    UA_HIP(hipGetLastError());
+    if (const char* e = mark_list_starts(view_.upper_ref, n, lists, d_starts, stream_))
+        return e;
     hipLaunchKernelGGL(compact_counts_kernel, dim3(chunks), dim3(256), 0, stream_, view_.keys, view_.upper_ref, d_starts, n, lists, d_levels,
                        d_chunk_live, d_chunk_lists);
     UA_HIP(hipGetLastError());

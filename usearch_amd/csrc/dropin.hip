@@ -37,6 +37,7 @@
 
 #include "build.hpp"
 #include "casts.hpp"
+#include "clustering.hpp"
 #include "combiner.hpp"
 #include "compact.hpp"
 #include "engine.hpp"
@@ -1552,6 +1553,66 @@ size_t usearch_compact(usearch_index_t handle, usearch_error_t* error) {
             delete index.builder, index.builder = nullptr; // staged and empty: the next add builds anew
         return (std::size_t)stats.removed_members;
     });
+}
+
+/// Both forms of `usearch_clustering*`: `member_slots` / `members` as `snapshot_t::clustering` takes them.
+static void clustering_shared(index_t& index, const void* queries, scalar_kind_t kind, std::size_t count, std::size_t stride,
+                              const usearch_key_t* member_keys, bool members, std::size_t min_clusters, std::size_t max_clusters,
+                              usearch_key_t* keys, usearch_distance_t* distances, std::size_t* stats, usearch_error_t* error) {
+    guarded(error, [&] {
+        unique_lock_t lock(index.mutex);
+        snapshot_t* device_index = nullptr;
+        if (const char* e = index.ready(&device_index)) // links what `usearch_add` deferred, as a search does
+            return fail(error, e);
+        if (!device_index)
+            return fail(error, "Index too small to cluster!");
+        std::vector<std::uint32_t> slots;
+        if (members && index.multi)
+            return fail(error, "Clustering by member keys is not available for a multi-index");
+        if (members && member_keys) {
+            slots.resize(count);
+            const auto& lookup = index.key_lookup();
+            for (std::size_t q = 0; q < count; ++q) {
+                const auto found = lookup.find(member_keys[q]);
+                if (found == lookup.end())
+                    return fail(error, "Key missing!"); // index_dense.hpp:875-876
+                slots[q] = found->second;
+            }
+        }
+        clustering_config_t config;
+        config.min_clusters = min_clusters, config.max_clusters = max_clusters;
+        clustering_stats_t s;
+        std::vector<std::uint64_t> found(count);
+        std::uint8_t nothing = 0;
+        if (const char* e = device_index->clustering(members ? nullptr : (queries ? queries : &nothing), kind, count, stride,
+                                                     slots.empty() ? nullptr : slots.data(), config, found.data(), distances, &s))
+            return fail(error, e);
+        if (keys)
+            std::copy(found.begin(), found.end(), keys);
+        if (stats)
+            stats[0] = (std::size_t)s.clusters, stats[1] = (std::size_t)s.visited_members, stats[2] = (std::size_t)s.computed_distances;
+    });
+}
+
+void usearch_clustering(usearch_index_t handle, void const* queries, usearch_scalar_kind_t query_kind, size_t queries_count,
+                        size_t queries_stride, size_t min_clusters, size_t max_clusters, usearch_key_t* keys,
+                        usearch_distance_t* distances, size_t* stats, usearch_error_t* error) {
+    const scalar_kind_t kind = scalar_from_c(query_kind);
+    if (kind == scalar_unknown_k)
+        return fail(error, "Unknown scalar kind!");
+    if (queries_count && (!queries || !keys || !distances))
+        return fail(error, "Clustering needs the query, key and distance buffers");
+    clustering_shared(*as_index(handle), queries, kind, queries_count, queries_stride, nullptr, false, min_clusters, max_clusters, keys,
+                      distances, stats, error);
+}
+
+void usearch_clustering_members(usearch_index_t handle, usearch_key_t const* member_keys, size_t count, size_t min_clusters,
+                                size_t max_clusters, usearch_key_t* keys, usearch_distance_t* distances, size_t* stats,
+                                usearch_error_t* error) {
+    if (count && (!keys || !distances))
+        return fail(error, "Clustering needs the key and distance buffers");
+    index_t& index = *as_index(handle);
+    clustering_shared(index, nullptr, index.scalar, count, 0, member_keys, true, min_clusters, max_clusters, keys, distances, stats, error);
 }
 
 void usearch_gpu_release(usearch_index_t handle, usearch_error_t*) {

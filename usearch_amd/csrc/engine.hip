@@ -526,6 +526,7 @@ const char* snapshot_t::build(const image_t& image, int device) {
     UA_HIP(hipSetDevice(device));
     metric_ = image.metric;
     scalar_ = image.scalar;
+    multi_ = image.multi;
     count_present_ = image.count_present;
 
     const std::uint64_t n = image.size;
@@ -666,8 +667,7 @@ static hipError_t launch_search(metric_kind_t metric, scalar_kind_t scalar, cons
     return hipErrorInvalidValue;
 }
 
-static hipError_t launch_distances(metric_kind_t metric, scalar_kind_t scalar, const distances_params_t& p,
-                                   const snapshot_view_t& view) {
+hipError_t launch_distances(metric_kind_t metric, scalar_kind_t scalar, const distances_params_t& p, const snapshot_view_t& view) {
     metric = kernel_metric(metric);
 #define UA_PAIR(m, sc, name)                                                                                           \
     if (metric == m && scalar == sc)                                                                                   \

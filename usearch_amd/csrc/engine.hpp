@@ -24,6 +24,8 @@ namespace usearch_amd {
 
 struct compact_config_t; // compact.hpp
 struct compact_stats_t;
+struct clustering_config_t; // clustering.hpp
+struct clustering_stats_t;
 
 /// Tunables of one search launch; zeros mean "choose for me".
 struct search_tuning_t {
@@ -353,6 +355,20 @@ class snapshot_t {
      */
     const char* compact(const compact_config_t& config, std::uint32_t* slot_map, compact_stats_t* stats);
 
+    /**
+     *  `index_dense_gt::cluster(begin, end, config, keys, distances)` (index_dense.hpp:1819-1981) for a batch: level choice, descent,
+     *  popularity count, refinement, merges and trace, everything between the first descent and the copy-out in HBM (clustering.hpp
+     *  has the rules, clustering.hip the kernels). `queries` (host, `query_kind`, `stride_bytes` apart) or, when null, members as
+     *  queries: `member_slots` (host, [count]) names them, null = every member whose key is not `free_key_k` in slot order (`count`
+     *  must be their number). `keys` / `distances`: host, [count]. Refused while search workspaces are leased.
+     */
+    const char* clustering(const void* queries, scalar_kind_t query_kind, std::size_t count, std::size_t stride_bytes,
+                           const std::uint32_t* member_slots, const clustering_config_t& config, std::uint64_t* keys,
+                           float* distances, clustering_stats_t* stats);
+    /// Several members may share a key (the image's head says so; a builder's configuration does).
+    bool multi() const { return multi_; }
+    void set_multi(bool multi) { multi_ = multi; }
+
     /// Leases a workspace (waits while `concurrency()` of them are out); `give_back` returns it. RAII: `lease_t`.
     const char* take(workspace_t*& out);
     void give_back(workspace_t* workspace);
@@ -384,6 +400,7 @@ class snapshot_t {
     scalar_kind_t scalar_ = scalar_unknown_k;
     std::uint32_t lanes_ = 1;
     int device_ = 0;
+    bool multi_ = false;
     std::size_t device_bytes_ = 0;
     std::uint64_t count_present_ = 0, upper_lists_ = 0, mutations_ = 0;
 
@@ -497,6 +514,15 @@ struct exact_params_t {
     std::uint64_t* out_keys;
     std::uint64_t* out_counts; ///< [partitions][queries]
 };
+
+/// One launch of the distance kernel behind `usearch_amd_distances` for the index's (metric, scalar) pair (engine.hip): `count` waves,
+/// `slots_per_query` rows each. Also what the merges and the closing distances of clustering.hip run.
+hipError_t launch_distances(metric_kind_t metric, scalar_kind_t scalar, const distances_params_t& p, const snapshot_view_t& view);
+
+/// starts[r] = 1 where upper-level list r is a member's first (compact.hip): lists of one member are consecutive and members own
+/// them in slot order, so the run of lists up to the next start is the member's level. `starts` ([lists], device) is zeroed first.
+const char* mark_list_starts(const std::uint32_t* upper_ref, std::uint64_t members, std::uint64_t lists, std::uint8_t* starts,
+                             hipStream_t stream);
 
 /**
  *  Exact search over the rows of `view` (device pointers everywhere; `view` needs `vectors`, sizes and — when

@@ -131,6 +131,22 @@ class CompactStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class ClusteringConfig(C.Structure):
+    """`usearch_amd_clustering_config_t`."""
+    _fields_ = [("struct_size", C.c_size_t), ("min_clusters", C.c_size_t), ("max_clusters", C.c_size_t)]
+
+
+class ClusteringStats(C.Structure):
+    """`usearch_amd_clustering_stats_t`."""
+    _fields_ = [("clusters", C.c_uint64), ("unique_before_merge", C.c_uint64), ("merge_cycles", C.c_uint64),
+                ("mapping_passes", C.c_uint64), ("visited_members", C.c_uint64), ("computed_distances", C.c_uint64),
+                ("level", C.c_uint32), ("reserved", C.c_uint32), ("seconds_map", C.c_float), ("seconds_merge", C.c_float),
+                ("seconds_trace", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 _library = None
 
 EXPORTED_SYMBOLS = [
@@ -148,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "usearch_amd_exact_search_many", "usearch_amd_exact_search_many_tiled", "usearch_amd_exact_search_dataset",
     "usearch_amd_exact_search_many_device",
     "usearch_amd_cluster_many",
+    "usearch_amd_clustering", "usearch_amd_clustering_members", "usearch_amd_snapshot_live_keys",
     "usearch_amd_filter_from_key_range", "usearch_amd_filter_from_keys", "usearch_amd_filter_from_bits",
     "usearch_amd_filter_allowed", "usearch_amd_filter_device_bits", "usearch_amd_filter_free",
     "usearch_amd_filtered_search_many", "usearch_amd_filtered_search_many_device", "usearch_amd_filtered_exact_search_many",
@@ -241,6 +258,14 @@ def library() -> C.CDLL:
     L.usearch_amd_merge_many.argtypes = [C.c_void_p] * 3 + [C.c_size_t] * 3 + [C.c_void_p] * 3 + [err_p]
     L.usearch_amd_cluster_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, err_p]
+    L.usearch_amd_clustering.restype = None
+    L.usearch_amd_clustering.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(ClusteringConfig),
+                                         C.c_void_p, C.c_void_p, C.POINTER(ClusteringStats), err_p]
+    L.usearch_amd_clustering_members.restype = None
+    L.usearch_amd_clustering_members.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ClusteringConfig), C.c_void_p,
+                                                 C.c_void_p, C.POINTER(ClusteringStats), err_p]
+    L.usearch_amd_snapshot_live_keys.restype = C.c_size_t
+    L.usearch_amd_snapshot_live_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, err_p]
     L.usearch_amd_exact_search_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), err_p]
     L.usearch_amd_exact_search_many_tiled.argtypes = L.usearch_amd_exact_search_many.argtypes
@@ -367,6 +392,38 @@ class BatchMatches:
 
     def mean_recall(self, expected: np.ndarray, count: Optional[int] = None) -> float:
         return self.count_matches(expected, count=count) / len(expected)
+
+
+class Clustering:
+    """What `Index.clustering` returns — `usearch.index.Clustering` (index.py:399-450) without its plotting helpers: `matches`
+    holds one (centroid key, distance) per query, `queries` the vectors or member keys that were clustered."""
+
+    def __init__(self, index: "Index", matches: BatchMatches, queries: np.ndarray, stats: dict, by_keys: bool):
+        self.index = index
+        self.matches = matches
+        self.queries = queries
+        self.stats = stats
+        self._by_keys = by_keys
+
+    def __repr__(self) -> str:
+        return f"usearch_amd.Clustering(for {len(self.queries)} queries, {self.stats.get('clusters', 0)} clusters)"
+
+    @property
+    def centroids_popularity(self):
+        """(centroid keys, how many queries each received), the keys ascending."""
+        return np.unique(self.matches.keys[:, 0], return_counts=True)
+
+    def members_of(self, centroid: int, queries_only: bool = False) -> np.ndarray:
+        """The queries that ended in `centroid`: their vectors or member keys, or with `queries_only` their positions."""
+        positions = np.flatnonzero(self.matches.keys[:, 0] == np.uint64(centroid))
+        return positions if queries_only else self.queries[positions]
+
+    def subcluster(self, centroid: int, **clustering_kwargs) -> "Clustering":
+        """Clusters the queries of one centroid again (`min_count`, `max_count` as for `Index.clustering`)."""
+        sub_queries = self.members_of(centroid)
+        if self._by_keys:
+            return self.index.clustering(keys=sub_queries, **clustering_kwargs)
+        return self.index.clustering(vectors=sub_queries, **clustering_kwargs)
 
 
 class Filter:
@@ -787,6 +844,49 @@ class Index:
         _raise(err, "usearch_amd_cluster_many")
         return keys, distances, visited, computed
 
+    def clustering(self, *, vectors: Optional[np.ndarray] = None, keys: Optional[np.ndarray] = None, min_count: Optional[int] = None,
+                   max_count: Optional[int] = None, dtype: Optional[str] = None) -> Clustering:
+        """`Index.cluster(vectors=… | keys=…, min_count=…, max_count=…)` of the reference (index.py:1202-1261 →
+        index_dense.hpp:1819-1981) on the device: every query descends to the level with more than `min_count` nodes, the least
+        popular centroids merge into their nearest until `max_count` are left. Neither input: every member is clustered. Equal
+        popularities are ordered by centroid key. `min_count` without `max_count` is refused (the reference never returns from
+        it). Named `clustering` because `cluster(vectors, level)` is the single descent."""
+        if vectors is not None and keys is not None:
+            raise ValueError("clustering takes `vectors` or `keys`, not both")
+        config = ClusteringConfig(C.sizeof(ClusteringConfig), int(min_count or 0), int(max_count or 0))
+        stats, err = ClusteringStats(), C.c_char_p()
+        if vectors is not None:
+            vectors = np.asarray(vectors)
+            if vectors.ndim == 1:
+                vectors = vectors[None, :]
+            if dtype is None:
+                dtype = _infer_dtype(vectors)
+            if vectors.strides[1] != vectors.itemsize:
+                vectors = np.ascontiguousarray(vectors)
+            q = len(vectors)
+            queries = vectors
+            out_keys, out_distances = np.zeros(q, dtype=np.uint64), np.zeros(q, dtype=np.float32)
+            library().usearch_amd_clustering(self._handle, _pointer(vectors), SCALAR_KINDS[dtype], q,
+                                             vectors.shape[1] * vectors.itemsize if q <= 1 else vectors.strides[0], C.byref(config),
+                                             _pointer(out_keys), _pointer(out_distances), C.byref(stats), C.byref(err))
+        else:
+            if keys is None:  # every member that was not removed, in slot order
+                queries = np.zeros(len(self), dtype=np.uint64)  # one read-back: room for every slot, cut to the live ones
+                live = library().usearch_amd_snapshot_live_keys(self._handle, _pointer(queries), len(queries), C.byref(err))
+                _raise(err, "usearch_amd_snapshot_live_keys")
+                queries = queries[:live].copy()
+                given = None
+            else:
+                queries = given = np.ascontiguousarray(np.atleast_1d(keys), dtype=np.uint64)
+            q = len(queries)
+            out_keys, out_distances = np.zeros(q, dtype=np.uint64), np.zeros(q, dtype=np.float32)
+            library().usearch_amd_clustering_members(self._handle, _pointer(given), q, C.byref(config), _pointer(out_keys),
+                                                     _pointer(out_distances), C.byref(stats), C.byref(err))
+        _raise(err, "usearch_amd_clustering")
+        matches = BatchMatches(out_keys[:, None], out_distances[:, None], np.ones(q, dtype=np.uint64),
+                               int(stats.visited_members), int(stats.computed_distances))
+        return Clustering(self, matches, queries, stats.as_dict(), vectors is None)
+
     # ---- semantic join
     def join(self, other: "Index", max_proposals: int = 0, exact: bool = False, *, expansion: Optional[int] = None,
              threads: int = 0) -> Dict[int, int]:
@@ -927,6 +1027,10 @@ class BuiltIndex:
     def compact(self, staging_bytes: int = 0, slot_map: bool = False):
         """`Index.compact` on the built index: `save_buffer`, `extend` and `update` go on working over the survivors."""
         return self.index.compact(staging_bytes, slot_map)
+
+    def clustering(self, **kwargs) -> Clustering:
+        """`Index.clustering` on the built index."""
+        return self.index.clustering(**kwargs)
 
     def save_buffer(self) -> np.ndarray:
         image = np.empty(self.serialized_length, dtype=np.uint8)
