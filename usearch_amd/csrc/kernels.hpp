@@ -1296,8 +1296,20 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
             phase_mark = now;
         }
     };
+    // the sketch's share of phase 3: records and bounds (the mark stays, phase 3 still sums to the whole), the hops that took the
+    // sketch path and those of them with more survivors than one round of one row per lane group holds
+    std::uint64_t diagnostic_bound_ticks = 0;
+    std::uint32_t diagnostic_sketch_hops = 0, diagnostic_wide_hops = 0;
+    auto tick_bounds = [&](std::uint32_t kept) {
+        if (args.phases) {
+            diagnostic_bound_ticks += __builtin_amdgcn_s_memtime() - phase_mark;
+            ++diagnostic_sketch_hops;
+            diagnostic_wide_hops += kept > 64u / lanes_ak ? 1u : 0u;
+        }
+    };
 #else
     auto tick = [](int) {};
+    auto tick_bounds = [](std::uint32_t) {};
 #endif
     const std::uint64_t query_row = !plain_ak && args.query_ids ? args.query_ids[q] : q;
     const query_norm_t a2 = stage_query<metric_ak, scalar_ak, lanes_ak>(
@@ -1412,77 +1424,43 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                                                                             count);
         computed += count;
     };
-    auto measure_hop = [&](std::uint32_t count, float radius_now) { // the beam: up to M0 fresh neighbours per hop
-        if constexpr (sketch_ak) {
-            // Once `top` is full a newcomer at d ≥ radius changes nothing — not `top`, not the frontier, not the radius — and its exact
-            // distance is never read: a PROOF of d ≥ radius does as well. The record of a candidate (one 128-byte line, eight lanes of
-            // 16 bytes) gives a lower bound of the distance this kernel would compute (sketch.hpp); a candidate whose bound reaches the
-            // radius of the hop's start (commits inside the hop only shrink it) keeps the bound as its distance — the commit test
-            // rejects it exactly as it would reject the true one — and only the others' rows are fetched. Same commits, same counters.
-            if (sketch_on && top.size == ef) {
-                const std::uint32_t sub = lane & 7u, group = lane >> 3;
-                const float* coefficients = reinterpret_cast<const float*>(query_lds + args.sketch_offset) + sub * 8;
-                const float4 q0 = *reinterpret_cast<const float4*>(coefficients), q1 = *reinterpret_cast<const float4*>(coefficients + 4);
-                const std::uint32_t my_slot = lane < count ? mem::load(cand_slots + lane) : 0u;
-                for (std::uint32_t base = 0; base < count; base += 32) {
-                    uint4 record[4]; // every record of the round is requested before the first one is used: one round trip
+    // the sketch's bound for the candidate whose record the eight lanes of a group hold, 16 bytes each (every lane of the group gets it)
+    auto record_bound = [&](const uint4 v, const float4 q0, const float4 q1, std::uint32_t sub) -> float {
+        const std::uint32_t last = sub == 7u ? 0u : v.w; // the last lane's last word is ρ, not two coefficients
+        float dot = 0.f;
+        dot = __builtin_fmaf(half_bits_to_float(v.x & 0xFFFFu), q0.x, dot);
+        dot = __builtin_fmaf(half_bits_to_float(v.x >> 16), q0.y, dot);
+        dot = __builtin_fmaf(half_bits_to_float(v.y & 0xFFFFu), q0.z, dot);
+        dot = __builtin_fmaf(half_bits_to_float(v.y >> 16), q0.w, dot);
+        dot = __builtin_fmaf(half_bits_to_float(v.z & 0xFFFFu), q1.x, dot);
+        dot = __builtin_fmaf(half_bits_to_float(v.z >> 16), q1.y, dot);
+        dot = __builtin_fmaf(half_bits_to_float(last & 0xFFFFu), q1.z, dot);
+        dot = __builtin_fmaf(half_bits_to_float(last >> 16), q1.w, dot);
+        float residual = sub == 7u ? __builtin_bit_cast(float, v.w) : 0.f;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const std::uint32_t ci = base + (std::uint32_t)r * 8 + group;
-                        record[r] = uint4{0u, 0u, 0u, 0u};
-                        if (ci < count)
-                            record[r] = *reinterpret_cast<const uint4*>(ix.sketch + (std::uint64_t)mem::load(cand_slots + ci) * sketch_record_bytes_k + sub * 16);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const std::uint32_t ci = base + (std::uint32_t)r * 8 + group;
-                        const uint4 v = record[r];
-                        const std::uint32_t last = sub == 7u ? 0u : v.w; // the last lane's last word is ρ, not two coefficients
-                        float dot = 0.f;
-                        dot = __builtin_fmaf(half_bits_to_float(v.x & 0xFFFFu), q0.x, dot);
-                        dot = __builtin_fmaf(half_bits_to_float(v.x >> 16), q0.y, dot);
-                        dot = __builtin_fmaf(half_bits_to_float(v.y & 0xFFFFu), q0.z, dot);
-                        dot = __builtin_fmaf(half_bits_to_float(v.y >> 16), q0.w, dot);
-                        dot = __builtin_fmaf(half_bits_to_float(v.z & 0xFFFFu), q1.x, dot);
-                        dot = __builtin_fmaf(half_bits_to_float(v.z >> 16), q1.y, dot);
-                        dot = __builtin_fmaf(half_bits_to_float(last & 0xFFFFu), q1.z, dot);
-                        dot = __builtin_fmaf(half_bits_to_float(last >> 16), q1.w, dot);
-                        float residual = sub == 7u ? __builtin_bit_cast(float, v.w) : 0.f;
-#pragma unroll
-                        for (int offset = 1; offset < 8; offset <<= 1) {
-                            dot += xor_lane(dot, offset);
-                            residual += xor_lane(residual, offset);
-                        }
-                        if (sub == 0u && ci < count)
-                            mem::store(cand_distances + ci, sketch_lower_bound(dot, residual, sketch_margin));
-                    }
-                }
-                wave_sync<false>();
-                const float bound = lane < count ? mem::load(cand_distances + lane) : 0.f;
-                const std::uint64_t survivors = ballot(lane < count && !(bound >= radius_now)); // a NaN bound proves nothing
-                const std::uint32_t kept = popcount64(survivors);
-                sketch_tested += count, sketch_pruned += count - kept;
-                if (kept < count) {
-                    const bool survivor = lane_bit(survivors);
-                    const std::uint32_t rank = rank_below(survivors, lane);
-                    wave_sync<false>(); // every lane has read its slot and its bound
-                    if (survivor)
-                        mem::store(cand_slots + rank, my_slot); // compacted, list order kept
-                    wave_sync<false>();
-                    if (kept)
-                        measure_rows<metric_ak, scalar_ak, lanes_ak, loads_ak, global_ak, rows_ak>(ix, query_lds, a2, cand_slots, cand_distances, kept);
-                    const float mine = survivor ? mem::load(cand_distances + rank) : bound;
-                    wave_sync<false>();
-                    if (lane < count) { // back to the hop's list positions
-                        mem::store(cand_slots + lane, my_slot);
-                        mem::store(cand_distances + lane, mine);
-                    }
-                    wave_sync<false>();
-                    computed += count;
-                    return;
-                }
+        for (int offset = 1; offset < 8; offset <<= 1) {
+            dot += xor_lane(dot, offset);
+            residual += xor_lane(residual, offset);
+        }
+        return sketch_lower_bound(dot, residual, sketch_margin);
+    };
+    // The rows the sketch could not rule out, `kept` of them compacted in `cand_slots`: about 3.4 of a hop's 22.8 fresh neighbours at the
+    // headline shape, so nearly every hop fits ONE round of one row per lane group. The two-row form would give every active group
+    // a second row slot that re-reads its first row and drops the result — each survivor's row loaded and folded twice. A row's
+    // summation chain does not depend on the form, so the distances keep their bits. The f16 / bf16 builds only: over 768 × f32 — a
+    // lane's share of a row is two rounds of twelve loads there — the one-row form measured SLOWER than the phantom row (1M × 768 f32
+    // at expansion 288: 15.6 → 16.4 ms per step, profiles/r11_sketch_hop/), so f32 rows keep the two-row form. (By scalar kind, at
+    // compile time: the same rule as a run-time test of the row's length cost the headline build 316 bytes of scratch.)
+    auto measure_survivors = [&](std::uint32_t kept) {
+        if constexpr (rows_ak > 1 && narrow_float<scalar_ak>()) {
+            if (kept <= 64u / lanes_ak) {
+                measure_rows<metric_ak, scalar_ak, lanes_ak, loads_ak, global_ak, 1>(ix, query_lds, a2, cand_slots, cand_distances, kept);
+                return;
             }
         }
+        measure_rows<metric_ak, scalar_ak, lanes_ak, loads_ak, global_ak, rows_ak>(ix, query_lds, a2, cand_slots, cand_distances, kept);
+    };
+    auto measure_hop = [&](std::uint32_t count) { // the beam: up to M0 fresh neighbours per hop
         if constexpr (team_ak > 1) {
             // the leader of a team: publish the gather list, take the first share, meet the helpers again when all of it is measured
             if (lane == 0)
@@ -1868,6 +1846,8 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
             bool early_done = false;
             std::uint64_t asked_mask = 0;    // early rows: the lanes whose rows were gathered next to the probe, …
             bool measured_early = false;     // … their distances waiting in `cand_distances` in that order
+            bool records_early = false;      // the sketch: the records of the list's neighbours were requested next to the probe, …
+            uint4 early_record[4];           // … lane group g holds, for round r, its 16 bytes of the record of list cell 8r + g
             if constexpr (mode_ak == scratch_global_k) {
                 fresh = visits_set<mode_ak>(visits, visits_mask, neighbor, present);
             } else {
@@ -1977,6 +1957,32 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                         old = atomicCAS(visits + h, none_slot_k, neighbor);
                     }
                 }
+                // ---- the sketch's records beside the probe. Which records a hop needs depends on the LIST alone, not on the probe's
+                //      answer: with `top` full and a list of at most 32 cells (four rounds of eight lane groups cover it) the record of
+                //      every present neighbour is requested now, by list position — the slot comes from the lane that holds it — and is
+                //      consumed once the probe has answered: the records' round trip runs next to the probe's instead of behind it. The
+                //      request goes out right BEHIND the probe's first compare-and-swap: loads return in issue order, so the wait for
+                //      the probe's answer does not wait for the records as well. A visited neighbour's record is fetched and thrown
+                //      away (about 9 of 32 per hop at the headline shape, 128 bytes each) and counts nowhere.
+                if constexpr (sketch_ak) {
+                    if (sketch_on && top.size == ef && tile == 0 && cells <= 32) {
+                        records_early = true;
+                        // an absent cell reads the record of slot 0 (one line every wave shares; nobody is fresh there, nothing reads
+                        // it): the loads need no predicate, so their number is known where the probe's answer is waited for
+                        const std::uint32_t present_slot = present ? neighbor : 0u;
+                        // (the lane number through an opaque move: what is derived from it here — exchange addresses, the lane's place in a
+                        // record — is computed on the spot, a few instructions, and not held in registers for the whole walk: the headline
+                        // build has none to spare)
+                        std::uint32_t lane_now = lane;
+                        asm volatile("" : "+v"(lane_now));
+                        const int from = (int)((lane_now >> 3) << 2); // byte address of lane `group` in the lane exchange
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const std::uint32_t slot = (std::uint32_t)__builtin_amdgcn_ds_bpermute(from + r * 32, (int)present_slot);
+                            early_record[r] = *reinterpret_cast<const uint4*>(ix.sketch + ((std::uint64_t)slot * sketch_record_bytes_k + (lane_now & 7u) * 16));
+                        }
+                    }
+                }
                 if (!popped)
                     pop_now();
                 shadow_work();
@@ -2048,11 +2054,87 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 candidate = fresh;
                 computed += count;
                 wave_sync<false>();
+            } else if (sketch_ak && sketch_on && top.size == ef) { // (constant false, and compiled away, in a build without the sketch)
+                // ---- the sketch. Once `top` is full a newcomer at d ≥ radius changes nothing — not `top`, not the frontier, not the radius —
+                //      and its exact distance is never read: a PROOF of d ≥ radius does as well. The record of a candidate (one 128-byte
+                //      line, eight lanes of 16 bytes) gives a lower bound of the distance this kernel would compute (sketch.hpp); a
+                //      candidate whose bound reaches the radius of the hop's start (commits inside the hop only shrink it) keeps the bound
+                //      as its distance — the commit test rejects it exactly as it would reject the true one — and only the others' rows
+                //      are fetched. Same commits, same counters. The candidates sit in list order either way: at their list positions
+                //      when the records came next to the probe (`records_early`), else compacted to the lanes below `count`, their
+                //      records fetched now, behind the probe. One ballot names the survivors, one compaction hands them to the gather.
+                //      Both routes share this block ON PURPOSE: with a gather of its own for each (the old route left in `measure_hop`)
+                //      the headline build holds two more copies of `measure_rows` and spills 332 bytes per lane; shared, it fits in 256
+                //      registers without scratch. A hop without the sketch — `top` not full yet, sketch off — takes `measure_hop` below.
+                const std::uint32_t sub = lane & 7u, group = lane >> 3;
+                bool member;
+                float bound;
+                if (records_early) {
+                    const float* coefficients = reinterpret_cast<const float*>(query_lds + args.sketch_offset) + sub * 8;
+                    const float4 q0 = *reinterpret_cast<const float4*>(coefficients), q1 = *reinterpret_cast<const float4*>(coefficients + 4);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (!((fresh_mask >> (r * 8)) & 0xFFu))
+                            continue; // (wave-uniform) nobody of this round is fresh: its records are dropped unread
+                        const float lower = record_bound(early_record[r], q0, q1, sub);
+                        if (sub == 0u)
+                            cand_distances[(std::uint32_t)r * 8 + group] = lower;
+                    }
+                    wave_sync<false>();
+                    member = fresh;
+                    mine_slot = neighbor;
+                    bound = fresh ? cand_distances[lane] : 0.f; // (fresh lanes sit below 32: the list has no more cells)
+                } else {
+                    if (fresh)
+                        cand_slots[rank_below(fresh_mask, lane)] = neighbor; // keeps list order
+                    wave_sync<false>();
+                    member = lane < count;
+                    mine_slot = member ? cand_slots[lane] : 0u;
+                    const float* coefficients = reinterpret_cast<const float*>(query_lds + args.sketch_offset) + sub * 8;
+                    const float4 q0 = *reinterpret_cast<const float4*>(coefficients), q1 = *reinterpret_cast<const float4*>(coefficients + 4);
+                    for (std::uint32_t base = 0; base < count; base += 32) {
+                        uint4 record[4]; // every record of the round is requested before the first one is used: one round trip
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const std::uint32_t ci = base + (std::uint32_t)r * 8 + group;
+                            record[r] = uint4{0u, 0u, 0u, 0u};
+                            if (ci < count)
+                                record[r] = *reinterpret_cast<const uint4*>(ix.sketch + (std::uint64_t)cand_slots[ci] * sketch_record_bytes_k + sub * 16);
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (base + (std::uint32_t)r * 8 >= count)
+                                break; // (wave-uniform) the eight candidates of this round and of the later ones lie beyond `count`
+                            const std::uint32_t ci = base + (std::uint32_t)r * 8 + group;
+                            const float lower = record_bound(record[r], q0, q1, sub);
+                            if (sub == 0u && ci < count)
+                                cand_distances[ci] = lower;
+                        }
+                    }
+                    wave_sync<false>();
+                    bound = member ? cand_distances[lane] : 0.f;
+                }
+                const std::uint64_t survivors = ballot(member && !(bound >= radius)); // a NaN bound proves nothing
+                const std::uint32_t kept = popcount64(survivors);
+                sketch_tested += count, sketch_pruned += count - kept;
+                tick_bounds(kept);
+                const bool survivor = lane_bit(survivors);
+                wave_sync<false>(); // every lane has read its slot and its bound
+                if (survivor)
+                    cand_slots[rank_below(survivors, lane)] = mine_slot; // compacted, list order kept
+                wave_sync<false>();
+                if (kept)
+                    measure_survivors(kept);
+                // (the rank is counted again from the mask: two instructions against a register held across the gather)
+                mine = survivor ? cand_distances[rank_below(survivors, lane)] : bound; // a pruned candidate carries its bound
+                candidate = member;
+                computed += count;
+                wave_sync<false>();
             } else {
                 if (fresh)
                     mem::store(cand_slots + rank_below(fresh_mask, lane), neighbor); // keeps list order
                 wave_sync<global_ak>();
-                measure_hop(count, radius);
+                measure_hop(count);
                 mine = lane < count ? mem::load(cand_distances + lane) : 0.f;
                 mine_slot = lane < count ? mem::load(cand_slots + lane) : 0u;
                 candidate = lane < count;
@@ -2122,6 +2204,11 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
         atomicAdd(args.phases + 8, (unsigned long long)diagnostic_push_ticks);
         atomicAdd(args.phases + 9, (unsigned long long)diagnostic_insert_ticks);
         atomicAdd(args.phases + 10, (unsigned long long)diagnostic_rechecks);
+        if constexpr (team_ak == 1) { // [11 … 15] belong to a team's helpers
+            atomicAdd(args.phases + 11, (unsigned long long)diagnostic_bound_ticks);
+            atomicAdd(args.phases + 12, (unsigned long long)diagnostic_sketch_hops);
+            atomicAdd(args.phases + 13, (unsigned long long)diagnostic_wide_hops);
+        }
     }
 #endif
     if constexpr (sketch_ak) {
