@@ -65,3 +65,39 @@ def test_containers_match_reference_rules(seed, levels, count, limit):
     (pk, ps), (tk, ts) = ua.test_containers(kinds, keys, slots, limit)
     assert [(float(a), int(b)) for a, b in zip(pk, ps)] == popped
     assert [(float(a), int(b)) for a, b in zip(tk, ts)] == top
+
+
+def micro_benchmarks(waves=3, fill=32, count=64, limit=16):
+    """What the two diagnostic hooks of csrc/test_hooks.hip report that does not depend on the clock: per wave, the checksum of what
+    the heap popped (serial and subtree pop) and how many candidates `top` accepted (4, 8 and 16 entries per lane)."""
+    import ctypes as C
+
+    from usearch_amd import index as ua
+    hooks = ua.test_hooks()
+    hooks.usearch_amd_bench_heap.argtypes = [C.c_uint32] * 4 + [C.c_void_p] * 3 + [C.POINTER(C.c_char_p)]
+    hooks.usearch_amd_bench_top.argtypes = [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p)]
+    checksums, ticks, accepted = {}, {}, {}
+    for serial in (1, 0):
+        pops, pushes, checksums[serial] = (np.zeros(waves, dtype=np.uint64) for _ in range(3))
+        err = C.c_char_p()
+        hooks.usearch_amd_bench_heap(serial, fill, count, waves, pops.ctypes.data, pushes.ctypes.data, checksums[serial].ctypes.data,
+                                     C.byref(err))
+        assert not err.value, err.value
+        ticks["serial pop" if serial else "subtree pop"] = pops
+    for entries_per_lane in (4, 8, 16):
+        ticks[entries_per_lane], accepted[entries_per_lane] = np.zeros(waves, dtype=np.uint64), np.zeros(waves, dtype=np.uint64)
+        err = C.c_char_p()
+        hooks.usearch_amd_bench_top(entries_per_lane, count, limit, waves, ticks[entries_per_lane].ctypes.data,
+                                    accepted[entries_per_lane].ctypes.data, C.byref(err))
+        assert not err.value, err.value
+    return checksums, ticks, accepted
+
+
+def test_micro_benchmark_hooks_report_every_wave():
+    waves, count, limit = 3, 64, 16
+    checksums, ticks, accepted = micro_benchmarks(waves, 32, count, limit)
+    assert np.array_equal(checksums[0], checksums[1]) and checksums[0].all(), "the two pops disagree on what they popped"
+    assert len(set(checksums[0].tolist())) == waves  # every wave draws its own keys
+    assert all(t.all() for t in ticks.values())  # every wave wrote its clock
+    for entries_per_lane in (4, 8, 16):  # the first `limit` candidates are always taken
+        assert ((accepted[entries_per_lane] >= limit) & (accepted[entries_per_lane] <= count)).all()

@@ -48,23 +48,6 @@ __global__ void build_refile_kernel(const build_args_t b, const std::uint32_t* f
             atomicAdd(b.counters + 3, 1ull);
 }
 
-/// Frees a set of device allocations when the build function returns, whatever the path.
-struct device_block_t {
-    std::vector<void*> pointers;
-    ~device_block_t() {
-        for (void* p : pointers)
-            placed_free(p); // time-stamps the release of large blocks (placement.hpp: settle, then allocate)
-    }
-    template <typename pointer_at> hipError_t allocate(pointer_at** out, std::size_t bytes) {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<std::size_t>(bytes, 16));
-        if (e == hipSuccess)
-            pointers.push_back(p);
-        *out = static_cast<pointer_at*>(p);
-        return e;
-    }
-};
-
 } // namespace
 
 const char* snapshot_t::allocate_for_build(metric_kind_t metric, scalar_kind_t scalar, std::size_t dimensions,

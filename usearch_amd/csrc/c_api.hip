@@ -20,8 +20,10 @@
 #include "casts.hpp"
 #include "clustering.hpp"
 #include "compact.hpp"
+#include "device_scratch.hpp"
 #include "engine.hpp"
 #include "filter.hpp"
+#include "host_util.hpp"
 #include "join.hpp"
 #include "kernels.hpp"
 #include "kmeans.hpp"
@@ -583,45 +585,38 @@ void usearch_amd_merge_many_device(usearch_amd_distance_t const* distances, usea
     fail_from_exception(error);
 }
 
+static const char* merge_many_host(float const* distances, uint64_t const* keys, uint64_t const* counts, size_t shards,
+                                   size_t queries_count, size_t wanted, float* out_distances, uint64_t* out_keys, uint64_t* out_counts) {
+    const size_t cells = shards * queries_count * wanted, rows = shards * queries_count;
+    if (!cells)
+        return nullptr;
+    float *d_distances = nullptr, *d_out_distances = nullptr;
+    uint64_t *d_keys = nullptr, *d_counts = nullptr, *d_out_keys = nullptr, *d_out_counts = nullptr;
+    device_scratch_t scratch(current_device_k); // no snapshot to ask: the calling thread's device
+    UA_HIP(scratch.allocate(&d_distances, cells * 4));
+    UA_HIP(scratch.allocate(&d_keys, cells * 8));
+    UA_HIP(scratch.allocate(&d_counts, rows * 8));
+    UA_HIP(scratch.allocate(&d_out_distances, queries_count * wanted * 4));
+    UA_HIP(scratch.allocate(&d_out_keys, queries_count * wanted * 8));
+    UA_HIP(scratch.allocate(&d_out_counts, queries_count * 8));
+    UA_HIP(hipMemcpy(d_distances, distances, cells * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_keys, keys, cells * 8, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_counts, counts, rows * 8, hipMemcpyHostToDevice));
+    if (const char* message = merge_shards_device(d_distances, d_keys, d_counts, shards, queries_count, wanted, d_out_distances,
+                                                  d_out_keys, d_out_counts, nullptr))
+        return message;
+    UA_HIP(hipMemcpy(out_distances, d_out_distances, queries_count * wanted * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(out_keys, d_out_keys, queries_count * wanted * 8, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(out_counts, d_out_counts, queries_count * 8, hipMemcpyDeviceToHost));
+    return nullptr;
+}
+
 void usearch_amd_merge_many(usearch_amd_distance_t const* distances, usearch_amd_key_t const* keys,
                             uint64_t const* counts, size_t shards, size_t queries_count, size_t wanted,
                             usearch_amd_distance_t* out_distances, usearch_amd_key_t* out_keys, uint64_t* out_counts,
                             usearch_amd_error_t* error) try {
-    const size_t cells = shards * queries_count * wanted, rows = shards * queries_count;
-    if (!cells)
-        return;
-    float *d_distances = nullptr, *d_out_distances = nullptr;
-    uint64_t *d_keys = nullptr, *d_counts = nullptr, *d_out_keys = nullptr, *d_out_counts = nullptr;
-    hipError_t e = hipSuccess;
-    auto check = [&](hipError_t r) {
-        if (e == hipSuccess)
-            e = r;
-    };
-    check(hipMalloc((void**)&d_distances, cells * 4));
-    check(hipMalloc((void**)&d_keys, cells * 8));
-    check(hipMalloc((void**)&d_counts, rows * 8));
-    check(hipMalloc((void**)&d_out_distances, queries_count * wanted * 4));
-    check(hipMalloc((void**)&d_out_keys, queries_count * wanted * 8));
-    check(hipMalloc((void**)&d_out_counts, queries_count * 8));
-    if (e == hipSuccess) {
-        check(hipMemcpy(d_distances, distances, cells * 4, hipMemcpyHostToDevice));
-        check(hipMemcpy(d_keys, keys, cells * 8, hipMemcpyHostToDevice));
-        check(hipMemcpy(d_counts, counts, rows * 8, hipMemcpyHostToDevice));
-    }
-    if (e == hipSuccess) {
-        if (const char* message = merge_shards_device(d_distances, d_keys, d_counts, shards, queries_count, wanted,
-                                                      d_out_distances, d_out_keys, d_out_counts, nullptr))
-            fail(error, message);
-        check(hipMemcpy(out_distances, d_out_distances, queries_count * wanted * 4, hipMemcpyDeviceToHost));
-        check(hipMemcpy(out_keys, d_out_keys, queries_count * wanted * 8, hipMemcpyDeviceToHost));
-        check(hipMemcpy(out_counts, d_out_counts, queries_count * 8, hipMemcpyDeviceToHost));
-    }
-    for (void* p : {(void*)d_distances, (void*)d_keys, (void*)d_counts, (void*)d_out_distances, (void*)d_out_keys,
-                    (void*)d_out_counts})
-        if (p)
-            (void)hipFree(p);
-    if (e != hipSuccess)
-        fail(error, hipGetErrorString(e));
+    if (const char* e = merge_many_host(distances, keys, counts, shards, queries_count, wanted, out_distances, out_keys, out_counts))
+        fail(error, e);
 } catch (...) {
     fail_from_exception(error);
 }

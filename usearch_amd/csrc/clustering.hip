@@ -26,6 +26,7 @@
 #include <mutex>
 
 #include "casts.hpp"
+#include "device_scratch.hpp"
 #include "engine.hpp"
 #include "host_util.hpp"
 #include "search_plan.hpp"
@@ -255,28 +256,8 @@ __global__ void clustering_trace_kernel(const u64* slots, const u32* slot_to_ent
     out_keys[q] = entry_key[entry];
 }
 
-struct scratch_t {
-    std::vector<void*> pointers;
-    ~scratch_t() {
-        for (void* p : pointers)
-            (void)hipFree(p);
-    }
-    template <typename pointer_at> hipError_t allocate(pointer_at** out, std::size_t bytes) {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<std::size_t>(bytes, 16));
-        if (e == hipSuccess)
-            pointers.push_back(p);
-        *out = static_cast<pointer_at*>(p);
-        return e;
-    }
-};
-
 float seconds_since(std::chrono::steady_clock::time_point start) {
     return std::chrono::duration<float>(std::chrono::steady_clock::now() - start).count();
-}
-
-unsigned blocks_for(u64 threads, int compute_units) {
-    return (unsigned)std::max<u64>(1, std::min<u64>((threads + 255) / 256, (u64)compute_units * 32));
 }
 
 } // namespace
@@ -300,7 +281,7 @@ const char* snapshot_t::clustering(const void* queries, scalar_kind_t query_kind
     const u64 n = view_.size;
     const u32 top_level = n ? view_.max_level : 0;
     UA_HIP(hipSetDevice(device_));
-    scratch_t scratch;
+    device_scratch_t scratch(device_);
 
     // ---- the level (rule 1)
     std::vector<u64> at_or_above(top_level + 2, 0);

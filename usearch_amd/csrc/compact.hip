@@ -16,6 +16,7 @@
 #include <mutex>
 
 #include "build.hpp"
+#include "device_scratch.hpp"
 #include "engine.hpp"
 #include "host_util.hpp"
 
@@ -265,29 +266,8 @@ __global__ void compact_gather_rows_kernel(const uint4* rows, const u32* old_of,
     }
 }
 
-/// Device allocations that live for one call.
-struct scratch_t {
-    std::vector<void*> pointers;
-    ~scratch_t() {
-        for (void* p : pointers)
-            placed_free(p);
-    }
-    template <typename pointer_at> hipError_t allocate(pointer_at** out, std::size_t bytes) {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<std::size_t>(bytes, 16));
-        if (e == hipSuccess)
-            pointers.push_back(p);
-        *out = static_cast<pointer_at*>(p);
-        return e;
-    }
-};
-
 float milliseconds_since(std::chrono::steady_clock::time_point start) {
     return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - start).count();
-}
-
-unsigned blocks_for(u64 threads, int compute_units) {
-    return (unsigned)std::max<u64>(1, std::min<u64>((threads + 255) / 256, (u64)compute_units * 32));
 }
 
 const char* launch_lists(const u32* source, u32* destination, u32 width, u64 lists, const u32* targets, const u32* slot_map, u64 members,
@@ -326,7 +306,7 @@ const char* snapshot_t::isolate(compact_stats_t* stats_out) {
     stats.new_entry_slot = view_.entry_slot, stats.new_max_level = view_.max_level;
     if (n) {
         UA_HIP(hipSetDevice(device_));
-        scratch_t scratch;
+        device_scratch_t scratch(device_, release_t::placed_free);
         u32* d_map = nullptr;
         compact_totals_t* d_totals = nullptr;
         UA_HIP(scratch.allocate(&d_map, n * 4));
@@ -386,7 +366,7 @@ const char* snapshot_t::compact(const compact_config_t& config, std::uint32_t* s
 
     // ---- scan: who stays, where everybody goes
     auto started = std::chrono::steady_clock::now();
-    scratch_t scratch;
+    device_scratch_t scratch(device_, release_t::placed_free);
     std::uint8_t* d_starts = nullptr;
     std::uint16_t* d_levels = nullptr;
     u32 *d_chunk_live = nullptr, *d_chunk_lists = nullptr, *d_map = nullptr, *d_old_of = nullptr, *d_list_target = nullptr;
@@ -541,7 +521,7 @@ const char* builder_t::remove(const std::uint32_t* slots, std::uint64_t count) {
         keys_[slots[i]] = free_key_k;
     if (count > 1) { // the rest in one upload and one launch
         UA_HIP(hipSetDevice(snapshot_.device()));
-        scratch_t scratch;
+        device_scratch_t scratch(snapshot_.device(), release_t::placed_free);
         u32* d_slots = nullptr;
         UA_HIP(scratch.allocate(&d_slots, (count - 1) * 4));
         UA_HIP(hipMemcpyAsync(d_slots, slots + 1, (count - 1) * 4, hipMemcpyHostToDevice, snapshot_.stream()));

@@ -31,6 +31,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <shared_mutex>
 #include <unordered_map>
 #include <vector>
@@ -40,6 +41,7 @@
 #include "clustering.hpp"
 #include "combiner.hpp"
 #include "compact.hpp"
+#include "device_scratch.hpp"
 #include "engine.hpp"
 #include "filter.hpp"
 #include "host_util.hpp"
@@ -480,18 +482,16 @@ struct lazy_predicate_t {
     std::vector<std::uint64_t> ask_keys;
     std::size_t words = 0;
     std::size_t callbacks = 0;
+    std::optional<device_scratch_t> scratch; ///< owns the five device arrays; made by `open`, for the index's device
 
-    ~lazy_predicate_t() {
-        for (void* p : {(void*)d_allow, (void*)d_known, (void*)d_ask_slots, (void*)d_cursor, (void*)d_ask_keys})
-            if (p)
-                (void)hipFree(p);
-    }
-    const char* open(std::size_t members) {
+    /// `device`: where the index lives. The walk dereferences these arrays, so they go there, whatever device the caller has current.
+    const char* open(std::size_t members, int device) {
         words = (members + 31) / 32 + 1;
         allow.assign(words, 0u), known.assign(words, 0u);
-        if (hipMalloc((void**)&d_allow, words * 4) != hipSuccess || hipMalloc((void**)&d_known, words * 4) != hipSuccess ||
-            hipMalloc((void**)&d_ask_slots, ask_cap_k * 4) != hipSuccess || hipMalloc((void**)&d_ask_keys, ask_cap_k * 8) != hipSuccess ||
-            hipMalloc((void**)&d_cursor, 4) != hipSuccess || hipMemset(d_allow, 0, words * 4) != hipSuccess ||
+        scratch.emplace(device);
+        if (scratch->allocate(&d_allow, words * 4) != hipSuccess || scratch->allocate(&d_known, words * 4) != hipSuccess ||
+            scratch->allocate(&d_ask_slots, ask_cap_k * 4) != hipSuccess || scratch->allocate(&d_ask_keys, ask_cap_k * 8) != hipSuccess ||
+            scratch->allocate(&d_cursor, 4) != hipSuccess || hipMemset(d_allow, 0, words * 4) != hipSuccess ||
             hipMemset(d_known, 0, words * 4) != hipSuccess)
             return (void)hipGetLastError(), "Out of device memory for the predicate's bitmaps";
         return nullptr;
@@ -1070,7 +1070,7 @@ static size_t search_shared(index_t& index, void const* queries, scalar_kind_t k
                             // the callback only for the members the walk wants to admit (`lazy_predicate_t`): provisional runs until
                             // one asks nothing; that one is the answer
                             lazy_predicate_t lazy;
-                            if (const char* e = lazy.open(index.size()))
+                            if (const char* e = lazy.open(index.size(), device_index->device()))
                                 return fail(error, e);
                             bool settled = false;
                             for (int round = 0; round < lazy_predicate_t::rounds_limit_k && !settled; ++round) {

@@ -15,6 +15,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "casts.hpp"
+#include "device_scratch.hpp"
 #include "host_util.hpp"
 #include "kernels.hpp"
 #include "search_plan.hpp"
@@ -538,20 +539,7 @@ const char* snapshot_t::build(const image_t& image, int device) {
         return "Failed to pull the header from the stream";
 
     // ---- scratch that lives for the load only: levels, tape bytes, the two prefix sums
-    struct scratch_t {
-        std::vector<void*> pointers;
-        ~scratch_t() {
-            for (void* p : pointers)
-                placed_free(p); // time-stamps the release of large blocks (placement.hpp: settle, then allocate)
-        }
-        hipError_t allocate(void** out, std::size_t bytes) {
-            *out = nullptr;
-            const hipError_t e = hipMalloc(out, std::max<std::size_t>(bytes, 16));
-            if (e == hipSuccess)
-                pointers.push_back(*out);
-            return e;
-        }
-    } scratch;
+    device_scratch_t scratch(device, release_t::placed_free);
     std::int16_t* d_levels = nullptr;
     std::uint8_t* d_tapes = nullptr;
     std::uint64_t *d_sizes = nullptr, *d_offsets = nullptr, *d_level_counts = nullptr, *d_first_list = nullptr;
@@ -559,12 +547,12 @@ const char* snapshot_t::build(const image_t& image, int device) {
     void* d_scan = nullptr;
     std::uint64_t tapes_bytes = 0, lists = 0;
     if (n) {
-        UA_HIP(scratch.allocate((void**)&d_levels, n * 2));
-        UA_HIP(scratch.allocate((void**)&d_sizes, n * 8));
-        UA_HIP(scratch.allocate((void**)&d_offsets, n * 8));
-        UA_HIP(scratch.allocate((void**)&d_level_counts, n * 8));
-        UA_HIP(scratch.allocate((void**)&d_first_list, n * 8));
-        UA_HIP(scratch.allocate((void**)&d_flags, 16));
+        UA_HIP(scratch.allocate(&d_levels, n * 2));
+        UA_HIP(scratch.allocate(&d_sizes, n * 8));
+        UA_HIP(scratch.allocate(&d_offsets, n * 8));
+        UA_HIP(scratch.allocate(&d_level_counts, n * 8));
+        UA_HIP(scratch.allocate(&d_first_list, n * 8));
+        UA_HIP(scratch.allocate(&d_flags, 16));
         UA_HIP(hipMemset(d_flags, 0, 16));
         UA_HIP(hipMemcpy(d_levels, image.levels, n * 2, hipMemcpyHostToDevice)); // 2-byte aligned in its own allocation
         const unsigned blocks = (unsigned)((n + 255) / 256);
@@ -610,7 +598,7 @@ const char* snapshot_t::build(const image_t& image, int device) {
     UA_HIP(hipMemset(d_upper_, 0xFF, (std::size_t)std::max<std::uint64_t>(lists, 1) * m * 4));
     bool tombstones = false;
     if (n) {
-        UA_HIP(scratch.allocate((void**)&d_tapes, tapes_bytes));
+        UA_HIP(scratch.allocate(&d_tapes, tapes_bytes));
         UA_HIP(hipMemcpy(d_tapes, image.tapes, tapes_bytes, hipMemcpyHostToDevice));
         const unsigned blocks = (unsigned)((n + 127) / 128);
         if (image.slot_bytes == 5)
@@ -1131,14 +1119,11 @@ const char* snapshot_t::tune(const void* queries, std::size_t count, std::size_t
         return nullptr;
     UA_HIP(hipSetDevice(device_));
     // the sample's results go nowhere: a scratch block for them
-    struct block_t {
-        void* p = nullptr;
-        ~block_t() { (void)hipFree(p); }
-    } results;
+    device_scratch_t results(device_);
     const std::size_t pad = 256, keys_bytes = (count * wanted * 8 + pad - 1) / pad * pad, distances_bytes = (count * wanted * 4 + pad - 1) / pad * pad,
                       column = (count * 8 + pad - 1) / pad * pad;
-    UA_HIP(hipMalloc(&results.p, keys_bytes + distances_bytes + 3 * column));
-    std::uint8_t* base = static_cast<std::uint8_t*>(results.p);
+    std::uint8_t* base = nullptr;
+    UA_HIP(results.allocate(&base, keys_bytes + distances_bytes + 3 * column));
     const std::uint32_t before = placement_.draws;
     {
         std::lock_guard<std::mutex> lock(pool_mutex_);
@@ -1344,55 +1329,39 @@ const char* exact_search_device(metric_kind_t metric, scalar_kind_t scalar, std:
 
     float* partial_distances = nullptr;
     std::uint64_t *partial_keys = nullptr, *partial_counts = nullptr;
-    hipEvent_t begin = nullptr, end = nullptr;
-    const char* error = nullptr;
-    hipError_t e = hipMalloc((void**)&partial_distances, partitions * count * wanted * 4);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&partial_keys, partitions * count * wanted * 8);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&partial_counts, partitions * count * 8);
-    if (e == hipSuccess && kernel_ms) {
-        e = hipEventCreate(&begin);
-        if (e == hipSuccess)
-            e = hipEventCreate(&end);
-        if (e == hipSuccess)
-            e = hipEventRecord(begin, stream);
+    event_pair_t events;
+    device_scratch_t scratch(current_device_k); // the caller has selected the device the view lives on
+    UA_HIP(scratch.allocate(&partial_distances, partitions * count * wanted * 4));
+    UA_HIP(scratch.allocate(&partial_keys, partitions * count * wanted * 8));
+    UA_HIP(scratch.allocate(&partial_counts, partitions * count * 8));
+    if (kernel_ms) {
+        UA_HIP(events.create());
+        UA_HIP(hipEventRecord(events.begin, stream));
     }
-    if (e == hipSuccess) {
-        exact_params_t p{};
-        p.lanes = lanes;
-        p.lds_bytes = view.chunks * (query_chunk_bytes_of(scalar)) + 512 + (std::uint32_t)wanted * 8 + 16;
-        p.stream = stream;
-        p.queries = static_cast<const std::uint8_t*>(queries);
-        p.query_stride = stride_bytes;
-        p.query_count = (std::uint32_t)count;
-        p.wanted = (std::uint32_t)wanted;
-        p.partitions = (std::uint32_t)partitions;
-        p.rows_per_partition = rows_per_partition;
-        p.map_keys = map_keys ? 1u : 0u;
-        p.allow_bits = allow_bits;
-        p.out_distances = partial_distances;
-        p.out_keys = partial_keys;
-        p.out_counts = partial_counts;
-        e = launch_exact(metric, scalar, p, view);
-    }
-    if (e == hipSuccess && kernel_ms)
-        e = hipEventRecord(end, stream);
-    if (e == hipSuccess)
-        error = merge_shards_device(partial_distances, partial_keys, partial_counts, partitions, count, wanted, distances,
-                                    keys, counts, stream, false);
-    if (e == hipSuccess && !error && kernel_ms)
-        e = hipEventElapsedTime(kernel_ms, begin, end);
-    if (e != hipSuccess)
-        error = hip_message(e);
-    for (void* p : {(void*)partial_distances, (void*)partial_keys, (void*)partial_counts})
-        if (p)
-            (void)hipFree(p);
-    if (begin)
-        (void)hipEventDestroy(begin);
-    if (end)
-        (void)hipEventDestroy(end);
-    return error;
+    exact_params_t p{};
+    p.lanes = lanes;
+    p.lds_bytes = view.chunks * (query_chunk_bytes_of(scalar)) + 512 + (std::uint32_t)wanted * 8 + 16;
+    p.stream = stream;
+    p.queries = static_cast<const std::uint8_t*>(queries);
+    p.query_stride = stride_bytes;
+    p.query_count = (std::uint32_t)count;
+    p.wanted = (std::uint32_t)wanted;
+    p.partitions = (std::uint32_t)partitions;
+    p.rows_per_partition = rows_per_partition;
+    p.map_keys = map_keys ? 1u : 0u;
+    p.allow_bits = allow_bits;
+    p.out_distances = partial_distances;
+    p.out_keys = partial_keys;
+    p.out_counts = partial_counts;
+    UA_HIP(launch_exact(metric, scalar, p, view));
+    if (kernel_ms)
+        UA_HIP(hipEventRecord(events.end, stream));
+    if (const char* error = merge_shards_device(partial_distances, partial_keys, partial_counts, partitions, count, wanted, distances,
+                                                keys, counts, stream, false))
+        return error;
+    if (kernel_ms)
+        UA_HIP(hipEventElapsedTime(kernel_ms, events.begin, events.end));
+    return nullptr;
 }
 
 const char* snapshot_t::exact_device(const void* queries, std::size_t count, std::size_t stride_bytes,
@@ -1478,53 +1447,40 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
     std::uint8_t *d_rows = nullptr, *d_queries = nullptr;
     std::uint64_t *d_keys = nullptr, *d_counts = nullptr;
     float* d_distances = nullptr;
+    device_scratch_t scratch(current_device_k); // no snapshot here: the dataset goes to the caller's device
+    UA_HIP(scratch.allocate(&d_rows, dataset_count * row_stride));
+    UA_HIP(scratch.allocate(&d_queries, queries_count * bpv));
+    UA_HIP(scratch.allocate(&d_keys, queries_count * wanted * 8));
+    UA_HIP(scratch.allocate(&d_distances, queries_count * wanted * 4));
+    UA_HIP(scratch.allocate(&d_counts, queries_count * 8));
+    if (const char* error = upload_rows(d_rows, row_stride, static_cast<const std::uint8_t*>(dataset), dataset_stride, bpv, dataset_count))
+        return error;
+    if (const char* error = upload_rows(d_queries, (std::uint32_t)bpv, static_cast<const std::uint8_t*>(queries), queries_stride, bpv,
+                                        queries_count))
+        return error;
+    snapshot_view_t view{};
+    view.vectors = d_rows;
+    view.size = dataset_count;
+    view.row_stride = row_stride;
+    view.chunks = row_chunks;
+    view.bytes_per_vector = (std::uint32_t)bpv;
+    view.dimensions = (std::uint32_t)dimensions;
+    // i8: the matrix-unit kernel returns the very same bits (exact integer sums, same closing arithmetic, same tie order);
+    // the float kinds only reach it when asked (tolerance instead of bit equality)
     const char* error = nullptr;
-    hipError_t e = hipMalloc((void**)&d_rows, std::max<std::size_t>(dataset_count * row_stride, 16));
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&d_queries, queries_count * bpv);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&d_keys, queries_count * wanted * 8);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&d_distances, queries_count * wanted * 4);
-    if (e == hipSuccess)
-        e = hipMalloc((void**)&d_counts, queries_count * 8);
-    if (e == hipSuccess)
-        error = upload_rows(d_rows, row_stride, static_cast<const std::uint8_t*>(dataset), dataset_stride, bpv, dataset_count);
-    if (e == hipSuccess && !error)
-        error = upload_rows(d_queries, (std::uint32_t)bpv, static_cast<const std::uint8_t*>(queries), queries_stride, bpv,
-                            queries_count);
-    std::vector<std::uint64_t> host_keys(queries_count * wanted);
-    std::vector<float> host_distances(queries_count * wanted);
-    if (e == hipSuccess && !error) {
-        snapshot_view_t view{};
-        view.vectors = d_rows;
-        view.size = dataset_count;
-        view.row_stride = row_stride;
-        view.chunks = row_chunks;
-        view.bytes_per_vector = (std::uint32_t)bpv;
-        view.dimensions = (std::uint32_t)dimensions;
-        // i8: the matrix-unit kernel returns the very same bits (exact integer sums, same closing arithmetic, same tie order);
-        // the float kinds only reach it when asked (tolerance instead of bit equality)
-        if (scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
-            !env_size("USEARCH_AMD_NO_TILED_EXACT", 0))
-            error = exact_search_tiled_device(metric, scalar, view, d_queries, queries_count, bpv, wanted, false, d_keys,
-                                              d_distances, d_counts, nullptr, nullptr);
-        else
-            error = exact_search_device(metric, scalar, lanes, view, d_queries, queries_count, bpv, wanted, false, d_keys,
-                                        d_distances, d_counts, nullptr, nullptr);
-    }
-    if (e == hipSuccess && !error) {
-        e = hipMemcpy(host_keys.data(), d_keys, host_keys.size() * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess)
-            e = hipMemcpy(host_distances.data(), d_distances, host_distances.size() * 4, hipMemcpyDeviceToHost);
-    }
-    for (void* p : {(void*)d_rows, (void*)d_queries, (void*)d_keys, (void*)d_distances, (void*)d_counts})
-        if (p)
-            (void)hipFree(p);
-    if (e != hipSuccess)
-        return hip_message(e);
+    if (scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
+        !env_size("USEARCH_AMD_NO_TILED_EXACT", 0))
+        error = exact_search_tiled_device(metric, scalar, view, d_queries, queries_count, bpv, wanted, false, d_keys, d_distances,
+                                          d_counts, nullptr, nullptr);
+    else
+        error = exact_search_device(metric, scalar, lanes, view, d_queries, queries_count, bpv, wanted, false, d_keys, d_distances,
+                                    d_counts, nullptr, nullptr);
     if (error)
         return error;
+    std::vector<std::uint64_t> host_keys(queries_count * wanted);
+    std::vector<float> host_distances(queries_count * wanted);
+    UA_HIP(hipMemcpy(host_keys.data(), d_keys, host_keys.size() * 8, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(host_distances.data(), d_distances, host_distances.size() * 4, hipMemcpyDeviceToHost));
     for (std::size_t q = 0; q < queries_count; ++q) {
         std::memcpy(reinterpret_cast<std::uint8_t*>(keys) + q * keys_stride, host_keys.data() + q * wanted, wanted * 8);
         std::memcpy(reinterpret_cast<std::uint8_t*>(distances) + q * distances_stride, host_distances.data() + q * wanted,
@@ -1547,53 +1503,34 @@ const char* snapshot_t::distances_host(const void* queries, std::size_t count, s
     std::uint8_t* d_queries = nullptr;
     std::uint32_t* d_slots = nullptr;
     float* d_out = nullptr;
-    UA_HIP(hipMalloc((void**)&d_queries, bpv * count));
-    UA_HIP(hipMalloc((void**)&d_slots, count * slots_per_query * 4));
-    UA_HIP(hipMalloc((void**)&d_out, count * slots_per_query * 4));
-    const char* error = nullptr;
-    do {
-        std::vector<std::uint8_t> dense(count * bpv);
-        for (std::size_t q = 0; q < count; ++q)
-            std::memcpy(dense.data() + q * bpv, static_cast<const std::uint8_t*>(queries) + q * stride_bytes, bpv);
-        hipError_t e = hipMemcpy(d_queries, dense.data(), bpv * count, hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(d_slots, slots, count * slots_per_query * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            error = hip_message(e);
-            break;
-        }
-        distances_params_t p{};
-        p.metric = metric_;
-        p.lanes = lanes_;
-        p.lds_bytes = view_.chunks * (query_chunk_bytes_of(scalar_)) + 512;
-        p.stream = stream_;
-        p.queries = d_queries;
-        p.query_stride = bpv;
-        p.slots = d_slots;
-        p.slots_per_query = (std::uint32_t)slots_per_query;
-        p.count = (std::uint32_t)count;
-        p.out = d_out;
-        if (e == hipSuccess)
-            e = hipEventRecord(event_begin_, stream_);
-        if (e == hipSuccess)
-            e = launch_distances(metric_, scalar_, p, view_);
-        if (e == hipSuccess)
-            e = hipEventRecord(event_end_, stream_);
-        if (e == hipSuccess)
-            e = hipEventSynchronize(event_end_);
-        if (e == hipSuccess)
-            e = hipEventElapsedTime(&last_distances_ms_, event_begin_, event_end_);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(stream_);
-        if (e == hipSuccess)
-            e = hipMemcpy(out, d_out, count * slots_per_query * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            error = hip_message(e);
-    } while (false);
-    (void)hipFree(d_queries);
-    (void)hipFree(d_slots);
-    (void)hipFree(d_out);
-    return error;
+    device_scratch_t scratch(device_); // declared after the lease: its blocks go before the workspace is given back
+    UA_HIP(scratch.allocate(&d_queries, bpv * count));
+    UA_HIP(scratch.allocate(&d_slots, count * slots_per_query * 4));
+    UA_HIP(scratch.allocate(&d_out, count * slots_per_query * 4));
+    std::vector<std::uint8_t> dense(count * bpv);
+    for (std::size_t q = 0; q < count; ++q)
+        std::memcpy(dense.data() + q * bpv, static_cast<const std::uint8_t*>(queries) + q * stride_bytes, bpv);
+    UA_HIP(hipMemcpy(d_queries, dense.data(), bpv * count, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_slots, slots, count * slots_per_query * 4, hipMemcpyHostToDevice));
+    distances_params_t p{};
+    p.metric = metric_;
+    p.lanes = lanes_;
+    p.lds_bytes = view_.chunks * (query_chunk_bytes_of(scalar_)) + 512;
+    p.stream = stream_;
+    p.queries = d_queries;
+    p.query_stride = bpv;
+    p.slots = d_slots;
+    p.slots_per_query = (std::uint32_t)slots_per_query;
+    p.count = (std::uint32_t)count;
+    p.out = d_out;
+    UA_HIP(hipEventRecord(event_begin_, stream_));
+    UA_HIP(launch_distances(metric_, scalar_, p, view_));
+    UA_HIP(hipEventRecord(event_end_, stream_));
+    UA_HIP(hipEventSynchronize(event_end_));
+    UA_HIP(hipEventElapsedTime(&last_distances_ms_, event_begin_, event_end_));
+    UA_HIP(hipStreamSynchronize(stream_));
+    UA_HIP(hipMemcpy(out, d_out, count * slots_per_query * 4, hipMemcpyDeviceToHost));
+    return nullptr;
 }
 
 } // namespace usearch_amd

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "device_scratch.hpp"
 #include "engine.hpp"
 #include "host_util.hpp"
 
@@ -1279,47 +1280,28 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
         partitions = (view.size + rows_per_partition - 1) / rows_per_partition;
     }
 
-    struct scratch_t {
-        std::vector<void*> pointers;
-        hipEvent_t begin = nullptr, end = nullptr;
-        ~scratch_t() {
-            for (void* p : pointers)
-                if (p)
-                    (void)hipFree(p);
-            if (begin)
-                (void)hipEventDestroy(begin);
-            if (end)
-                (void)hipEventDestroy(end);
-        }
-        hipError_t allocate(void** out, std::size_t bytes) {
-            *out = nullptr;
-            const hipError_t e = hipMalloc(out, std::max<std::size_t>(bytes, 16));
-            if (e == hipSuccess)
-                pointers.push_back(*out);
-            return e;
-        }
-    } scratch;
+    event_pair_t events;
+    device_scratch_t scratch(current_device_k); // the caller has selected the device the view lives on
     std::uint32_t *row_norms = nullptr, *query_norms = nullptr;
     float* partial_distances = nullptr;
     std::uint64_t *partial_keys = nullptr, *partial_counts = nullptr;
-    UA_HIP(scratch.allocate((void**)&row_norms, view.size * 4));
-    UA_HIP(scratch.allocate((void**)&query_norms, count * 4));
-    UA_HIP(scratch.allocate((void**)&partial_distances, partitions * count * wanted * 4));
-    UA_HIP(scratch.allocate((void**)&partial_keys, partitions * count * wanted * 8));
-    UA_HIP(scratch.allocate((void**)&partial_counts, partitions * count * 8));
+    UA_HIP(scratch.allocate(&row_norms, view.size * 4));
+    UA_HIP(scratch.allocate(&query_norms, count * 4));
+    UA_HIP(scratch.allocate(&partial_distances, partitions * count * wanted * 4));
+    UA_HIP(scratch.allocate(&partial_keys, partitions * count * wanted * 8));
+    UA_HIP(scratch.allocate(&partial_counts, partitions * count * 8));
     std::uint8_t* padded_queries = nullptr;
     std::uint32_t* shared_bounds = nullptr;
     if (wide) {
-        UA_HIP(scratch.allocate((void**)&padded_queries, (count + wide_queries_k - 1) / wide_queries_k * wide_queries_k *
-                                                              wide_padded_stride(view.bytes_per_vector)));
+        UA_HIP(scratch.allocate(&padded_queries, (count + wide_queries_k - 1) / wide_queries_k * wide_queries_k *
+                                                     wide_padded_stride(view.bytes_per_vector)));
         // per query, the smallest k-th best any partition has reached so far, as ordered bits: all ones = nobody has k results yet
-        UA_HIP(scratch.allocate((void**)&shared_bounds, count * 4));
+        UA_HIP(scratch.allocate(&shared_bounds, count * 4));
         UA_HIP(hipMemsetAsync(shared_bounds, 0xFF, count * 4, stream));
     }
     if (kernel_ms) {
-        UA_HIP(hipEventCreate(&scratch.begin));
-        UA_HIP(hipEventCreate(&scratch.end));
-        UA_HIP(hipEventRecord(scratch.begin, stream));
+        UA_HIP(events.create());
+        UA_HIP(hipEventRecord(events.begin, stream));
     }
     const std::uint8_t* query_bytes = static_cast<const std::uint8_t*>(queries);
     hipError_t e = hipSuccess;
@@ -1364,12 +1346,12 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
     }
 #endif
     if (kernel_ms)
-        UA_HIP(hipEventRecord(scratch.end, stream));
+        UA_HIP(hipEventRecord(events.end, stream));
     if (const char* error = merge_shards_device(partial_distances, partial_keys, partial_counts, partitions, count, wanted,
                                                 distances, keys, counts, stream, false))
         return error;
     if (kernel_ms)
-        UA_HIP(hipEventElapsedTime(kernel_ms, scratch.begin, scratch.end));
+        UA_HIP(hipEventElapsedTime(kernel_ms, events.begin, events.end));
     return nullptr;
 }
 

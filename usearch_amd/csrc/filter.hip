@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "device_scratch.hpp"
 #include "host_util.hpp"
 
 namespace usearch_amd {
@@ -128,17 +129,14 @@ const char* filter_t::from_bits(snapshot_t& snapshot, const std::uint32_t* bits_
     if (words < needed || (needed && !bits_host))
         return "The bitmap does not cover every member";
     if (filter->members_) {
+        device_scratch_t scratch(filter->device_);
         std::uint32_t* given = nullptr;
-        UA_HIP(hipMalloc((void**)&given, needed * 4));
-        hipError_t e = hipMemcpyAsync(given, bits_host, needed * 4, hipMemcpyHostToDevice, snapshot.stream());
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(filter_bits_kernel, dim3(blocks_for(filter->members_)), dim3(filter_threads_k), 0, snapshot.stream(),
-                               snapshot.view().keys, filter->members_, (const std::uint32_t*)given, filter->d_bits_, filter->d_allowed_);
-        }
-        const char* error = e == hipSuccess ? filter->finish(snapshot.stream()) : hip_message(e);
-        (void)hipFree(given);
-        if (error)
-            return error;
+        UA_HIP(scratch.allocate(&given, needed * 4));
+        UA_HIP(hipMemcpyAsync(given, bits_host, needed * 4, hipMemcpyHostToDevice, snapshot.stream()));
+        hipLaunchKernelGGL(filter_bits_kernel, dim3(blocks_for(filter->members_)), dim3(filter_threads_k), 0, snapshot.stream(),
+                           snapshot.view().keys, filter->members_, (const std::uint32_t*)given, filter->d_bits_, filter->d_allowed_);
+        if (const char* e = filter->finish(snapshot.stream()))
+            return e;
     }
     out = std::move(filter);
     return nullptr;
@@ -168,19 +166,16 @@ const char* filter_t::from_keys(snapshot_t& snapshot, const std::uint64_t* keys,
         std::vector<std::uint64_t> sorted(keys, keys + count);
         std::sort(sorted.begin(), sorted.end());
         sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+        device_scratch_t scratch(filter->device_);
         std::uint64_t* listed = nullptr;
-        UA_HIP(hipMalloc((void**)&listed, std::max<std::size_t>(sorted.size(), 1) * 8));
-        hipError_t e = sorted.empty() ? hipSuccess
-                                      : hipMemcpyAsync(listed, sorted.data(), sorted.size() * 8, hipMemcpyHostToDevice, snapshot.stream());
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(filter_keys_kernel, dim3(blocks_for(filter->members_)), dim3(filter_threads_k), 0, snapshot.stream(),
-                               snapshot.view().keys, filter->members_, (const std::uint64_t*)listed, (std::uint64_t)sorted.size(),
-                               allow ? 1u : 0u, filter->d_bits_, filter->d_allowed_);
-        }
-        const char* error = e == hipSuccess ? filter->finish(snapshot.stream()) : hip_message(e); // waits: `sorted` may go
-        (void)hipFree(listed);
-        if (error)
-            return error;
+        UA_HIP(scratch.allocate(&listed, sorted.size() * 8));
+        if (!sorted.empty())
+            UA_HIP(hipMemcpyAsync(listed, sorted.data(), sorted.size() * 8, hipMemcpyHostToDevice, snapshot.stream()));
+        hipLaunchKernelGGL(filter_keys_kernel, dim3(blocks_for(filter->members_)), dim3(filter_threads_k), 0, snapshot.stream(),
+                           snapshot.view().keys, filter->members_, (const std::uint64_t*)listed, (std::uint64_t)sorted.size(),
+                           allow ? 1u : 0u, filter->d_bits_, filter->d_allowed_);
+        if (const char* e = filter->finish(snapshot.stream())) // waits: `sorted` may go
+            return e;
     }
     out = std::move(filter);
     return nullptr;

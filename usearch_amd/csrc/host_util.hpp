@@ -1,5 +1,6 @@
 /**
- *  usearch_amd/csrc/host_util.hpp — small host-side helpers shared by engine.hip and build.hip.
+ *  usearch_amd/csrc/host_util.hpp — small host-side helpers shared by every host-side unit: the `UA_HIP` early return, sizes and
+ *  grids, the host's thread pool, row uploads. Per-call device memory has its own header, device_scratch.hpp.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +27,11 @@ inline std::uint32_t pow2_ceil(std::uint32_t v) {
     while (p < v)
         p <<= 1;
     return p;
+}
+
+/// Workgroups of 256 for a grid-stride kernel over `threads` items: at least one, at most 32 per compute unit.
+inline unsigned blocks_for(std::uint64_t threads, int compute_units) {
+    return (unsigned)std::max<std::uint64_t>(1, std::min<std::uint64_t>((threads + 255) / 256, (std::uint64_t)compute_units * 32));
 }
 
 inline std::size_t env_size(const char* name, std::size_t fallback) {

@@ -21,6 +21,7 @@
 #include <map>
 #include <mutex>
 
+#include "device_scratch.hpp"
 #include "host_util.hpp"
 
 namespace usearch_amd {
@@ -190,29 +191,13 @@ __global__ __launch_bounds__(join_threads_k) void sum_kernel(const std::uint64_t
 unsigned blocks_for(std::uint64_t n) { return (unsigned)std::max<std::uint64_t>(1, (n + join_threads_k - 1) / join_threads_k); }
 unsigned strided_blocks(std::uint64_t n) { return (unsigned)std::min<std::uint64_t>(4096, blocks_for(n)); }
 
-/// Device allocations of one join, freed together.
-struct arena_t {
-    std::vector<void*> blocks;
-    ~arena_t() {
-        for (void* p : blocks)
-            (void)hipFree(p);
-    }
-    template <typename T> const char* get(T*& out, std::uint64_t count) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<std::uint64_t>(1, count) * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            return "The preference lists do not fit in free HBM";
-        }
-        blocks.push_back(p);
-        out = static_cast<T*>(p);
+/// Room for `count` elements out of one of the join's arenas, or the join's own out-of-memory message.
+template <typename T> const char* get(device_scratch_t& arena, T*& out, std::uint64_t count) {
+    if (arena.allocate(&out, count * sizeof(T)) == hipSuccess)
         return nullptr;
-    }
-    void release() {
-        for (void* p : blocks)
-            (void)hipFree(p);
-        blocks.clear();
-    }
-};
+    (void)hipGetLastError();
+    return "The preference lists do not fit in free HBM";
+}
 
 /// Joins run one at a time in a process. A join holds a lease of its proposers' snapshot while every list search leases one of the
 /// other snapshot; two joins in opposite directions over snapshots of one workspace each would otherwise each hold what the other
@@ -295,17 +280,17 @@ const char* join_snapshots(snapshot_t& a, snapshot_t& b, const join_config_t& co
     UA_HIP(hipMemcpy(men_keys.data(), men.view().keys, n_men * 8, hipMemcpyDeviceToHost));
     UA_HIP(hipMemcpy(women_keys.data(), women.view().keys, n_women * 8, hipMemcpyDeviceToHost));
 
-    arena_t arena;
+    device_scratch_t arena(men.device());
     std::uint64_t *pref_slots, *pref_counts, *visited, *computed, *offers;
     float *pref_distances, *husband_distance;
     std::uint32_t *next, *proposed_to, *husband, *free_a, *free_b, *touched, *lazy, *lazy_k_of, *counters;
     unsigned long long* totals;
-    for (const char* e : {arena.get(pref_slots, n_men * width), arena.get(pref_distances, n_men * width), arena.get(pref_counts, n_men),
-                          arena.get(visited, chunk), arena.get(computed, chunk), arena.get(offers, n_women),
-                          arena.get(husband_distance, n_women), arena.get(next, n_men), arena.get(proposed_to, n_men),
-                          arena.get(husband, n_women), arena.get(free_a, n_men), arena.get(free_b, n_men), arena.get(touched, n_men),
-                          arena.get(lazy, n_men), arena.get(lazy_k_of, n_men), arena.get(counters, counters_k),
-                          arena.get(totals, totals_k)})
+    for (const char* e : {get(arena, pref_slots, n_men * width), get(arena, pref_distances, n_men * width), get(arena, pref_counts, n_men),
+                          get(arena, visited, chunk), get(arena, computed, chunk), get(arena, offers, n_women),
+                          get(arena, husband_distance, n_women), get(arena, next, n_men), get(arena, proposed_to, n_men),
+                          get(arena, husband, n_women), get(arena, free_a, n_men), get(arena, free_b, n_men), get(arena, touched, n_men),
+                          get(arena, lazy, n_men), get(arena, lazy_k_of, n_men), get(arena, counters, counters_k),
+                          get(arena, totals, totals_k)})
         if (e)
             return e;
     UA_HIP(hipMemsetAsync(totals, 0, totals_k * 8, stream));
@@ -373,7 +358,7 @@ const char* join_snapshots(snapshot_t& a, snapshot_t& b, const join_config_t& co
     std::uint64_t *lazy_counts = nullptr, *lazy_visited = nullptr, *lazy_computed = nullptr;
     std::uint32_t* lazy_ids = nullptr;
     std::uint64_t lazy_cells = 0, lazy_rows = 0;
-    arena_t lazy_arena; // replaced, not added to, when a larger group comes
+    device_scratch_t lazy_arena(men.device()); // replaced, not added to, when a larger group comes
     std::vector<std::uint32_t> lazy_men, lazy_wanted;
 
     while (free_count) {
@@ -400,9 +385,9 @@ const char* join_snapshots(snapshot_t& a, snapshot_t& b, const join_config_t& co
                     if (cells > lazy_cells || rows > lazy_rows) {
                         lazy_cells = std::max(lazy_cells, cells), lazy_rows = std::max(lazy_rows, rows);
                         lazy_arena.release(); // nothing in flight reads them: every group ends in a synchronize
-                        for (const char* e : {lazy_arena.get(lazy_slots, lazy_cells), lazy_arena.get(lazy_distances, lazy_cells),
-                                              lazy_arena.get(lazy_counts, lazy_rows), lazy_arena.get(lazy_visited, lazy_rows),
-                                              lazy_arena.get(lazy_computed, lazy_rows), lazy_arena.get(lazy_ids, lazy_rows)})
+                        for (const char* e : {get(lazy_arena, lazy_slots, lazy_cells), get(lazy_arena, lazy_distances, lazy_cells),
+                                              get(lazy_arena, lazy_counts, lazy_rows), get(lazy_arena, lazy_visited, lazy_rows),
+                                              get(lazy_arena, lazy_computed, lazy_rows), get(lazy_arena, lazy_ids, lazy_rows)})
                             if (e)
                                 return e;
                     }

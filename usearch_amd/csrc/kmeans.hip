@@ -51,18 +51,13 @@
 
 #include "casts.hpp"
 #include "common.hpp"
+#include "device_scratch.hpp"
+#include "host_util.hpp"
 #include "kmeans.hpp"
 
 namespace usearch_amd {
 
 namespace {
-
-#define UK_HIP(call)                                                                                                                   \
-    do {                                                                                                                               \
-        hipError_t uk_error_ = (call);                                                                                                 \
-        if (uk_error_ != hipSuccess)                                                                                                   \
-            return hipGetErrorString(uk_error_);                                                                                       \
-    } while (0)
 
 constexpr int tile_points_k = 64;     ///< points per workgroup
 constexpr int tile_centroids_k = 128; ///< centroids per inner tile
@@ -670,33 +665,6 @@ __global__ __launch_bounds__(64) void finalize_kernel(double* sums, std::uint32_
 //  Host side
 // ---------------------------------------------------------------------------------------------------------------------
 
-/// A device allocation that goes with its scope.
-struct device_buffer_t {
-    void* data = nullptr;
-    device_buffer_t() = default;
-    device_buffer_t(const device_buffer_t&) = delete;
-    device_buffer_t& operator=(const device_buffer_t&) = delete;
-    ~device_buffer_t() {
-        if (data)
-            (void)hipFree(data);
-    }
-    const char* reserve(std::size_t bytes) {
-        UK_HIP(hipMalloc(&data, bytes ? bytes : 16));
-        return nullptr;
-    }
-    template <typename type_at> type_at* as() const { return static_cast<type_at*>(data); }
-};
-
-struct device_events_t {
-    hipEvent_t begin = nullptr, end = nullptr;
-    ~device_events_t() {
-        if (begin)
-            (void)hipEventDestroy(begin);
-        if (end)
-            (void)hipEventDestroy(end);
-    }
-};
-
 inline std::uint32_t grid_for(std::uint64_t cells, std::uint32_t per_block) {
     const std::uint64_t blocks = (cells + per_block - 1) / per_block;
     return (std::uint32_t)(blocks < 1 ? 1 : (blocks > 65536 ? 65536 : blocks));
@@ -722,29 +690,28 @@ const char* refuse_kinds(scalar_kind_t kind, scalar_kind_t quantization) {
 /// Host rows of `kind` → device rows of `quantization`, `quantized_stride` bytes apart and zero padded, slab by slab.
 const char* quantize_rows(const std::uint8_t* rows, std::size_t count, std::size_t stride, scalar_kind_t kind,
                           std::size_t dimensions, scalar_kind_t quantization, std::uint8_t* quantized, std::size_t quantized_stride) {
-    UK_HIP(hipMemset(quantized, 0, count * quantized_stride));
+    UA_HIP(hipMemset(quantized, 0, count * quantized_stride));
     const std::size_t row_bytes = bytes_per_vector(kind, dimensions);
     if (kind == quantization) {
-        UK_HIP(hipMemcpy2D(quantized, quantized_stride, rows, stride, row_bytes, count, hipMemcpyHostToDevice));
+        UA_HIP(hipMemcpy2D(quantized, quantized_stride, rows, stride, row_bytes, count, hipMemcpyHostToDevice));
         return nullptr;
     }
     const std::size_t slab_rows = std::max<std::size_t>(1, std::min<std::size_t>(count, (std::size_t(1) << 30) / row_bytes));
-    device_buffer_t slab;
-    if (const char* e = slab.reserve(slab_rows * row_bytes))
-        return e;
+    device_scratch_t scratch(current_device_k); // the device of `quantized`, which the caller has selected
+    std::uint8_t* slab = nullptr;
+    UA_HIP(scratch.allocate(&slab, slab_rows * row_bytes));
     for (std::size_t first = 0; first < count; first += slab_rows) {
         const std::size_t here = std::min(slab_rows, count - first);
-        UK_HIP(hipMemcpy2D(slab.data, row_bytes, rows + first * stride, stride, row_bytes, here, hipMemcpyHostToDevice));
+        UA_HIP(hipMemcpy2D(slab, row_bytes, rows + first * stride, stride, row_bytes, here, hipMemcpyHostToDevice));
         std::uint8_t* target = quantized + first * quantized_stride;
         if (quantization == scalar_i8_k)
-            cast_to_i8_kernel<<<(std::uint32_t)((here + 63) / 64), 64>>>(slab.as<std::uint8_t>(), row_bytes, (int)kind, target,
-                                                                         quantized_stride, here, (std::uint32_t)dimensions);
+            cast_to_i8_kernel<<<(std::uint32_t)((here + 63) / 64), 64>>>(slab, row_bytes, (int)kind, target, quantized_stride, here,
+                                                                         (std::uint32_t)dimensions);
         else
-            cast_elements_kernel<<<grid_for(here * dimensions, 256), 256>>>(slab.as<std::uint8_t>(), row_bytes, (int)kind, target,
-                                                                            quantized_stride, (int)quantization, here,
-                                                                            (std::uint32_t)dimensions);
-        UK_HIP(hipGetLastError());
-        UK_HIP(hipDeviceSynchronize()); // the slab is written again
+            cast_elements_kernel<<<grid_for(here * dimensions, 256), 256>>>(slab, row_bytes, (int)kind, target, quantized_stride,
+                                                                            (int)quantization, here, (std::uint32_t)dimensions);
+        UA_HIP(hipGetLastError());
+        UA_HIP(hipDeviceSynchronize()); // the slab is written again
     }
     return nullptr;
 }
@@ -758,7 +725,7 @@ const char* launch_norms(scalar_kind_t quantization, const std::uint8_t* rows, s
         row_norms_kernel<scalar_bf16_k><<<grid, 256>>>(rows, count, stride, bytes, norms);
     else if (quantization == scalar_i8_k)
         row_norms_kernel<scalar_i8_k><<<grid, 256>>>(rows, count, stride, bytes, norms);
-    UK_HIP(hipGetLastError());
+    UA_HIP(hipGetLastError());
     return nullptr;
 }
 
@@ -787,7 +754,7 @@ template <int metric_ak> const char* launch_assign_metric(scalar_kind_t quantiza
     else
         assign_tiled_kernel<metric_ak, scalar_i8_k><<<tiles, 256>>>(a.points, a.count, a.centroids, a.clusters, a.stride, a.point_norms,
                                                                     a.centroid_norms, a.assignments, a.distances, a.shifted);
-    UK_HIP(hipGetLastError());
+    UA_HIP(hipGetLastError());
     return nullptr;
 }
 
@@ -810,14 +777,14 @@ const char* launch_update_kind(metric_kind_t metric, const std::uint8_t* points,
                                std::uint32_t clusters, const std::uint32_t* offsets, const std::uint32_t* members, double* sums,
                                std::uint8_t* centroids) {
     sums_kernel<scalar_ak><<<dim3(clusters, (dimensions + 63) / 64), 64>>>(points, stride, dimensions, clusters, offsets, members, sums);
-    UK_HIP(hipGetLastError());
+    UA_HIP(hipGetLastError());
     if (metric == metric_l2sq_k)
         launch_finalize<metric_l2sq_k, scalar_ak>(sums, dimensions, clusters, offsets, centroids, stride);
     else if (metric == metric_cos_k)
         launch_finalize<metric_cos_k, scalar_ak>(sums, dimensions, clusters, offsets, centroids, stride);
     else
         launch_finalize<metric_ip_k, scalar_ak>(sums, dimensions, clusters, offsets, centroids, stride);
-    UK_HIP(hipGetLastError());
+    UA_HIP(hipGetLastError());
     return nullptr;
 }
 
@@ -851,14 +818,14 @@ const char* kmeans_quantize(const std::uint8_t* points, std::size_t count, std::
         return e;
     if (!count)
         return nullptr;
-    UK_HIP(hipSetDevice(device));
+    UA_HIP(hipSetDevice(device));
     const std::size_t quantized_stride = quantized_stride_of(quantization, dimensions);
-    device_buffer_t quantized;
-    if (const char* e = quantized.reserve(count * quantized_stride))
+    device_scratch_t scratch(device);
+    std::uint8_t* quantized = nullptr;
+    UA_HIP(scratch.allocate(&quantized, count * quantized_stride));
+    if (const char* e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride))
         return e;
-    if (const char* e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized.as<std::uint8_t>(), quantized_stride))
-        return e;
-    UK_HIP(hipMemcpy2D(out, out_stride, quantized.data, quantized_stride, bytes_per_vector(quantization, dimensions), count,
+    UA_HIP(hipMemcpy2D(out, out_stride, quantized, quantized_stride, bytes_per_vector(quantization, dimensions), count,
                        hipMemcpyDeviceToHost));
     return nullptr;
 }
@@ -876,35 +843,37 @@ const char* kmeans_assign(const std::uint8_t* points, std::size_t count, std::si
         return e;
     if (!count)
         return nullptr;
-    UK_HIP(hipSetDevice(device));
+    UA_HIP(hipSetDevice(device));
     const std::size_t quantized_stride = quantized_stride_of(quantization, dimensions);
     const std::uint32_t bytes = (std::uint32_t)bytes_per_vector(quantization, dimensions);
-    device_buffer_t quantized, quantized_centroids, point_norms, centroid_norms, indexes, nearest, shifted;
+    device_scratch_t scratch(device);
+    std::uint8_t *quantized = nullptr, *quantized_centroids = nullptr;
+    std::uint32_t *point_norms = nullptr, *centroid_norms = nullptr, *indexes = nullptr, *shifted = nullptr;
+    float* nearest = nullptr;
+    UA_HIP(scratch.allocate(&quantized, count * quantized_stride));
+    UA_HIP(scratch.allocate(&quantized_centroids, clusters * quantized_stride));
+    UA_HIP(scratch.allocate(&point_norms, count * 4));
+    UA_HIP(scratch.allocate(&centroid_norms, clusters * 4));
+    UA_HIP(scratch.allocate(&indexes, count * 4));
+    UA_HIP(scratch.allocate(&nearest, count * 4));
+    UA_HIP(scratch.allocate(&shifted, 4));
     const char* e = nullptr;
-    if ((e = quantized.reserve(count * quantized_stride)) || (e = quantized_centroids.reserve(clusters * quantized_stride)) ||
-        (e = point_norms.reserve(count * 4)) || (e = centroid_norms.reserve(clusters * 4)) || (e = indexes.reserve(count * 4)) ||
-        (e = nearest.reserve(count * 4)) || (e = shifted.reserve(4)))
-        return e;
-    if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized.as<std::uint8_t>(), quantized_stride)) ||
-        (e = quantize_rows(centroids, clusters, centroids_stride, kind, dimensions, quantization, quantized_centroids.as<std::uint8_t>(),
-                           quantized_stride)))
+    if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride)) ||
+        (e = quantize_rows(centroids, clusters, centroids_stride, kind, dimensions, quantization, quantized_centroids, quantized_stride)))
         return e;
     if (quantization != scalar_f32_k)
-        if ((e = launch_norms(quantization, quantized.as<std::uint8_t>(), count, quantized_stride, bytes, point_norms.as<std::uint32_t>())) ||
-            (e = launch_norms(quantization, quantized_centroids.as<std::uint8_t>(), clusters, quantized_stride, bytes,
-                              centroid_norms.as<std::uint32_t>())))
+        if ((e = launch_norms(quantization, quantized, count, quantized_stride, bytes, point_norms)) ||
+            (e = launch_norms(quantization, quantized_centroids, clusters, quantized_stride, bytes, centroid_norms)))
             return e;
-    UK_HIP(hipMemset(indexes.data, 0xFF, count * 4));
-    UK_HIP(hipMemset(shifted.data, 0, 4));
-    const assign_args_t args{quantized.as<std::uint8_t>(), (std::uint32_t)count, quantized_centroids.as<std::uint8_t>(),
-                             (std::uint32_t)clusters, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
-                             point_norms.as<std::uint32_t>(), centroid_norms.as<std::uint32_t>(), indexes.as<std::uint32_t>(),
-                             nearest.as<float>(), shifted.as<std::uint32_t>()};
+    UA_HIP(hipMemset(indexes, 0xFF, count * 4));
+    UA_HIP(hipMemset(shifted, 0, 4));
+    const assign_args_t args{quantized, (std::uint32_t)count, quantized_centroids, (std::uint32_t)clusters, (std::uint32_t)quantized_stride,
+                             (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, shifted};
     if ((e = launch_assign(metric, quantization, args)))
         return e;
     std::vector<std::uint32_t> narrow(count);
-    UK_HIP(hipMemcpy(narrow.data(), indexes.data, count * 4, hipMemcpyDeviceToHost));
-    UK_HIP(hipMemcpy(distances, nearest.data, count * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(narrow.data(), indexes, count * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(distances, nearest, count * 4, hipMemcpyDeviceToHost));
     for (std::size_t i = 0; i != count; ++i)
         assignments[i] = narrow[i];
     return nullptr;
@@ -928,7 +897,7 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
         return e;
     if (const char* e = check_shape(count, dimensions, clusters))
         return e;
-    UK_HIP(hipSetDevice(config.device)); // before any allocation
+    UA_HIP(hipSetDevice(config.device)); // before any allocation
 
     const std::size_t quantized_stride = quantized_stride_of(quantization, dimensions);
     const std::uint32_t bytes = (std::uint32_t)bytes_per_vector(quantization, dimensions);
@@ -946,26 +915,36 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
                                chunks * clusters * 4 + clusters * dimensions * 8 +
                                (kind == quantization ? 0 : std::min<std::size_t>(count * bytes_per_vector(kind, dimensions), std::size_t(1) << 30));
     std::size_t free_bytes = 0, total_bytes = 0;
-    UK_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
+    UA_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
     if (needed > free_bytes)
         return "The points, the centroids and their f64 sums do not fit in free device memory";
 
-    device_buffer_t quantized, quantized_centroids, point_norms, centroid_norms, indexes, nearest, scalars, seeds, cells, counts, offsets,
-        members, sums;
-    const char* e = nullptr;
-    if ((e = quantized.reserve(count * quantized_stride)) || (e = quantized_centroids.reserve(clusters * quantized_stride)) ||
-        (e = point_norms.reserve(count * 4)) || (e = centroid_norms.reserve(clusters * 4)) || (e = indexes.reserve(count * 4)) ||
-        (e = nearest.reserve(count * 4)) || (e = scalars.reserve(16)) || (e = seeds.reserve(clusters * 4)) ||
-        (e = cells.reserve(chunks * clusters * 4)) || (e = counts.reserve(clusters * 4)) || (e = offsets.reserve((clusters + 1) * 4)) ||
-        (e = members.reserve(count * 4)) || (e = sums.reserve(clusters * dimensions * 8)))
-        return e;
-    device_events_t events;
-    UK_HIP(hipEventCreate(&events.begin));
-    UK_HIP(hipEventCreate(&events.end));
+    device_scratch_t scratch(config.device);
+    std::uint8_t *quantized = nullptr, *quantized_centroids = nullptr;
+    std::uint32_t *point_norms = nullptr, *centroid_norms = nullptr, *indexes = nullptr, *scalars = nullptr, *seeds = nullptr,
+                  *cells = nullptr, *counts = nullptr, *offsets = nullptr, *members = nullptr;
+    float* nearest = nullptr;
+    double* sums = nullptr;
+    UA_HIP(scratch.allocate(&quantized, count * quantized_stride));
+    UA_HIP(scratch.allocate(&quantized_centroids, clusters * quantized_stride));
+    UA_HIP(scratch.allocate(&point_norms, count * 4));
+    UA_HIP(scratch.allocate(&centroid_norms, clusters * 4));
+    UA_HIP(scratch.allocate(&indexes, count * 4));
+    UA_HIP(scratch.allocate(&nearest, count * 4));
+    UA_HIP(scratch.allocate(&scalars, 16)); // the f64 aggregate, then the count of points that changed centroid
+    UA_HIP(scratch.allocate(&seeds, clusters * 4));
+    UA_HIP(scratch.allocate(&cells, chunks * clusters * 4));
+    UA_HIP(scratch.allocate(&counts, clusters * 4));
+    UA_HIP(scratch.allocate(&offsets, (clusters + 1) * 4));
+    UA_HIP(scratch.allocate(&members, count * 4));
+    UA_HIP(scratch.allocate(&sums, clusters * dimensions * 8));
+    event_pair_t events;
+    UA_HIP(events.create());
 
-    if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized.as<std::uint8_t>(), quantized_stride)))
+    const char* e = nullptr;
+    if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride)))
         return e;
-    UK_HIP(hipMemset(quantized_centroids.data, 0, clusters * quantized_stride));
+    UA_HIP(hipMemset(quantized_centroids, 0, clusters * quantized_stride));
 
     // ---- seeding, index_plugins.hpp:2308-2350, the uniqueness test as the reference has it
     std::vector<std::uint32_t> index(count, (std::uint32_t)clusters), seed_points(clusters);
@@ -989,21 +968,18 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
             index[random_index] = (std::uint32_t)i;
         }
     }
-    UK_HIP(hipMemcpy(indexes.data, index.data(), count * 4, hipMemcpyHostToDevice));
-    UK_HIP(hipMemcpy(seeds.data, seed_points.data(), clusters * 4, hipMemcpyHostToDevice));
-    gather_rows_kernel<<<grid_for(clusters * (quantized_stride / 16), 256), 256>>>(quantized.as<std::uint8_t>(), seeds.as<std::uint32_t>(),
-                                                                                   quantized_centroids.as<std::uint8_t>(),
-                                                                                   (std::uint32_t)clusters, (std::uint32_t)quantized_stride);
-    UK_HIP(hipGetLastError());
+    UA_HIP(hipMemcpy(indexes, index.data(), count * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(seeds, seed_points.data(), clusters * 4, hipMemcpyHostToDevice));
+    gather_rows_kernel<<<grid_for(clusters * (quantized_stride / 16), 256), 256>>>(quantized, seeds, quantized_centroids, (std::uint32_t)clusters,
+                                                                                   (std::uint32_t)quantized_stride);
+    UA_HIP(hipGetLastError());
     if (quantization != scalar_f32_k)
-        if ((e = launch_norms(quantization, quantized.as<std::uint8_t>(), count, quantized_stride, bytes, point_norms.as<std::uint32_t>())))
+        if ((e = launch_norms(quantization, quantized, count, quantized_stride, bytes, point_norms)))
             return e;
-    UK_HIP(hipDeviceSynchronize());
+    UA_HIP(hipDeviceSynchronize());
 
-    const assign_args_t args{quantized.as<std::uint8_t>(), (std::uint32_t)count, quantized_centroids.as<std::uint8_t>(),
-                             (std::uint32_t)clusters, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
-                             point_norms.as<std::uint32_t>(), centroid_norms.as<std::uint32_t>(), indexes.as<std::uint32_t>(),
-                             nearest.as<float>(), scalars.as<std::uint32_t>() + 2};
+    const assign_args_t args{quantized, (std::uint32_t)count, quantized_centroids, (std::uint32_t)clusters, (std::uint32_t)quantized_stride,
+                             (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, scalars + 2};
     struct {
         double aggregate;
         std::uint32_t shifted, unused;
@@ -1017,20 +993,19 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
     while (iterations < config.max_iterations) {
         iterations++;
         // ---- assignment: the centroids' norms, every point against every centroid, the aggregate
-        UK_HIP(hipMemsetAsync(scalars.data, 0, 16));
-        UK_HIP(hipEventRecord(events.begin));
+        UA_HIP(hipMemsetAsync(scalars, 0, 16));
+        UA_HIP(hipEventRecord(events.begin));
         if (quantization != scalar_f32_k)
-            if ((e = launch_norms(quantization, quantized_centroids.as<std::uint8_t>(), clusters, quantized_stride, bytes,
-                                  centroid_norms.as<std::uint32_t>())))
+            if ((e = launch_norms(quantization, quantized_centroids, clusters, quantized_stride, bytes, centroid_norms)))
                 return e;
         if ((e = launch_assign(metric, quantization, args)))
             return e;
-        aggregate_kernel<<<1, 1024>>>(nearest.as<float>(), (std::uint32_t)count, scalars.as<double>());
-        UK_HIP(hipGetLastError());
-        UK_HIP(hipEventRecord(events.end));
-        UK_HIP(hipMemcpy(&readback, scalars.data, 16, hipMemcpyDeviceToHost));
+        aggregate_kernel<<<1, 1024>>>(nearest, (std::uint32_t)count, reinterpret_cast<double*>(scalars));
+        UA_HIP(hipGetLastError());
+        UA_HIP(hipEventRecord(events.end));
+        UA_HIP(hipMemcpy(&readback, scalars, 16, hipMemcpyDeviceToHost));
         float milliseconds = 0;
-        UK_HIP(hipEventElapsedTime(&milliseconds, events.begin, events.end));
+        UA_HIP(hipEventElapsedTime(&milliseconds, events.begin, events.end));
         result.assign_ms += milliseconds;
 
         const double aggregate_distance = readback.aggregate;
@@ -1053,50 +1028,44 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
                 break;
 
         // ---- update
-        UK_HIP(hipEventRecord(events.begin));
-        UK_HIP(hipMemsetAsync(cells.data, 0, chunks * clusters * 4));
-        members_kernel<false><<<(std::uint32_t)chunks, 64>>>(indexes.as<std::uint32_t>(), (std::uint32_t)count, (std::uint32_t)clusters,
-                                                             (std::uint32_t)steps, cells.as<std::uint32_t>(), nullptr, nullptr);
-        chunk_scan_kernel<<<(std::uint32_t)((clusters + 255) / 256), 256>>>(cells.as<std::uint32_t>(), (std::uint32_t)chunks,
-                                                                            (std::uint32_t)clusters, counts.as<std::uint32_t>());
-        offsets_kernel<<<1, 1024>>>(counts.as<std::uint32_t>(), (std::uint32_t)clusters, offsets.as<std::uint32_t>());
-        members_kernel<true><<<(std::uint32_t)chunks, 64>>>(indexes.as<std::uint32_t>(), (std::uint32_t)count, (std::uint32_t)clusters,
-                                                            (std::uint32_t)steps, cells.as<std::uint32_t>(), offsets.as<std::uint32_t>(),
-                                                            members.as<std::uint32_t>());
-        UK_HIP(hipGetLastError());
-        const std::uint8_t* rows = quantized.as<std::uint8_t>();
-        std::uint8_t* targets = quantized_centroids.as<std::uint8_t>();
-        const std::uint32_t* starts = offsets.as<std::uint32_t>();
-        const std::uint32_t* listed = members.as<std::uint32_t>();
+        UA_HIP(hipEventRecord(events.begin));
+        UA_HIP(hipMemsetAsync(cells, 0, chunks * clusters * 4));
+        members_kernel<false><<<(std::uint32_t)chunks, 64>>>(indexes, (std::uint32_t)count, (std::uint32_t)clusters, (std::uint32_t)steps, cells,
+                                                             nullptr, nullptr);
+        chunk_scan_kernel<<<(std::uint32_t)((clusters + 255) / 256), 256>>>(cells, (std::uint32_t)chunks, (std::uint32_t)clusters, counts);
+        offsets_kernel<<<1, 1024>>>(counts, (std::uint32_t)clusters, offsets);
+        members_kernel<true><<<(std::uint32_t)chunks, 64>>>(indexes, (std::uint32_t)count, (std::uint32_t)clusters, (std::uint32_t)steps, cells,
+                                                            offsets, members);
+        UA_HIP(hipGetLastError());
         if (quantization == scalar_f32_k)
-            e = launch_update_kind<scalar_f32_k>(metric, rows, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
-                                                 (std::uint32_t)clusters, starts, listed, sums.as<double>(), targets);
+            e = launch_update_kind<scalar_f32_k>(metric, quantized, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
+                                                 (std::uint32_t)clusters, offsets, members, sums, quantized_centroids);
         else if (quantization == scalar_f16_k)
-            e = launch_update_kind<scalar_f16_k>(metric, rows, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
-                                                 (std::uint32_t)clusters, starts, listed, sums.as<double>(), targets);
+            e = launch_update_kind<scalar_f16_k>(metric, quantized, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
+                                                 (std::uint32_t)clusters, offsets, members, sums, quantized_centroids);
         else if (quantization == scalar_bf16_k)
-            e = launch_update_kind<scalar_bf16_k>(metric, rows, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
-                                                  (std::uint32_t)clusters, starts, listed, sums.as<double>(), targets);
+            e = launch_update_kind<scalar_bf16_k>(metric, quantized, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
+                                                  (std::uint32_t)clusters, offsets, members, sums, quantized_centroids);
         else
-            e = launch_update_kind<scalar_i8_k>(metric, rows, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
-                                                (std::uint32_t)clusters, starts, listed, sums.as<double>(), targets);
+            e = launch_update_kind<scalar_i8_k>(metric, quantized, (std::uint32_t)quantized_stride, (std::uint32_t)dimensions,
+                                                (std::uint32_t)clusters, offsets, members, sums, quantized_centroids);
         if (e)
             return e;
-        UK_HIP(hipEventRecord(events.end));
-        UK_HIP(hipEventSynchronize(events.end));
-        UK_HIP(hipEventElapsedTime(&milliseconds, events.begin, events.end));
+        UA_HIP(hipEventRecord(events.end));
+        UA_HIP(hipEventSynchronize(events.end));
+        UA_HIP(hipEventElapsedTime(&milliseconds, events.begin, events.end));
         result.update_ms += milliseconds;
     }
 
     // ---- export, index_plugins.hpp:2480-2496
     result.iterations = iterations;
     result.computed_distances = (std::uint64_t)count * clusters * iterations;
-    UK_HIP(hipMemcpy(index.data(), indexes.data, count * 4, hipMemcpyDeviceToHost));
-    UK_HIP(hipMemcpy(distances, nearest.data, count * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(index.data(), indexes, count * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(distances, nearest, count * 4, hipMemcpyDeviceToHost));
     for (std::size_t i = 0; i != count; ++i)
         assignments[i] = index[i];
     std::vector<std::uint8_t> rows(clusters * quantized_stride);
-    UK_HIP(hipMemcpy(rows.data(), quantized_centroids.data, rows.size(), hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(rows.data(), quantized_centroids, rows.size(), hipMemcpyDeviceToHost));
     for (std::size_t i = 0; i != clusters; ++i) {
         const std::uint8_t* row = rows.data() + i * quantized_stride;
         std::uint8_t* target = centroids + i * centroids_stride;

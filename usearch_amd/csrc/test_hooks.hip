@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "device_scratch.hpp"
+#include "host_util.hpp"
 #include "kernels.hpp"
 #include "kmeans.hpp"
 #include "placement.hpp"
@@ -131,8 +133,9 @@ __attribute__((visibility("default"))) void usearch_amd_bench_heap(uint32_t seri
                                                                     uint32_t waves, uint64_t* pop_ticks,
                                                                     uint64_t* push_ticks, uint64_t* checksums,
                                                                     usearch_amd_error_t* error) {
+    device_scratch_t scratch(current_device_k);
     unsigned long long* d_out = nullptr;
-    if (hipMalloc((void**)&d_out, (size_t)waves * 24) != hipSuccess)
+    if (scratch.allocate(&d_out, (size_t)waves * 24) != hipSuccess)
         return fail(error, "hipMalloc failed");
     const size_t lds = ((size_t)fill + 8) * 8;
     if (serial)
@@ -145,15 +148,15 @@ __attribute__((visibility("default"))) void usearch_amd_bench_heap(uint32_t seri
         fail(error, "heap bench failed");
     for (uint32_t w = 0; w < waves; ++w)
         pop_ticks[w] = host[3 * w], push_ticks[w] = host[3 * w + 1], checksums[w] = host[3 * w + 2];
-    (void)hipFree(d_out);
 }
 
 /** Diagnostic: ticks[wave] and accepted[wave] of `top_bench_kernel` (entries per lane 4, 8 or 16). */
 __attribute__((visibility("default"))) void usearch_amd_bench_top(uint32_t epl, uint32_t count, uint32_t limit,
                                                                    uint32_t waves, uint64_t* ticks, uint64_t* accepted,
                                                                    usearch_amd_error_t* error) {
+    device_scratch_t scratch(current_device_k);
     unsigned long long* d_out = nullptr;
-    if (hipMalloc((void**)&d_out, (size_t)waves * 16) != hipSuccess)
+    if (scratch.allocate(&d_out, (size_t)waves * 16) != hipSuccess)
         return fail(error, "hipMalloc failed");
     if (epl == 4)
         hipLaunchKernelGGL(top_bench_kernel<4>, dim3(waves), dim3(64), 0, nullptr, count, limit, d_out);
@@ -167,7 +170,6 @@ __attribute__((visibility("default"))) void usearch_amd_bench_top(uint32_t epl, 
         fail(error, "top bench failed");
     for (uint32_t w = 0; w < waves; ++w)
         ticks[w] = host[2 * w], accepted[w] = host[2 * w + 1] >> 32;
-    (void)hipFree(d_out);
 }
 
 /**
@@ -175,48 +177,76 @@ __attribute__((visibility("default"))) void usearch_amd_bench_top(uint32_t epl, 
  *  {keys[i], slots[i]}, 1 = frontier pop, 2 = insert {keys[i], slots[i]} into the result buffer limited to `limit`) and
  *  returns what was popped and the final result buffer, each entry packed as (slot << 32 | float bits).
  */
-__attribute__((visibility("default"))) void usearch_amd_test_containers(uint32_t const* kinds, float const* keys, uint32_t const* slots, size_t count,
-                                 size_t limit, uint64_t* popped, size_t* popped_count, uint64_t* top, size_t* top_count,
-                                 usearch_amd_error_t* error) {
+static const char* test_containers(uint32_t const* kinds, float const* keys, uint32_t const* slots, size_t count, size_t limit,
+                                   uint64_t* popped, size_t* popped_count, uint64_t* top, size_t* top_count) {
     const size_t capacity = count + 1;
     uint32_t *d_kinds = nullptr, *d_slots = nullptr, *d_counts = nullptr;
     float* d_keys = nullptr;
     uint64_t *d_popped = nullptr, *d_top = nullptr;
-    hipError_t e = hipSuccess;
-    auto check = [&](hipError_t r) {
-        if (e == hipSuccess)
-            e = r;
-    };
-    check(hipMalloc((void**)&d_kinds, count * 4 + 4));
-    check(hipMalloc((void**)&d_slots, count * 4 + 4));
-    check(hipMalloc((void**)&d_keys, count * 4 + 4));
-    check(hipMalloc((void**)&d_popped, capacity * 8));
-    check(hipMalloc((void**)&d_top, (limit + 1) * 8));
-    check(hipMalloc((void**)&d_counts, 8));
-    if (e == hipSuccess) {
-        check(hipMemcpy(d_kinds, kinds, count * 4, hipMemcpyHostToDevice));
-        check(hipMemcpy(d_slots, slots, count * 4, hipMemcpyHostToDevice));
-        check(hipMemcpy(d_keys, keys, count * 4, hipMemcpyHostToDevice));
-        const size_t lds = (capacity + limit + 1) * 8;
-        hipLaunchKernelGGL(containers_kernel, dim3(1), dim3(64), lds, nullptr, d_kinds, d_keys, d_slots,
-                           (uint32_t)count, (uint32_t)limit, (uint32_t)capacity, d_popped, d_counts, d_top,
-                           d_counts + 1);
-        check(hipGetLastError());
-        check(hipDeviceSynchronize());
-        uint32_t host_counts[2] = {0, 0};
-        check(hipMemcpy(host_counts, d_counts, 8, hipMemcpyDeviceToHost));
-        if (e == hipSuccess) {
-            *popped_count = host_counts[0];
-            *top_count = host_counts[1];
-            check(hipMemcpy(popped, d_popped, host_counts[0] * 8, hipMemcpyDeviceToHost));
-            check(hipMemcpy(top, d_top, host_counts[1] * 8, hipMemcpyDeviceToHost));
+    device_scratch_t scratch(current_device_k);
+    UA_HIP(scratch.allocate(&d_kinds, count * 4 + 4));
+    UA_HIP(scratch.allocate(&d_slots, count * 4 + 4));
+    UA_HIP(scratch.allocate(&d_keys, count * 4 + 4));
+    UA_HIP(scratch.allocate(&d_popped, capacity * 8));
+    UA_HIP(scratch.allocate(&d_top, (limit + 1) * 8));
+    UA_HIP(scratch.allocate(&d_counts, 8));
+    UA_HIP(hipMemcpy(d_kinds, kinds, count * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_slots, slots, count * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_keys, keys, count * 4, hipMemcpyHostToDevice));
+    const size_t lds = (capacity + limit + 1) * 8;
+    hipLaunchKernelGGL(containers_kernel, dim3(1), dim3(64), lds, nullptr, d_kinds, d_keys, d_slots, (uint32_t)count, (uint32_t)limit,
+                       (uint32_t)capacity, d_popped, d_counts, d_top, d_counts + 1);
+    UA_HIP(hipGetLastError());
+    UA_HIP(hipDeviceSynchronize());
+    uint32_t host_counts[2] = {0, 0};
+    UA_HIP(hipMemcpy(host_counts, d_counts, 8, hipMemcpyDeviceToHost));
+    *popped_count = host_counts[0];
+    *top_count = host_counts[1];
+    UA_HIP(hipMemcpy(popped, d_popped, host_counts[0] * 8, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(top, d_top, host_counts[1] * 8, hipMemcpyDeviceToHost));
+    return nullptr;
+}
+__attribute__((visibility("default"))) void usearch_amd_test_containers(uint32_t const* kinds, float const* keys, uint32_t const* slots, size_t count,
+                                 size_t limit, uint64_t* popped, size_t* popped_count, uint64_t* top, size_t* top_count,
+                                 usearch_amd_error_t* error) {
+    fail(error, test_containers(kinds, keys, slots, count, limit, popped, popped_count, top, top_count));
+}
+
+/**
+ *  Self-test hook of `device_scratch_t` (device_scratch.hpp); launches no kernel. Makes `current` the thread's device, opens a holder for
+ *  `home`, takes blocks of 0, 1 and 4096 bytes, then asks for 2^60 bytes, which the runtime refuses. Reports, read AFTER that refusal:
+ *  `pointers[3]`, the device each block lives on (`devices[3]`) and the room behind each pointer (`room[3]`, bytes); the refused
+ *  request's error code (`refused`, a hipError_t) and what it left in its out-pointer (`refused_pointer`). The scope then ends and
+ *  the thread's device is put back.
+ */
+__attribute__((visibility("default"))) void usearch_amd_test_device_scratch(int home, int current, void** pointers, int* devices, size_t* room,
+                                                                             int* refused, void** refused_pointer,
+                                                                             usearch_amd_error_t* error) {
+    int entered = 0;
+    fail(error, [&]() -> const char* {
+        UA_HIP(hipGetDevice(&entered));
+        UA_HIP(hipSetDevice(current));
+        device_scratch_t scratch(home);
+        const size_t sizes[3] = {0, 1, 4096};
+        std::uint8_t* blocks[3] = {nullptr, nullptr, nullptr};
+        for (int i = 0; i < 3; ++i)
+            UA_HIP(scratch.allocate(&blocks[i], sizes[i]));
+        std::uint8_t* huge = reinterpret_cast<std::uint8_t*>(std::uintptr_t(1)); // must come back null
+        *refused = (int)scratch.allocate(&huge, std::size_t(1) << 60);
+        *refused_pointer = huge;
+        (void)hipGetLastError(); // the refusal is expected: leave no error behind for the next launch check of this thread
+        for (int i = 0; i < 3; ++i) {
+            hipPointerAttribute_t attributes{};
+            UA_HIP(hipPointerGetAttributes(&attributes, blocks[i]));
+            hipDeviceptr_t base = nullptr;
+            size_t extent = 0;
+            UA_HIP(hipMemGetAddressRange(&base, &extent, blocks[i]));
+            pointers[i] = blocks[i], devices[i] = attributes.device;
+            room[i] = extent - (size_t)(blocks[i] - static_cast<std::uint8_t*>(base));
         }
-    }
-    for (void* p : {(void*)d_kinds, (void*)d_slots, (void*)d_keys, (void*)d_popped, (void*)d_top, (void*)d_counts})
-        if (p)
-            (void)hipFree(p);
-    if (e != hipSuccess)
-        fail(error, hipGetErrorString(e));
+        return nullptr;
+    }());
+    (void)hipSetDevice(entered);
 }
 
 } // extern "C"

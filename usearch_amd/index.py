@@ -1256,6 +1256,9 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_kmeans_quantize.restype = None
         _test_hooks.usearch_amd_test_kmeans_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_device_scratch.restype = None
+        _test_hooks.usearch_amd_test_device_scratch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                                                C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]
     return _test_hooks
 
 
@@ -1330,6 +1333,21 @@ def test_sketch_bounds(rows: np.ndarray, queries: np.ndarray, dtype: str):
                                                 rows.strides[0], _pointer(bounds), C.byref(rank), C.byref(err))
     _raise(err, "usearch_amd_test_sketch_bounds")
     return bounds, int(rank.value)
+
+
+def test_device_scratch(home: int, current: int) -> dict:
+    """The holder of per-call device memory (csrc/device_scratch.hpp), no kernel involved: with device `current` selected, a holder for
+    device `home` takes blocks of 0, 1 and 4096 bytes, then is refused 2^60 bytes. → what was read after the refusal: `pointers`,
+    `devices` and `room` (bytes behind each pointer) of the three blocks, the refusal's `refused` (a hipError_t, 0 = it was granted)
+    and `refused_pointer` (what the refused request left in its out-pointer; 0 = null)."""
+    pointers, room = np.zeros(3, dtype=np.uint64), np.zeros(3, dtype=np.uint64)
+    devices = np.full(3, -1, dtype=np.int32)
+    refused, refused_pointer, err = C.c_int(), C.c_void_p(1), C.c_char_p()
+    test_hooks().usearch_amd_test_device_scratch(home, current, _pointer(pointers), _pointer(devices), _pointer(room), C.byref(refused),
+                                                 C.byref(refused_pointer), C.byref(err))
+    _raise(err, "usearch_amd_test_device_scratch")
+    return {"pointers": [int(p) for p in pointers], "devices": [int(d) for d in devices], "room": [int(r) for r in room],
+            "refused": int(refused.value), "refused_pointer": int(refused_pointer.value or 0)}
 
 
 def test_containers(kinds: np.ndarray, keys: np.ndarray, slots: np.ndarray, limit: int):
