@@ -67,13 +67,31 @@ def test_exact_search_of_a_raw_dataset():
     assert np.array_equal(keys[:, 0] == np.arange(50), distances[:, 0] == 0) and np.all(distances[:, 0] == 0)
 
 
-@pytest.mark.parametrize("tile", [64, 256])
-@pytest.mark.parametrize("metric,dtype,ndim,n,k,full_range",
-                         [("l2sq", "i8", 96, 20011, 10, False), ("cos", "i8", 40, 9000, 64, False), ("ip", "i8", 130, 5003, 7, False),
-                          ("cos", "i8", 200, 9000, 16, False), ("cos", "i8", 130, 5003, 16, True)],
-                         ids=["l2sq-i8-96-20011-10", "cos-i8-40-9000-64", "ip-i8-130-5003-7", "cos-i8-200-9000-16",
-                              "cos-i8-130-5003-16-full-range"])
-def test_tiled_exact_search_is_bit_identical_for_i8(reference, monkeypatch, metric, dtype, ndim, n, k, full_range, tile):
+def routed(cases):
+    """(…, n, k, …) cases → one `pytest.param` per case and forced tile, with the kernel it is there for: `tile=256` takes the wide
+    tile only for k ≤ 16 over ≥ 8 192 rows (csrc/exact_plan.hpp) — a case with more results says in its id that the 64 tile takes it,
+    and a case with fewer rows is run over 8 200 when the wide tile is what it is meant for."""
+    params = []
+    for metric, dtype, ndim, n, k, *rest in cases:
+        suffix = "".join(f"-{part}" for part in rest if isinstance(part, str))
+        flags = [part for part in rest if not isinstance(part, str)]
+        params.append(pytest.param(metric, dtype, ndim, n, k, *flags, 64, False, id=f"{metric}-{dtype}-{ndim}-{n}-{k}{suffix}-64"))
+        rows = n if k > 16 else max(n, 8200)
+        params.append(pytest.param(metric, dtype, ndim, rows, k, *flags, 256, k <= 16,
+                                   id=f"{metric}-{dtype}-{ndim}-{rows}-{k}{suffix}-256" + ("" if k <= 16 else "-takes-64")))
+    return params
+
+
+def assert_route(index, rows, count, k, wide):
+    """Through the planner's test hook, with the environment as the engine reads it: the kernel this case is there for runs."""
+    from usearch_amd.index import test_plan_exact
+    assert bool(test_plan_exact(rows, index.bytes_per_vector, index.row_stride, count, k)["wide"]) == wide
+
+
+@pytest.mark.parametrize("metric,dtype,ndim,n,k,full_range,tile,wide",
+                         routed([("l2sq", "i8", 96, 20011, 10, False), ("cos", "i8", 40, 9000, 64, False), ("ip", "i8", 130, 5003, 7, False),
+                                 ("cos", "i8", 200, 9000, 16, False), ("cos", "i8", 130, 5003, 16, True, "full-range")]))
+def test_tiled_exact_search_is_bit_identical_for_i8(reference, monkeypatch, metric, dtype, ndim, n, k, full_range, tile, wide):
     """The matrix-unit kernels (exact_tiled.hip: 64 queries per workgroup, and the wide tile of 256 for batches that fill the
     chip with it — forced here either way) sum integers exactly and close with the same arithmetic as the wave-per-query
     kernel, so keys, distance bits and counts are identical — ties resolved as lower_bound insertion in slot order does —
@@ -89,6 +107,7 @@ def test_tiled_exact_search_is_bit_identical_for_i8(reference, monkeypatch, metr
     queries = distance_edges.full_range_i8(count, ndim, 94) if full_range else util.make_vectors(count, ndim, dtype, seed=94)
     queries[:20] = vectors[:20]
     index = Index.restore(image)
+    assert_route(index, n, count, k, wide)
     exact = index.search(queries, k, exact=True)
     tiled = index.search(queries, k, exact="tiled")
     assert np.array_equal(exact.counts, tiled.counts)
@@ -97,11 +116,11 @@ def test_tiled_exact_search_is_bit_identical_for_i8(reference, monkeypatch, metr
     assert not np.isin(tiled.keys, removed[:200]).any()
 
 
-@pytest.mark.parametrize("tile", [64, 256])
-@pytest.mark.parametrize("metric,dtype,ndim,n,k", [("cos", "f16", 768, 12001, 10), ("ip", "f16", 100, 9000, 32), ("ip", "f16", 256, 9000, 10),
-                                                   ("cos", "bf16", 96, 7000, 10), ("ip", "bf16", 768, 5000, 5),
-                                                   ("l2sq", "f16", 96, 6000, 10), ("l2sq", "bf16", 200, 5000, 8)])
-def test_tiled_exact_search_of_float_pairs_is_within_tolerance(reference, monkeypatch, metric, dtype, ndim, n, k, tile):
+@pytest.mark.parametrize("metric,dtype,ndim,n,k,tile,wide",
+                         routed([("cos", "f16", 768, 12001, 10), ("ip", "f16", 100, 9000, 32), ("ip", "f16", 256, 9000, 10),
+                                 ("cos", "bf16", 96, 7000, 10), ("ip", "bf16", 768, 5000, 5),
+                                 ("l2sq", "f16", 96, 6000, 10), ("l2sq", "bf16", 200, 5000, 8)]))
+def test_tiled_exact_search_of_float_pairs_is_within_tolerance(reference, monkeypatch, metric, dtype, ndim, n, k, tile, wide):
     """f16 / bf16: products are exact, the matrix unit accumulates them in f32 in its own order — every distance within the
     float tolerance of the bit-exact kernel's, the same neighbours wherever distances are separated by more than that."""
     from usearch_amd import Index
@@ -110,6 +129,7 @@ def test_tiled_exact_search_of_float_pairs_is_within_tolerance(reference, monkey
     queries = util.make_vectors(70 if tile == 64 else 300, ndim, dtype, seed=96)
     queries[:10] = vectors[:10]
     index = Index.restore(image)
+    assert_route(index, n, len(queries), k, wide)
     exact = index.search(queries, k, exact=True, dtype=dtype)
     tiled = index.search(queries, k, exact="tiled", dtype=dtype)
     assert np.array_equal(exact.counts, tiled.counts)
@@ -144,6 +164,7 @@ def test_wide_tile_thresholds_inside_the_sums_at_their_corners(reference, monkey
                               np.zeros((1, ndim))]).astype(np.float16)                          # a query of zero norm
     queries[7] = vectors[300]
     index = Index.restore(image)
+    assert_route(index, n, len(queries), k, True)
     exact = index.search(queries, k, exact=True, dtype="f16")
     tiled = index.search(queries, k, exact="tiled", dtype="f16")
     assert np.array_equal(exact.counts, tiled.counts)

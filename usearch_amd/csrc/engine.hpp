@@ -535,8 +535,8 @@ const char* exact_search_device(metric_kind_t metric, scalar_kind_t scalar, std:
                                 float* distances, std::uint64_t* counts, hipStream_t stream, float* kernel_ms,
                                 const std::uint32_t* allow_bits = nullptr);
 
-/// Is there a tiled (matrix-unit) exact-search kernel for this pair and result count? (exact_tiled.hip: cos / ip over f16 and
-/// bf16 — float tolerance — and cos / ip / l2sq over i8 — bit-identical to the wave-per-query kernel.)
+/// Is there a tiled (matrix-unit) exact-search kernel for this pair and result count? (exact_tiled.hip: cos / ip / l2sq over f16
+/// and bf16 — float tolerance — and cos / ip / l2sq over i8 — bit-identical to the wave-per-query kernel.)
 bool exact_tiled_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted);
 
 /// Many-to-many exact search as a tiled matrix product (index_plugins.hpp:2071-2164): rows are read once per 64 queries. Same

@@ -1,0 +1,93 @@
+/**
+ *  usearch_amd/csrc/exact_plan.hpp — the ONE place that chooses how a tiled exact search (exact_tiled.hip) is launched: the wide tile
+ *  (256 queries × 256 rows per workgroup) or the 64-query tile, the split of the rows into partitions, the wide kernel's deal of
+ *  (query tile, partition) pairs over its workgroups, and where the wide kernel keeps its lists. Pure integer arithmetic over plain
+ *  values: no HIP runtime call, no snapshot, no look at the environment (the caller reads USEARCH_AMD_EXACT_TILE and
+ *  USEARCH_AMD_EXACT_GLOBAL_LISTS and passes them in). tests/test_exact_plan.py pins it through `usearch_amd_test_plan_exact`.
+ */
+#pragma once
+#include <algorithm>
+#include <cstdint>
+
+namespace usearch_amd {
+
+constexpr int tile_queries_k = 64;  ///< queries per workgroup
+constexpr int tile_rows_k = 128;    ///< dataset rows per inner tile
+constexpr int chunk_bytes_k = 128;  ///< bytes of every row staged per step of the summation loop (4 MFMA steps of 32 bytes)
+constexpr int max_wanted_k = 64;    ///< per-query results the epilogue keeps (one lane per entry)
+
+constexpr int wide_queries_k = 256; ///< queries per workgroup: a row is read once per 256 queries
+constexpr int wide_rows_k = 256;    ///< dataset rows per tile: a query chunk is read once per 256 rows
+constexpr int wide_wanted_k = 16;   ///< results per query this kernel keeps (a lane per entry in the ordered insert, entries in the output arrays)
+/// Results per query up to which the lists fit LDS next to the two staging buffers (an insert is then an LDS affair of a few
+/// hundred cycles instead of a global round trip and a fence: the epilogue and, through it, the barrier shrink).
+constexpr int wide_lds_lists_k = 10;
+constexpr std::uint64_t wide_least_rows_k = 8u * 4u * wide_rows_k; ///< the wide tile wants eight partitions of four tiles at least
+
+inline std::uint64_t wide_padded_stride(std::uint64_t bytes_per_vector) {
+    return (bytes_per_vector + chunk_bytes_k - 1) / chunk_bytes_k * chunk_bytes_k;
+}
+
+/// What `plan_exact` settles. The 64-query tile runs a grid of (query tiles, partitions); the wide tile a 1-D grid of `workgroups`,
+/// each of which finds its (query tile, partition) from `query_tiles` and `tiles_per_xcd` (exact_wide_kernel).
+struct exact_plan_t {
+    std::uint32_t wide = 0;      ///< 1: the wide tile
+    std::uint32_t lds_lists = 0; ///< wide only — 1: the lists live in LDS, 0: in the output arrays
+    std::uint64_t query_tiles = 0;
+    std::uint64_t partitions = 0;
+    std::uint64_t rows_per_partition = 0;
+    std::uint64_t tiles_per_xcd = 0; ///< wide only
+    std::uint64_t workgroups = 0;    ///< wide only
+};
+
+/// `forced_tile`: USEARCH_AMD_EXACT_TILE (64 / 256 force either kernel where it can run, anything else leaves the choice here);
+/// `global_lists`: USEARCH_AMD_EXACT_GLOBAL_LISTS. → nullptr, or why the call is refused.
+inline const char* plan_exact(std::uint64_t rows, std::uint64_t bytes_per_vector, std::uint64_t row_stride, std::uint64_t count,
+                              std::uint64_t wanted, std::uint64_t forced_tile, bool global_lists, exact_plan_t& plan) {
+    plan = exact_plan_t{};
+    if (!wanted || wanted > (std::uint64_t)max_wanted_k)
+        return "No tiled exact-search kernel for this metric / scalar kind / result count";
+    if (!count)
+        return nullptr;
+    if (!rows)
+        return "Nothing to scan";
+    // The wide tile (256 queries per workgroup: a quarter of the dataset passes) takes batches that fill the chip with it; the
+    // 64-query tile keeps the small batches and the long result lists. USEARCH_AMD_EXACT_TILE=64 / 256 forces either.
+    // (a tile of 256 rows, stored or padded, must lie inside one buffer resource with 32-bit offsets: rows of < 8 MB)
+    const bool wide = forced_tile != 64 && wanted <= (std::uint64_t)wide_wanted_k && rows >= wide_least_rows_k &&
+                      (forced_tile == 256 || count > 512) && row_stride * wide_rows_k < (1ull << 31) &&
+                      wide_padded_stride(bytes_per_vector) * wide_queries_k < (1ull << 31);
+    plan.wide = wide ? 1u : 0u;
+    if (wide) {
+        // ONE round of the chip (32 compute units per XCD) with as few partitions as that takes (exact_wide_kernel)
+        const std::uint64_t query_tiles = plan.query_tiles = (count + wide_queries_k - 1) / wide_queries_k;
+        const std::uint64_t most = std::max<std::uint64_t>(1, rows / (4 * wide_rows_k)); // a partition is at least four tiles
+        if (query_tiles >= 8) { // tiles dealt over the XCDs, every XCD sees every partition
+            plan.tiles_per_xcd = (query_tiles + 7) / 8;
+            plan.partitions = std::min<std::uint64_t>(std::max<std::uint64_t>(1, 32 / plan.tiles_per_xcd), most);
+            plan.workgroups = 8 * plan.tiles_per_xcd * plan.partitions;
+        } else { // every XCD works on all the tiles, partitions ≡ xcd (mod 8)
+            plan.tiles_per_xcd = query_tiles;
+            plan.partitions = std::max<std::uint64_t>(8, 32 / query_tiles * 8);
+            while (plan.partitions > 8 && plan.partitions > most)
+                plan.partitions -= 8;
+            plan.workgroups = plan.tiles_per_xcd * plan.partitions;
+        }
+        plan.rows_per_partition = (rows + plan.partitions - 1) / plan.partitions;
+        plan.rows_per_partition = (plan.rows_per_partition + wide_rows_k - 1) / wide_rows_k * wide_rows_k;
+        plan.lds_lists = wanted <= (std::uint64_t)wide_lds_lists_k && !global_lists ? 1u : 0u;
+    } else {
+        // enough (query tile, partition) workgroups to fill the chip several times over; few enough lists per query to fold
+        const std::uint64_t query_tiles = plan.query_tiles = (count + tile_queries_k - 1) / tile_queries_k;
+        std::uint64_t partitions = std::max<std::uint64_t>(1, (2048 + query_tiles - 1) / query_tiles);
+        partitions = std::min<std::uint64_t>(partitions, std::max<std::uint64_t>(1, 8192 / wanted));
+        partitions = std::min<std::uint64_t>(partitions, std::max<std::uint64_t>(1, rows / (4 * tile_rows_k)));
+        partitions = std::min<std::uint64_t>(partitions, 65535);
+        plan.rows_per_partition = (rows + partitions - 1) / partitions;
+        plan.rows_per_partition = (plan.rows_per_partition + tile_rows_k - 1) / tile_rows_k * tile_rows_k;
+        plan.partitions = (rows + plan.rows_per_partition - 1) / plan.rows_per_partition;
+    }
+    return nullptr;
+}
+
+} // namespace usearch_amd

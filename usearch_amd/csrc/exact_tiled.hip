@@ -26,17 +26,15 @@
 #include "common.hpp"
 #include "device_scratch.hpp"
 #include "engine.hpp"
+#include "exact_plan.hpp"
 #include "host_util.hpp"
 
 namespace usearch_amd {
 
 namespace {
 
-constexpr int tile_queries_k = 64;  ///< queries per workgroup
-constexpr int tile_rows_k = 128;    ///< dataset rows per inner tile
-constexpr int chunk_bytes_k = 128;  ///< bytes of every row staged per step of the summation loop (4 MFMA steps of 32 bytes)
+// (tile_queries_k, tile_rows_k, chunk_bytes_k, max_wanted_k and the wide tile's shape: exact_plan.hpp, with the launch planner)
 constexpr int pitch_k = chunk_bytes_k + 16; ///< LDS row pitch: keeps 16-byte reads of consecutive rows off the same banks
-constexpr int max_wanted_k = 64;    ///< per-query results the epilogue keeps (one lane per entry)
 
 using f32x16_t = float __attribute__((ext_vector_type(16)));
 using i32x16_t = int __attribute__((ext_vector_type(16)));
@@ -324,22 +322,13 @@ __global__ __launch_bounds__(256) void exact_tiled_kernel(const snapshot_view_t 
 //  (`global_load_lds_dwordx4`, no staging registers, no `ds_write`) into two XOR-swizzled buffers; register epilogue
 // ---------------------------------------------------------------------------------------------------------------------
 
-constexpr int wide_queries_k = 256; ///< queries per workgroup: a row is read once per 256 queries
-constexpr int wide_rows_k = 256;    ///< dataset rows per tile: a query chunk is read once per 256 rows
 constexpr int wide_blocks_k = wide_rows_k / 32; ///< 32-row blocks of a tile = accumulators of a wave
 constexpr int wide_threads_k = 512; ///< 8 waves; wave w multiplies queries [32w, 32w + 32) with the tile's 256 rows
-constexpr int wide_wanted_k = 16;   ///< results per query this kernel keeps (a lane per entry in the ordered insert, entries in the output arrays)
 constexpr int wide_buffers_k = 2;   ///< staging buffers: one being multiplied, one being filled
 constexpr int wide_stage_rows_k = wide_queries_k + wide_rows_k;
 constexpr std::uint32_t wide_stage_bytes_k = wide_stage_rows_k * chunk_bytes_k;         ///< a buffer: [512][128] bytes, no padding
 constexpr int wide_fills_k = wide_stage_rows_k / 8 / (wide_threads_k / 64);              ///< fill instructions per wave per chunk: 8
 
-inline std::uint64_t wide_padded_stride(std::uint64_t bytes_per_vector) {
-    return (bytes_per_vector + chunk_bytes_k - 1) / chunk_bytes_k * chunk_bytes_k;
-}
-/// Results per query up to which the lists fit LDS next to the two staging buffers (an insert is then an LDS affair of a few
-/// hundred cycles instead of a global round trip and a fence: the epilogue and, through it, the barrier shrink).
-constexpr int wide_lds_lists_k = 10;
 constexpr std::uint32_t wide_lds_bytes(bool lds_lists, std::uint32_t wanted) {
     return wide_buffers_k * wide_stage_bytes_k + wide_queries_k * 4 * 5 + 2 * wide_rows_k * 4 + 2 * 512 * 4 +
            (lds_lists ? wide_queries_k * wanted * 8 : 0);
@@ -1151,25 +1140,26 @@ __global__ __launch_bounds__(256) void pad_queries_kernel(const std::uint8_t* qu
 
 template <int metric_ak, int scalar_ak>
 hipError_t launch_wide(const snapshot_view_t& view, const std::uint8_t* queries, std::uint64_t query_stride,
-                       std::uint8_t* padded, std::uint32_t query_count, std::uint32_t wanted, std::uint32_t tiles_per_xcd, std::uint32_t workgroups,
-                       std::uint64_t rows_per_partition, const std::uint32_t* row_norms, const std::uint32_t* query_norms,
+                       std::uint8_t* padded, std::uint32_t query_count, std::uint32_t wanted, const exact_plan_t& plan,
+                       const std::uint32_t* row_norms, const std::uint32_t* query_norms,
                        bool map_keys, const std::uint32_t* allow_bits, std::uint32_t* shared_bounds, float* out_distances,
                        std::uint64_t* out_keys, std::uint64_t* out_counts, hipStream_t stream) {
-    const bool lds_lists = wanted <= (std::uint32_t)wide_lds_lists_k && !env_size("USEARCH_AMD_EXACT_GLOBAL_LISTS", 0);
+    const bool lds_lists = plan.lds_lists != 0;
     auto kernel = lds_lists ? exact_wide_kernel<metric_ak, scalar_ak, true> : exact_wide_kernel<metric_ak, scalar_ak, false>;
     const std::uint32_t lds_bytes = wide_lds_bytes(lds_lists, wanted);
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)lds_bytes);
     if (e != hipSuccess)
         return e;
-    const std::uint32_t query_tiles = (query_count + wide_queries_k - 1) / wide_queries_k;
+    const std::uint32_t query_tiles = (std::uint32_t)plan.query_tiles;
     const std::uint64_t padded_stride = wide_padded_stride(view.bytes_per_vector);
     const std::uint64_t padded_rows = (std::uint64_t)query_tiles * wide_queries_k;
     hipLaunchKernelGGL(pad_queries_kernel, dim3((unsigned)std::min<std::uint64_t>((padded_rows * padded_stride + 255) / 256, 1u << 20)),
                        dim3(256), 0, stream, queries, query_stride, query_count, (std::uint32_t)view.bytes_per_vector, padded,
                        padded_stride, padded_rows);
-    hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(wide_threads_k), lds_bytes, stream, view,
-                       (const std::uint8_t*)padded, padded_stride, query_count, wanted, rows_per_partition, query_tiles, tiles_per_xcd, row_norms,
+    hipLaunchKernelGGL(kernel, dim3((std::uint32_t)plan.workgroups), dim3(wide_threads_k), lds_bytes, stream, view,
+                       (const std::uint8_t*)padded, padded_stride, query_count, wanted, plan.rows_per_partition, query_tiles,
+                       (std::uint32_t)plan.tiles_per_xcd, row_norms,
                        query_norms, map_keys ? 1u : 0u, allow_bits, shared_bounds, out_distances, out_keys, out_counts,
 #ifdef USEARCH_AMD_EXPERIMENT_EXACT_KNOCKOUT
                        (std::uint32_t)env_size("USEARCH_AMD_EXACT_KNOCKOUT", 0));
@@ -1241,44 +1231,14 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
         return nullptr;
     if (count >= none_slot_k || view.size >= none_slot_k)
         return "Batch is too large";
-    if (!view.size)
-        return "Nothing to scan";
-    // The wide tile (256 queries per workgroup: a quarter of the dataset passes) takes batches that fill the chip with it; the
-    // 64-query tile keeps the small batches and the long result lists. USEARCH_AMD_EXACT_TILE=64 / 256 forces either.
-    const std::size_t forced_tile = env_size("USEARCH_AMD_EXACT_TILE", 0);
-    // (a tile of 256 rows, stored or padded, must lie inside one buffer resource with 32-bit offsets: rows of < 8 MB)
-    const bool wide = forced_tile != 64 && wanted <= (std::size_t)wide_wanted_k && view.size >= 8u * 4u * wide_rows_k &&
-                      (forced_tile == 256 || count > 512) && (std::uint64_t)view.row_stride * wide_rows_k < (1ull << 31) &&
-                      wide_padded_stride(view.bytes_per_vector) * wide_queries_k < (1ull << 31);
-    std::uint64_t partitions, rows_per_partition, tiles_per_xcd = 0, workgroups = 0;
-    if (wide) {
-        // ONE round of the chip (32 compute units per XCD) with as few partitions as that takes (exact_wide_kernel)
-        const std::uint64_t query_tiles = (count + wide_queries_k - 1) / wide_queries_k;
-        const std::uint64_t most = std::max<std::uint64_t>(1, view.size / (4 * wide_rows_k)); // a partition is at least four tiles
-        if (query_tiles >= 8) { // tiles dealt over the XCDs, every XCD sees every partition
-            tiles_per_xcd = (query_tiles + 7) / 8;
-            partitions = std::min<std::uint64_t>(std::max<std::uint64_t>(1, 32 / tiles_per_xcd), most);
-            workgroups = 8 * tiles_per_xcd * partitions;
-        } else { // every XCD works on all the tiles, partitions ≡ xcd (mod 8)
-            tiles_per_xcd = query_tiles;
-            partitions = std::max<std::uint64_t>(8, 32 / query_tiles * 8);
-            while (partitions > 8 && partitions > most)
-                partitions -= 8;
-            workgroups = tiles_per_xcd * partitions;
-        }
-        rows_per_partition = (view.size + partitions - 1) / partitions;
-        rows_per_partition = (rows_per_partition + wide_rows_k - 1) / wide_rows_k * wide_rows_k;
-    } else {
-        // enough (query tile, partition) workgroups to fill the chip several times over; few enough lists per query to fold
-        const std::uint64_t query_tiles = (count + tile_queries_k - 1) / tile_queries_k;
-        partitions = std::max<std::uint64_t>(1, (2048 + query_tiles - 1) / query_tiles);
-        partitions = std::min<std::uint64_t>(partitions, std::max<std::uint64_t>(1, 8192 / wanted));
-        partitions = std::min<std::uint64_t>(partitions, std::max<std::uint64_t>(1, view.size / (4 * tile_rows_k)));
-        partitions = std::min<std::uint64_t>(partitions, 65535);
-        rows_per_partition = (view.size + partitions - 1) / partitions;
-        rows_per_partition = (rows_per_partition + tile_rows_k - 1) / tile_rows_k * tile_rows_k;
-        partitions = (view.size + rows_per_partition - 1) / rows_per_partition;
-    }
+    // which kernel, how many partitions, which workgroup takes which (query tile, partition): exact_plan.hpp. USEARCH_AMD_EXACT_TILE =
+    // 64 / 256 forces either kernel, USEARCH_AMD_EXACT_GLOBAL_LISTS=1 keeps the wide kernel's lists in the output arrays.
+    exact_plan_t plan;
+    if (const char* refusal = plan_exact(view.size, view.bytes_per_vector, view.row_stride, count, wanted, env_size("USEARCH_AMD_EXACT_TILE", 0),
+                                         env_size("USEARCH_AMD_EXACT_GLOBAL_LISTS", 0) != 0, plan))
+        return refusal;
+    const bool wide = plan.wide != 0;
+    const std::uint64_t partitions = plan.partitions, rows_per_partition = plan.rows_per_partition;
 
     event_pair_t events;
     device_scratch_t scratch(current_device_k); // the caller has selected the device the view lives on
@@ -1312,8 +1272,7 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
             e = launch_norms<sc>(query_bytes, count, stride_bytes, view.bytes_per_vector, query_norms, stream);        \
         if (e == hipSuccess && wide)                                                                                   \
             e = launch_wide<m, sc>(view, query_bytes, stride_bytes, padded_queries, (std::uint32_t)count,              \
-                                   (std::uint32_t)wanted, (std::uint32_t)tiles_per_xcd, (std::uint32_t)workgroups, rows_per_partition, \
-                                   row_norms, query_norms,                                                              \
+                                   (std::uint32_t)wanted, plan, row_norms, query_norms,                                 \
                                    map_keys, allow_bits, shared_bounds, partial_distances, partial_keys, partial_counts,  \
                                    stream);                                                                         \
         else if (e == hipSuccess)                                                                                      \

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "device_scratch.hpp"
+#include "exact_plan.hpp"
 #include "host_util.hpp"
 #include "kernels.hpp"
 #include "kmeans.hpp"
@@ -360,4 +361,22 @@ extern "C" __attribute__((visibility("default"))) size_t usearch_amd_test_plan_s
     if (planned)
         plan->stats.mode = (std::uint32_t)rungs[0].mode + 1, plan->stats.grid = rungs[0].grid, plan->stats.lds_bytes = rungs[0].lds_bytes;
     return planned;
+}
+
+// ---- the tiled exact search's planner (exact_plan.hpp) on plain values, for tests/test_exact_plan.py and the GPU tests that assert the
+//      route they are there for: what `exact_search_tiled_device` settles for `rows` rows of `bytes_per_vector` bytes at pitch
+//      `row_stride`, `count` queries and `wanted` results. `forced_tile` < 0 / `global_lists` < 0 = the environment, read as the engine
+//      reads it. → 1, or 0 and `error` set: the call is refused.
+extern "C" __attribute__((visibility("default"))) int usearch_amd_test_plan_exact(uint64_t rows, uint64_t bytes_per_vector, uint64_t row_stride,
+                                                                                  uint64_t count, uint64_t wanted, int64_t forced_tile,
+                                                                                  int global_lists, usearch_amd::exact_plan_t* plan,
+                                                                                  usearch_amd_error_t* error) {
+    using namespace usearch_amd;
+    const std::uint64_t tile = forced_tile < 0 ? env_size("USEARCH_AMD_EXACT_TILE", 0) : (std::uint64_t)forced_tile;
+    const bool lists = global_lists < 0 ? env_size("USEARCH_AMD_EXACT_GLOBAL_LISTS", 0) != 0 : global_lists != 0;
+    if (const char* e = plan_exact(rows, bytes_per_vector, row_stride, count, wanted, tile, lists, *plan)) {
+        fail(error, e);
+        return 0;
+    }
+    return 1;
 }

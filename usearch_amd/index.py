@@ -1253,6 +1253,9 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_plan_search.argtypes = [C.POINTER(PlanShape), C.POINTER(PlanTuning), C.c_void_p, C.c_size_t,
                                                              C.POINTER(PlanKnobs), C.POINTER(Plan), C.POINTER(PlanRung),
                                                              C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_plan_exact.restype = C.c_int
+        _test_hooks.usearch_amd_test_plan_exact.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int,
+                                                            C.POINTER(ExactPlan), C.POINTER(C.c_char_p)]
         _test_hooks.usearch_amd_test_kmeans_quantize.restype = None
         _test_hooks.usearch_amd_test_kmeans_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
@@ -1305,6 +1308,23 @@ def test_plan_search(shape: dict, tuning: dict, pending, knobs: Optional[dict] =
                                                         C.byref(plan), rungs, C.byref(err))
     _raise(err, "usearch_amd_test_plan_search")
     return plan.as_dict(), [rungs[i].as_dict() for i in range(planned)]
+
+
+# the tiled exact search's plan (csrc/exact_plan.hpp: exact_plan_t)
+ExactPlan = _struct("ExactPlan", (C.c_uint32, "wide lds_lists"), (C.c_uint64, "query_tiles partitions rows_per_partition tiles_per_xcd workgroups"))
+
+
+def test_plan_exact(rows: int, bytes_per_vector: int, row_stride: int, count: int, wanted: int, forced_tile: Optional[int] = None,
+                    global_lists: Optional[bool] = None) -> dict:
+    """The tiled exact search's planner (csrc/exact_plan.hpp) on plain values, no GPU involved: which kernel a batch of `count` queries
+    for `wanted` results over `rows` rows takes and how the rows are split. `forced_tile` / `global_lists` replace
+    USEARCH_AMD_EXACT_TILE / USEARCH_AMD_EXACT_GLOBAL_LISTS; None reads them as the engine does. → the fields of `ExactPlan` as a dict;
+    a refusal raises."""
+    plan, err = ExactPlan(), C.c_char_p()
+    test_hooks().usearch_amd_test_plan_exact(rows, bytes_per_vector, row_stride, count, wanted, -1 if forced_tile is None else int(forced_tile),
+                                             -1 if global_lists is None else int(bool(global_lists)), C.byref(plan), C.byref(err))
+    _raise(err, "usearch_amd_test_plan_exact")
+    return plan.as_dict()
 
 
 def test_kmeans_quantize(X: np.ndarray, from_dtype: str, to_dtype: str, device: int = 0) -> np.ndarray:
