@@ -356,8 +356,9 @@ USEARCH_AMD_EXPORT size_t usearch_amd_snapshot_live_keys(usearch_amd_snapshot_t 
  *  The same exact search as a TILED MATRIX PRODUCT on the matrix units (usearch_amd/csrc/exact_tiled.hip) — what the reference's
  *  `exact_search_t` does with its distance matrix (index_plugins.hpp:2071-2164): dataset rows are read once per 64 queries
  *  instead of once per query (once per 256 for batches above 512 queries). Pairs: cos / ip / l2sq over f16 and bf16 (f32 accumulation in the matrix unit: distances within the
- *  float tolerance of `usearch_amd_exact_search_many`, which remains the bit-exact path) and cos / ip / l2sq over i8
- *  (bit-identical to it, ties included); `wanted` ≤ 64. Other pairs: an error.
+ *  float tolerance of `usearch_amd_exact_search_many`, which remains the bit-exact path), cos / ip over f32 (l2sq over f32 is refused; `v_mfma_f32_32x32x2_f32`: f32
+ *  products and sums in the matrix unit's order — within a derived bound of the f64 distance, not bit-equal to the bit-exact path
+ *  and not promised within 1e-5 of it) and over i8 (bit-identical to it, ties included); `wanted` ≤ 64. Other pairs: an error.
  */
 USEARCH_AMD_EXPORT void usearch_amd_exact_search_many_tiled(usearch_amd_snapshot_t snapshot, void const* queries,
                                                             int query_kind, size_t queries_count, size_t queries_stride,
@@ -389,6 +390,22 @@ USEARCH_AMD_EXPORT void usearch_amd_exact_search_dataset(void const* dataset, si
                                                          usearch_amd_key_t* keys, size_t keys_stride,
                                                          usearch_amd_distance_t* distances, size_t distances_stride,
                                                          usearch_amd_error_t* error);
+
+/**
+ *  The same call, same arguments, as a TILED MATRIX PRODUCT over the uploaded rows (usearch_amd/csrc/exact_tiled.hip) for every
+ *  pair that has a tiled kernel — cos / ip / l2sq over f16, bf16 and i8, cos / ip over f32, `wanted` ≤ 64; any other pair is refused ("No tiled
+ *  exact-search kernel for this metric / scalar kind / result count"), never sent down the other kernel quietly. Float kinds:
+ *  every distance lies within a derived bound of the f64 distance of the row it names (f32: f32 arithmetic in the matrix unit's
+ *  summation order — NOT bit-equal to `usearch_amd_exact_search_dataset`, which stays the bit-exact path, and not promised within
+ *  1e-5 of it); i8: the same bits.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_exact_search_dataset_tiled(void const* dataset, size_t dataset_count,
+                                                               size_t dataset_stride, void const* queries,
+                                                               size_t queries_count, size_t queries_stride, int scalar_kind,
+                                                               size_t dimensions, int metric_kind, size_t wanted,
+                                                               usearch_amd_key_t* keys, size_t keys_stride,
+                                                               usearch_amd_distance_t* distances, size_t distances_stride,
+                                                               usearch_amd_error_t* error);
 
 /* ------------------------------------------------------------------------------------------------------------------
  *  Sharded search across the GPUs of one node — one process per GPU, one shard (its own HNSW) per process.

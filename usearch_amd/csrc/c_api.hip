@@ -493,6 +493,20 @@ void usearch_amd_exact_search_dataset(void const* dataset, size_t dataset_count,
     fail_from_exception(error);
 }
 
+void usearch_amd_exact_search_dataset_tiled(void const* dataset, size_t dataset_count, size_t dataset_stride,
+                                            void const* queries, size_t queries_count, size_t queries_stride,
+                                            int scalar_kind, size_t dimensions, int metric_kind, size_t wanted,
+                                            usearch_amd_key_t* keys, size_t keys_stride, usearch_amd_distance_t* distances,
+                                            size_t distances_stride, usearch_amd_error_t* error) try {
+    if (const char* e = exact_search_dataset_host(metric_from_c(metric_kind), scalar_from_c(scalar_kind), dimensions,
+                                                  dataset, dataset_count, dataset_stride, queries, queries_count,
+                                                  queries_stride, wanted, keys, keys_stride, distances,
+                                                  distances_stride, true))
+        fail(error, e);
+} catch (...) {
+    fail_from_exception(error);
+}
+
 void usearch_amd_comm_unique_id(void* out, usearch_amd_error_t* error) {
     if (const char* e = comm_t::unique_id(out))
         fail(error, e);

@@ -1432,11 +1432,13 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
                                       const void* dataset, std::size_t dataset_count, std::size_t dataset_stride,
                                       const void* queries, std::size_t queries_count, std::size_t queries_stride,
                                       std::size_t wanted, std::uint64_t* keys, std::size_t keys_stride,
-                                      float* distances, std::size_t distances_stride) {
+                                      float* distances, std::size_t distances_stride, bool tiled) {
     if (!kernel_available(metric, scalar))
         return "No MI355X kernel for this metric / scalar kind combination";
     if (!queries_count || !wanted)
         return nullptr;
+    if (tiled && !exact_tiled_available(metric, scalar, wanted)) // asked for by name: no quiet detour over the wave kernel
+        return "No tiled exact-search kernel for this metric / scalar kind / result count";
     if (dataset_count >= none_slot_k)
         return "Dataset is too large for 32-bit offsets";
     const std::size_t bpv = bytes_per_vector(scalar, dimensions);
@@ -1466,10 +1468,10 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
     view.bytes_per_vector = (std::uint32_t)bpv;
     view.dimensions = (std::uint32_t)dimensions;
     // i8: the matrix-unit kernel returns the very same bits (exact integer sums, same closing arithmetic, same tie order);
-    // the float kinds only reach it when asked (tolerance instead of bit equality)
+    // the float kinds only reach it when asked (`tiled`: a derived bound instead of bit equality)
     const char* error = nullptr;
-    if (scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
-        !env_size("USEARCH_AMD_NO_TILED_EXACT", 0))
+    if (tiled || (scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
+                  !env_size("USEARCH_AMD_NO_TILED_EXACT", 0)))
         error = exact_search_tiled_device(metric, scalar, view, d_queries, queries_count, bpv, wanted, false, d_keys, d_distances,
                                           d_counts, nullptr, nullptr);
     else

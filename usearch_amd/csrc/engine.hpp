@@ -536,7 +536,8 @@ const char* exact_search_device(metric_kind_t metric, scalar_kind_t scalar, std:
                                 const std::uint32_t* allow_bits = nullptr);
 
 /// Is there a tiled (matrix-unit) exact-search kernel for this pair and result count? (exact_tiled.hip: cos / ip / l2sq over f16
-/// and bf16 — float tolerance — and cos / ip / l2sq over i8 — bit-identical to the wave-per-query kernel.)
+/// and bf16 — float tolerance —, cos / ip over f32 — a derived bound, not bit equality; l2sq over f32 stays refused — and over i8 — bit-identical to the wave-per-query
+/// kernel. The table itself: `exact_tiled_pair` of exact_plan.hpp.)
 bool exact_tiled_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted);
 
 /// Many-to-many exact search as a tiled matrix product (index_plugins.hpp:2071-2164): rows are read once per 64 queries. Same
@@ -547,11 +548,13 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
                                       hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits = nullptr);
 
 /// Host-buffer exact search of a raw dataset — `usearch_exact_search` (c/usearch.h:467-474): keys are dataset offsets.
+/// `tiled`: the matrix-unit kernel over the uploaded rows for any pair that has one (`exact_tiled_available`; refused otherwise)
+/// instead of the bit-exact wave-per-query one, which stays what the float kinds get unasked.
 const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar, std::size_t dimensions,
                                       const void* dataset, std::size_t dataset_count, std::size_t dataset_stride,
                                       const void* queries, std::size_t queries_count, std::size_t queries_stride,
                                       std::size_t wanted, std::uint64_t* keys, std::size_t keys_stride,
-                                      float* distances, std::size_t distances_stride);
+                                      float* distances, std::size_t distances_stride, bool tiled = false);
 
 /// Lanes per stored row, the row pitch and the 16-byte chunks the kernels read of a row of `bytes` bytes (the summation layout
 /// of DESIGN.md §3.3; the pitch may exceed chunks × 16 so that short rows never straddle a 128-byte line).

@@ -4,10 +4,13 @@
  *  (query tile, partition) pairs over its workgroups, and where the wide kernel keeps its lists. Pure integer arithmetic over plain
  *  values: no HIP runtime call, no snapshot, no look at the environment (the caller reads USEARCH_AMD_EXACT_TILE and
  *  USEARCH_AMD_EXACT_GLOBAL_LISTS and passes them in). tests/test_exact_plan.py pins it through `usearch_amd_test_plan_exact`.
+ *  The table of pairs that have a tiled kernel at all (`exact_tiled_pair`) lives here too, for the same reason: checkable without a GPU.
  */
 #pragma once
 #include <algorithm>
 #include <cstdint>
+
+#include "common.hpp"
 
 namespace usearch_amd {
 
@@ -26,6 +29,24 @@ constexpr std::uint64_t wide_least_rows_k = 8u * 4u * wide_rows_k; ///< the wide
 
 inline std::uint64_t wide_padded_stride(std::uint64_t bytes_per_vector) {
     return (bytes_per_vector + chunk_bytes_k - 1) / chunk_bytes_k * chunk_bytes_k;
+}
+
+/// Which (metric, scalar kind) pairs have a tiled kernel, and for how many results per query: cos, ip and l2sq over f16, bf16 and
+/// i8, cos and ip over f32, 1 … `max_wanted_k` results. Both kernels are instantiated for every pair here — which of them runs is
+/// a matter of the batch's shape (`plan_exact`), never of the kind. tests/test_exact_tiled_pairs.py pins it through
+/// `usearch_amd_test_exact_tiled_pair`.
+/// l2sq over f32 is NOT here, on purpose: that `exact="tiled"` over an l2sq f32 index is refused is behaviour the suite pins
+/// (tests/test_gpu_exact.py: "no matrix-unit kernel for this pair: said so, not silently rerouted"), and giving the pair a kernel
+/// changes it. Nothing in the kernels stands in the way — l2sq closes through the float branch every kind shares — so it is this
+/// row and three instantiations, in a change that also moves that assertion to a pair that stays without a kernel.
+inline bool exact_tiled_pair(metric_kind_t metric, scalar_kind_t scalar, std::uint64_t wanted) {
+    if (!wanted || wanted > (std::uint64_t)max_wanted_k)
+        return false;
+    if (scalar == scalar_f32_k)
+        return metric == metric_cos_k || metric == metric_ip_k;
+    if (scalar != scalar_f16_k && scalar != scalar_bf16_k && scalar != scalar_i8_k)
+        return false;
+    return metric == metric_cos_k || metric == metric_ip_k || metric == metric_l2sq_k;
 }
 
 /// What `plan_exact` settles. The 64-query tile runs a grid of (query tiles, partitions); the wide tile a 1-D grid of `workgroups`,

@@ -5,18 +5,26 @@
  *  matrix, then a partial sort per query) and `index_gt::search_exact_` (index.hpp:4252-4268) are the one place on this path
  *  where operands ARE reused — every query meets every row — so unlike the graph walk this is a GEMM: a workgroup owns a tile
  *  of 64 queries and streams its share of the dataset through in tiles of 128 rows, rows are read once per 64 queries instead
- *  of once per query, the products run on `v_mfma_f32_32x32x16_{f16,bf16}` / `v_mfma_i32_32x32x32_i8`, and the per-query
- *  top-k is folded in the epilogue of every tile (a candidate survives only if it beats the query's current k-th best).
+ *  of once per query, the products run on `v_mfma_f32_32x32x16_{f16,bf16}` / `v_mfma_i32_32x32x32_i8` /
+ *  `v_mfma_f32_32x32x2_f32`, and the per-query top-k is folded in the epilogue of every tile (a candidate survives only if it
+ *  beats the query's current k-th best).
  *
- *  Pairs: cos, ip and l2sq over f16 / bf16 (f32 accumulation inside the matrix unit: results within the float tolerance of the
- *  wave-per-query kernel of kernels.hpp, which stays THE bit-exact path), and ip / cos / l2sq over i8 (exact int32 sums and
- *  the same closing arithmetic as `finalize_distance`: bit-identical to that kernel, ties included — selection is the total
- *  order (distance ↑, slot ↓) that `search_exact_`'s lower_bound inserts produce).
+ *  Pairs (the table is `exact_tiled_pair` of exact_plan.hpp; every pair is instantiated on BOTH kernels, the 64-query tile and
+ *  the wide 256 × 256 tile — the planner chooses by shape, not by kind): cos, ip and l2sq over f16 / bf16 (f32 accumulation
+ *  inside the matrix unit: results within the float tolerance of the wave-per-query kernel of kernels.hpp, which stays THE
+ *  bit-exact path), over i8 (exact int32 sums and the same closing arithmetic as `finalize_distance`: bit-identical to that
+ *  kernel, ties included — selection is the total order (distance ↑, slot ↓) that `search_exact_`'s lower_bound inserts
+ *  produce), and cos and ip over f32 — l2sq over f32 stays refused, see `exact_tiled_pair` — (f32 products AND sums: an fmaf chain in the matrix unit's order, one rounding per product — every
+ *  distance within a derived bound of its row's f64 distance, tests/exact_truth_f32.py; NOT bit-equal to the wave kernel and
+ *  not promised within 1e-5 of it — opt-in, the wave kernel stays what `exact=True` runs). Row shapes: any number of bytes; a
+ *  stored row is zero padded to whole 16-byte pieces, a query row need not be (32-d f32 = 128 B is one staged chunk, 33-d =
+ *  132 B leaves one scalar alone in the second, 50-d = 200 B half fills a 16-byte piece).
  *
  *  Both operands are row-major with the summation index contiguous, and the A and B fragments of these MFMA shapes use the
  *  same (lane half, element) → k assignment, so every lane simply loads 16 consecutive bytes of "its" query row and of "its"
- *  dataset row: no transposition anywhere. C/D: column (dataset row) = lane & 31, row (query) = (reg & 3) + 8·(reg >> 2) +
- *  4·(lane >> 5).
+ *  dataset row: no transposition anywhere. f32: those 16 bytes are four scalars and each feeds one 32x32x2 step — lanes 0 … 31
+ *  carry k = e, lanes 32 … 63 k = 4 + e, for A and B alike — so the sum is right as it is; only the order of its terms is the
+ *  kernel's own. C/D: column (dataset row) = lane & 31, row (query) = (reg & 3) + 8·(reg >> 2) + 4·(lane >> 5).
  */
 #include <hip/hip_runtime.h>
 
@@ -41,6 +49,7 @@ using i32x16_t = int __attribute__((ext_vector_type(16)));
 using f16x8_t = _Float16 __attribute__((ext_vector_type(8)));
 using bf16x8_t = __bf16 __attribute__((ext_vector_type(8)));
 using i32x4_t = int __attribute__((ext_vector_type(4)));
+using f32x4_t = float __attribute__((ext_vector_type(4)));
 
 template <int scalar_ak> struct accumulator_gt {
     using type = f32x16_t;
@@ -56,7 +65,16 @@ __device__ __forceinline__ typename accumulator_gt<scalar_ak>::type multiply(uin
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
     else if constexpr (scalar_ak == scalar_bf16_k)
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    else
+    else if constexpr (scalar_ak == scalar_f32_k) {
+        // the lane's 16 bytes are four scalars, each one step of `v_mfma_f32_32x32x2_f32` (lanes 0 … 31: k = e, lanes 32 … 63:
+        // k = 4 + e, for A and B alike) chained on the one accumulator: an fmaf chain in k order, one rounding per product. The
+        // dependent latency of the instruction equals its issue interval: the chain costs what four independent ones would.
+        const f32x4_t x = __builtin_bit_cast(f32x4_t, a), y = __builtin_bit_cast(f32x4_t, b);
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(x[0], y[0], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(x[1], y[1], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(x[2], y[2], c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x2f32(x[3], y[3], c, 0, 0, 0);
+    } else
         return __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4_t, a), __builtin_bit_cast(i32x4_t, b), c, 0, 0, 0);
 }
 
@@ -70,10 +88,19 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const std::uint8_t* rows
         const std::uint8_t* p = rows + row * stride;
         float sum = 0.f;
         int exact = 0;
-        for (std::uint32_t b = lane * 2; b < bytes; b += 128) {
+        // bytes a lane takes per round: one f32, one 16-bit scalar, or two i8. `bytes` is what the row holds, whatever its pitch
+        // (a query row is not padded to 16 bytes, and a caller's batch need not be aligned to more than its scalars)
+        constexpr std::uint32_t width = scalar_ak == scalar_f32_k ? 4 : 2;
+        for (std::uint32_t b = lane * width; b < bytes; b += 64 * width) {
             if constexpr (scalar_ak == scalar_i8_k) {
                 const int x = (std::int8_t)p[b], y = b + 1 < bytes ? (std::int8_t)p[b + 1] : 0;
                 exact += x * x + y * y;
+            } else if constexpr (scalar_ak == scalar_f32_k) {
+                const float x = (std::uintptr_t)(p + b) % 4 == 0
+                                    ? *reinterpret_cast<const float*>(p + b)
+                                    : __builtin_bit_cast(float, (std::uint32_t)p[b] | ((std::uint32_t)p[b + 1] << 8) |
+                                                                    ((std::uint32_t)p[b + 2] << 16) | ((std::uint32_t)p[b + 3] << 24));
+                sum = __builtin_fmaf(x, x, sum);
             } else {
                 const std::uint32_t bits = (std::uint32_t)p[b] | ((std::uint32_t)p[b + 1] << 8);
                 const float x = scalar_ak == scalar_bf16_k ? __builtin_bit_cast(float, bits << 16)
@@ -1210,13 +1237,7 @@ hipError_t launch_norms(const std::uint8_t* rows, std::uint64_t count, std::uint
 } // namespace
 
 bool exact_tiled_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted) {
-    if (!wanted || wanted > (std::size_t)max_wanted_k)
-        return false;
-    if (scalar == scalar_f16_k || scalar == scalar_bf16_k)
-        return metric == metric_cos_k || metric == metric_ip_k || metric == metric_l2sq_k;
-    if (scalar == scalar_i8_k)
-        return metric == metric_cos_k || metric == metric_ip_k || metric == metric_l2sq_k;
-    return false;
+    return exact_tiled_pair(metric, scalar, wanted); // the table: exact_plan.hpp
 }
 
 const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar, const snapshot_view_t& view,
@@ -1289,6 +1310,8 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
     UA_TILED(metric_cos_k, scalar_i8_k)
     UA_TILED(metric_ip_k, scalar_i8_k)
     UA_TILED(metric_l2sq_k, scalar_i8_k)
+    UA_TILED(metric_cos_k, scalar_f32_k)
+    UA_TILED(metric_ip_k, scalar_f32_k)
 #undef UA_TILED
     if (e != hipSuccess)
         return hip_message(e);

@@ -380,3 +380,10 @@ extern "C" __attribute__((visibility("default"))) int usearch_amd_test_plan_exac
     }
     return 1;
 }
+
+// ---- which (metric, scalar kind, result count) has a tiled exact-search kernel at all (`exact_tiled_pair` of exact_plan.hpp, what
+//      `exact_tiled_available` answers with), for tests/test_exact_tiled_pairs.py. `metric` / `scalar`: metric_kind_t / scalar_kind_t of
+//      common.hpp. → 1 or 0.
+extern "C" __attribute__((visibility("default"))) int usearch_amd_test_exact_tiled_pair(int metric, int scalar, uint64_t wanted) {
+    return usearch_amd::exact_tiled_pair((usearch_amd::metric_kind_t)metric, (usearch_amd::scalar_kind_t)scalar, wanted) ? 1 : 0;
+}

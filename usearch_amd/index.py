@@ -162,7 +162,7 @@ EXPORTED_SYMBOLS = [
     "usearch_amd_search_many_device", "usearch_amd_last_peaks", "usearch_amd_distances",
     "usearch_amd_last_distances_ms", "usearch_amd_merge_many", "usearch_amd_merge_many_device",
     "usearch_amd_exact_search_many", "usearch_amd_exact_search_many_tiled", "usearch_amd_exact_search_dataset",
-    "usearch_amd_exact_search_many_device",
+    "usearch_amd_exact_search_many_device", "usearch_amd_exact_search_dataset_tiled",
     "usearch_amd_cluster_many",
     "usearch_amd_clustering", "usearch_amd_clustering_members", "usearch_amd_snapshot_live_keys",
     "usearch_amd_filter_from_key_range", "usearch_amd_filter_from_keys", "usearch_amd_filter_from_bits",
@@ -275,6 +275,7 @@ def library() -> C.CDLL:
     L.usearch_amd_exact_search_dataset.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
                                                    C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p,
                                                    C.c_size_t, C.c_void_p, C.c_size_t, err_p]
+    L.usearch_amd_exact_search_dataset_tiled.argtypes = L.usearch_amd_exact_search_dataset.argtypes
     L.usearch_amd_filter_from_key_range.restype = C.c_void_p
     L.usearch_amd_filter_from_key_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, err_p]
     L.usearch_amd_filter_from_keys.restype = C.c_void_p
@@ -739,7 +740,7 @@ class Index:
             return batch[0] if single else batch
         if exact:  # brute force over every stored vector (Index.search(..., exact=True), index.py:700-748)
             kernel_ms = C.c_float()
-            # exact="tiled": the matrix-unit kernel (f16 / bf16 cos, ip within float tolerance; i8 bit-identical)
+            # exact="tiled": the matrix-unit kernel (f16 / bf16 within float tolerance; f32 within a derived bound; i8 bit-identical)
             entry = (library().usearch_amd_exact_search_many_tiled if exact == "tiled"
                      else library().usearch_amd_exact_search_many)
             entry(self._handle, _pointer(vectors), SCALAR_KINDS[dtype], q,
@@ -1090,9 +1091,12 @@ def build(vectors, metric: str = "cos", dtype: Optional[str] = None, *, keys: Op
 
 
 def exact_search(dataset: np.ndarray, queries: np.ndarray, count: int, metric: str = "cos",
-                 dtype: Optional[str] = None):
+                 dtype: Optional[str] = None, tiled: bool = False):
     """`usearch.index.search(dataset, queries, count, exact=True)` (index.py:1608-1700) → (keys = row offsets [Q, k],
-    distances [Q, k]); both matrices in the same scalar kind, rows may be strided."""
+    distances [Q, k]); both matrices in the same scalar kind, rows may be strided. `tiled`: the matrix-unit kernel
+    (csrc/exact_tiled.hip) over the uploaded rows — cos / ip / l2sq over f16, bf16 and i8, cos / ip over f32, count ≤ 64, any
+    other pair is refused; float distances then lie within a derived bound of the f64 distance instead of being the wave kernel's bits (f32:
+    not promised within 1e-5 of them). The default stays the bit-exact wave-per-query kernel."""
     dataset, queries = np.asarray(dataset), np.asarray(queries)
     if dtype is None:
         dtype = _infer_dtype(dataset)
@@ -1101,11 +1105,11 @@ def exact_search(dataset: np.ndarray, queries: np.ndarray, count: int, metric: s
     keys = np.zeros((len(queries), count), dtype=np.uint64)
     distances = np.zeros((len(queries), count), dtype=np.float32)
     err = C.c_char_p()
-    library().usearch_amd_exact_search_dataset(_pointer(dataset), len(dataset), dataset.strides[0], _pointer(queries),
-                                               len(queries), queries.strides[0], SCALAR_KINDS[dtype], ndim,
-                                               metric_kind, count, _pointer(keys), keys.strides[0],
-                                               _pointer(distances), distances.strides[0], C.byref(err))
-    _raise(err, "usearch_amd_exact_search_dataset")
+    entry = "usearch_amd_exact_search_dataset_tiled" if tiled else "usearch_amd_exact_search_dataset"
+    getattr(library(), entry)(_pointer(dataset), len(dataset), dataset.strides[0], _pointer(queries), len(queries),
+                              queries.strides[0], SCALAR_KINDS[dtype], ndim, metric_kind, count, _pointer(keys), keys.strides[0],
+                              _pointer(distances), distances.strides[0], C.byref(err))
+    _raise(err, entry)
     return keys, distances
 
 
@@ -1256,6 +1260,8 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_plan_exact.restype = C.c_int
         _test_hooks.usearch_amd_test_plan_exact.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int,
                                                             C.POINTER(ExactPlan), C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_exact_tiled_pair.restype = C.c_int
+        _test_hooks.usearch_amd_test_exact_tiled_pair.argtypes = [C.c_int, C.c_int, C.c_uint64]
         _test_hooks.usearch_amd_test_kmeans_quantize.restype = None
         _test_hooks.usearch_amd_test_kmeans_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
@@ -1325,6 +1331,15 @@ def test_plan_exact(rows: int, bytes_per_vector: int, row_stride: int, count: in
                                              -1 if global_lists is None else int(bool(global_lists)), C.byref(plan), C.byref(err))
     _raise(err, "usearch_amd_test_plan_exact")
     return plan.as_dict()
+
+
+def test_exact_tiled_pair(metric: str, dtype: str, wanted: int) -> bool:
+    """Is there a tiled (matrix-unit) exact-search kernel for `metric` over `dtype` rows and `wanted` results per query? The table of
+    csrc/exact_plan.hpp (`exact_tiled_pair`) that `exact="tiled"` and `exact_search(…, tiled=True)` are refused by; no GPU involved."""
+    metric_kind = ord({"ip": "i", "cos": "c", "l2sq": "e", "hamming": "b", "pearson": "p", "haversine": "h", "divergence": "d",
+                       "jaccard": "j", "tanimoto": "t", "sorensen": "s"}[metric])  # metric_kind_t and scalar_kind_t of csrc/common.hpp
+    scalar_kind = {"b1": 1, "bf16": 4, "f64": 10, "f32": 11, "f16": 12, "i8": 23}[dtype]
+    return bool(test_hooks().usearch_amd_test_exact_tiled_pair(metric_kind, scalar_kind, wanted))
 
 
 def test_kmeans_quantize(X: np.ndarray, from_dtype: str, to_dtype: str, device: int = 0) -> np.ndarray:
