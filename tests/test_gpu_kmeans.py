@@ -63,6 +63,39 @@ def test_assign_i8_is_exact_and_ties_go_to_the_lower_index(metric, ndim):
             assert got_index[point] == low
 
 
+@functools.lru_cache(maxsize=None)
+def shared_tile_case(ndim: int, dtype: str):
+    """197 points and 300 centroids in `dtype`: the integers −60 … 60 of the test above for i8; for the 16-bit kinds the same
+    integers plus a fraction, so that products and partial sums round and the order of the summation shows in the bits."""
+    rng = np.random.default_rng(ndim)
+    X, centroids = rng.integers(-60, 61, (COUNT, ndim)), rng.integers(-60, 61, (300, ndim))
+    if dtype == "i8":
+        return X.astype(np.int8), centroids.astype(np.int8)
+    X, centroids = (X + rng.random(X.shape)) / 8.0, (centroids + rng.random(centroids.shape)) / 8.0
+    narrow = util.to_bf16 if dtype == "bf16" else (lambda a: a.astype(np.float16))
+    return narrow(X), narrow(centroids)
+
+
+@pytest.mark.parametrize("ndim", [33, 96])
+@pytest.mark.parametrize("metric", ["l2sq", "ip", "cos"])
+@pytest.mark.parametrize("dtype", ["i8", "f16", "bf16"])
+def test_assignment_and_exact_search_close_the_same_distance(dtype, metric, ndim):
+    """The assignment kernel and the 64-query tile of exact search multiply, take Σx² and close through the same code
+    (csrc/device_math.hpp): a point's distance to its nearest centroid has the same float bits either way — i8 also on the
+    wave-per-query kernel, whose bits the integer sums carry. Distances only: among equal ones k-means keeps the lower index, exact
+    search the later slot. (f16 / bf16: same products in the same order; the bits were equal before the code was shared, too.)"""
+    X, centroids = shared_tile_case(ndim, dtype)
+    _, assigned = usearch_amd.kmeans_assign(X, centroids, metric=metric, dtype=dtype)
+    assert np.isfinite(assigned).all()
+    routes = [True, False] if dtype == "i8" else [True]
+    for tiled in routes:
+        _, nearest = usearch_amd.exact_search(centroids, X, 1, metric=metric, dtype=dtype, tiled=tiled)
+        differing = assigned.view(np.uint32) != nearest[:, 0].view(np.uint32)
+        print(f"{dtype} {metric} {ndim} tiled={tiled}: {int(differing.sum())} of {COUNT} distances differ in their bits, "
+              f"max |difference| {np.abs(assigned.astype(np.float64) - nearest[:, 0]).max():.3g}")
+        assert not differing.any()
+
+
 def test_assign_all_nan_distances_end_at_index_zero():
     """A NaN never wins; a point whose distances are all NaN keeps index 0 and FLT_MAX (index_plugins.hpp:2366-2375)."""
     X = blob_case(40, 5)[0].copy()

@@ -17,15 +17,18 @@
 #include <cstdint>
 #include <cstring>
 
+#include <hip/hip_runtime.h>
+
 #include "common.hpp"
 
 namespace usearch_amd {
 
-inline float f16_bits_to_f32(std::uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-inline std::uint16_t f32_to_f16_bits(float f) { return __builtin_bit_cast(std::uint16_t, (_Float16)f); }
-inline float bf16_bits_to_f32(std::uint16_t h) { return __builtin_bit_cast(float, (std::uint32_t)h << 16); }
+// (the four 16-bit conversions serve the device too: the cast and update kernels of kmeans.hip must give the host's bits)
+__host__ __device__ inline float f16_bits_to_f32(std::uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+__host__ __device__ inline std::uint16_t f32_to_f16_bits(float f) { return __builtin_bit_cast(std::uint16_t, (_Float16)f); }
+__host__ __device__ inline float bf16_bits_to_f32(std::uint16_t h) { return __builtin_bit_cast(float, (std::uint32_t)h << 16); }
 /// bf16_bits_t(float) of index_plugins.hpp:430-470 truncates (keeps the upper 16 bits) — no rounding.
-inline std::uint16_t f32_to_bf16_bits(float f) { return (std::uint16_t)(__builtin_bit_cast(std::uint32_t, f) >> 16); }
+__host__ __device__ inline std::uint16_t f32_to_bf16_bits(float f) { return (std::uint16_t)(__builtin_bit_cast(std::uint32_t, f) >> 16); }
 
 inline double load_scalar(scalar_kind_t kind, const std::uint8_t* p, std::size_t i) {
     switch (kind) {

@@ -26,6 +26,7 @@
 #include <mutex>
 
 #include "casts.hpp"
+#include "device_math.hpp"
 #include "device_scratch.hpp"
 #include "engine.hpp"
 #include "host_util.hpp"
@@ -193,9 +194,7 @@ __global__ __launch_bounds__(256) void clustering_merge_kernel(const std::uint8_
     for (u32 p = threadIdx.x; p < candidates; p += 256) {
         const float d = distance[p];
         if (d < FLT_MAX) {
-            const u32 bits = __float_as_uint(d + 0.f); // −0 → +0: they compare equal
-            const u32 ordered = bits & 0x80000000u ? ~bits : bits | 0x80000000u;
-            const u64 cell = ((u64)ordered << 32) | p;
+            const u64 cell = ((u64)ordered_bits(d + 0.f) << 32) | p; // (+ 0.f: −0 → +0, they compare equal)
             best = cell < best ? cell : best;
         }
     }

@@ -11,12 +11,12 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "device_math.hpp" // chunk_bytes_k: the staged tile is the kernels', the planner pads query rows to it
 
 namespace usearch_amd {
 
 constexpr int tile_queries_k = 64;  ///< queries per workgroup
 constexpr int tile_rows_k = 128;    ///< dataset rows per inner tile
-constexpr int chunk_bytes_k = 128;  ///< bytes of every row staged per step of the summation loop (4 MFMA steps of 32 bytes)
 constexpr int max_wanted_k = 64;    ///< per-query results the epilogue keeps (one lane per entry)
 
 constexpr int wide_queries_k = 256; ///< queries per workgroup: a row is read once per 256 queries

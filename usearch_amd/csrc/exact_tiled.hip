@@ -20,11 +20,9 @@
  *  stored row is zero padded to whole 16-byte pieces, a query row need not be (32-d f32 = 128 B is one staged chunk, 33-d =
  *  132 B leaves one scalar alone in the second, 50-d = 200 B half fills a 16-byte piece).
  *
- *  Both operands are row-major with the summation index contiguous, and the A and B fragments of these MFMA shapes use the
- *  same (lane half, element) → k assignment, so every lane simply loads 16 consecutive bytes of "its" query row and of "its"
- *  dataset row: no transposition anywhere. f32: those 16 bytes are four scalars and each feeds one 32x32x2 step — lanes 0 … 31
- *  carry k = e, lanes 32 … 63 k = 4 + e, for A and B alike — so the sum is right as it is; only the order of its terms is the
- *  kernel's own. C/D: column (dataset row) = lane & 31, row (query) = (reg & 3) + 8·(reg >> 2) + 4·(lane >> 5).
+ *  The matrix-unit product and the fragment geometry (which lane holds which bytes of an operand row, which accumulator register
+ *  which (query, row) of a block), Σx² of the rows, the closing arithmetic and the ordered bits of a bound are device_math.hpp's,
+ *  shared with the k-means assignment (kmeans.hip): what is here is the staging, the pipelines and the folds.
  */
 #include <hip/hip_runtime.h>
 
@@ -32,6 +30,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "device_math.hpp"
 #include "device_scratch.hpp"
 #include "engine.hpp"
 #include "exact_plan.hpp"
@@ -41,112 +40,12 @@ namespace usearch_amd {
 
 namespace {
 
-// (tile_queries_k, tile_rows_k, chunk_bytes_k, max_wanted_k and the wide tile's shape: exact_plan.hpp, with the launch planner)
-constexpr int pitch_k = chunk_bytes_k + 16; ///< LDS row pitch: keeps 16-byte reads of consecutive rows off the same banks
+// (tile_queries_k, tile_rows_k, max_wanted_k and the wide tile's shape: exact_plan.hpp, with the launch planner)
 
-using f32x16_t = float __attribute__((ext_vector_type(16)));
-using i32x16_t = int __attribute__((ext_vector_type(16)));
-using f16x8_t = _Float16 __attribute__((ext_vector_type(8)));
-using bf16x8_t = __bf16 __attribute__((ext_vector_type(8)));
-using i32x4_t = int __attribute__((ext_vector_type(4)));
-using f32x4_t = float __attribute__((ext_vector_type(4)));
-
-template <int scalar_ak> struct accumulator_gt {
-    using type = f32x16_t;
-};
-template <> struct accumulator_gt<scalar_i8_k> {
-    using type = i32x16_t;
-};
-
-template <int scalar_ak>
-__device__ __forceinline__ typename accumulator_gt<scalar_ak>::type multiply(uint4 a, uint4 b,
-                                                                             typename accumulator_gt<scalar_ak>::type c) {
-    if constexpr (scalar_ak == scalar_f16_k)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    else if constexpr (scalar_ak == scalar_bf16_k)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    else if constexpr (scalar_ak == scalar_f32_k) {
-        // the lane's 16 bytes are four scalars, each one step of `v_mfma_f32_32x32x2_f32` (lanes 0 … 31: k = e, lanes 32 … 63:
-        // k = 4 + e, for A and B alike) chained on the one accumulator: an fmaf chain in k order, one rounding per product. The
-        // dependent latency of the instruction equals its issue interval: the chain costs what four independent ones would.
-        const f32x4_t x = __builtin_bit_cast(f32x4_t, a), y = __builtin_bit_cast(f32x4_t, b);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(x[0], y[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(x[1], y[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(x[2], y[2], c, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_32x32x2f32(x[3], y[3], c, 0, 0, 0);
-    } else
-        return __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4_t, a), __builtin_bit_cast(i32x4_t, b), c, 0, 0, 0);
-}
-
-/// Σx² of every row, as the closing arithmetic wants it: f32 for the float kinds, exact int32 for i8 (stored as bits).
-template <int scalar_ak>
-__global__ __launch_bounds__(256) void row_norms_kernel(const std::uint8_t* rows, std::uint64_t count, std::uint64_t stride,
-                                                        std::uint32_t bytes, std::uint32_t* out) {
-    // one wave per row, grid-stride: a launch may not exceed 2^32 threads, and 100M rows × 64 lanes would
-    const std::uint32_t lane = threadIdx.x % 64;
-    for (std::uint64_t row = blockIdx.x * 4ull + threadIdx.x / 64; row < count; row += (std::uint64_t)gridDim.x * 4) {
-        const std::uint8_t* p = rows + row * stride;
-        float sum = 0.f;
-        int exact = 0;
-        // bytes a lane takes per round: one f32, one 16-bit scalar, or two i8. `bytes` is what the row holds, whatever its pitch
-        // (a query row is not padded to 16 bytes, and a caller's batch need not be aligned to more than its scalars)
-        constexpr std::uint32_t width = scalar_ak == scalar_f32_k ? 4 : 2;
-        for (std::uint32_t b = lane * width; b < bytes; b += 64 * width) {
-            if constexpr (scalar_ak == scalar_i8_k) {
-                const int x = (std::int8_t)p[b], y = b + 1 < bytes ? (std::int8_t)p[b + 1] : 0;
-                exact += x * x + y * y;
-            } else if constexpr (scalar_ak == scalar_f32_k) {
-                const float x = (std::uintptr_t)(p + b) % 4 == 0
-                                    ? *reinterpret_cast<const float*>(p + b)
-                                    : __builtin_bit_cast(float, (std::uint32_t)p[b] | ((std::uint32_t)p[b + 1] << 8) |
-                                                                    ((std::uint32_t)p[b + 2] << 16) | ((std::uint32_t)p[b + 3] << 24));
-                sum = __builtin_fmaf(x, x, sum);
-            } else {
-                const std::uint32_t bits = (std::uint32_t)p[b] | ((std::uint32_t)p[b + 1] << 8);
-                const float x = scalar_ak == scalar_bf16_k ? __builtin_bit_cast(float, bits << 16)
-                                                           : (float)__builtin_bit_cast(_Float16, (std::uint16_t)bits);
-                sum = __builtin_fmaf(x, x, sum);
-            }
-        }
-#pragma unroll
-        for (int offset = 32; offset >= 1; offset >>= 1) {
-            sum += __shfl_xor(sum, offset, 64);
-            exact += __shfl_xor(exact, offset, 64);
-        }
-        if (lane == 0)
-            out[row] = scalar_ak == scalar_i8_k ? (std::uint32_t)exact : __builtin_bit_cast(std::uint32_t, sum);
-    }
-}
-
-/// The metric's closing arithmetic from the matrix unit's sum Σab and the two stored Σx² (bits of an f32, or an exact int32 for
-/// i8) — the same expressions as `finalize_distance` of kernels.hpp.
+/// Both tiles close with the clamp that turns a NaN into 0 (device_math.hpp has the reasons).
 template <int metric_ak, int scalar_ak, typename sum_at>
-__device__ __forceinline__ float closing_distance(sum_at sum, std::uint32_t a2_bits, std::uint32_t b2_bits) {
-    if constexpr (scalar_ak == scalar_i8_k) {
-        const int ab = sum, a2 = (int)a2_bits, b2 = (int)b2_bits;
-        if constexpr (metric_ak == metric_cos_k) { // metric_cos_i8_t, index_plugins.hpp:1583-1607
-            const float a2f = __builtin_sqrtf((float)a2), b2f = __builtin_sqrtf((float)b2);
-            return ab != 0 ? 1.f - (float)ab / (a2f * b2f) : 0.f;
-        } else if constexpr (metric_ak == metric_ip_k) {
-            return 1.f - (float)ab;
-        } else { // metric_l2sq_i8_t 1613-1630
-            return (float)(a2 + b2 - 2 * ab);
-        }
-    } else {
-        const float ab = sum, a2 = __builtin_bit_cast(float, a2_bits), b2 = __builtin_bit_cast(float, b2_bits);
-        if constexpr (metric_ak == metric_cos_k) { // metric_cos_gt, index_plugins.hpp:1334-1359
-            if (a2 == 0.f && b2 == 0.f)
-                return 0.f;
-            if (a2 == 0.f || b2 == 0.f)
-                return 1.f;
-            return 1.f - ab / (__builtin_sqrtf(a2) * __builtin_sqrtf(b2));
-        } else if constexpr (metric_ak == metric_l2sq_k) { // Σ(a−b)² (index_plugins.hpp:1365-1385) as Σa² + Σb² − 2Σab, never below 0
-            const float d = a2 + b2 - 2.f * ab;
-            return d > 0.f ? d : 0.f;
-        } else {
-            return 1.f - ab;
-        }
-    }
+__device__ __forceinline__ float tile_distance(sum_at sum, std::uint32_t a2_bits, std::uint32_t b2_bits) {
+    return closing_distance<metric_ak, scalar_ak, l2sq_nan_to_zero_k>(sum, a2_bits, b2_bits);
 }
 
 /// 1/√Σx² for the conservative bound of the wide kernel's epilogue; NaN (= "take the exact path") when the norm is zero or so
@@ -178,10 +77,7 @@ __global__ __launch_bounds__(256) void exact_tiled_kernel(const snapshot_view_t 
     std::uint8_t* stage_q = lds;                                      // [64][pitch]
     std::uint8_t* stage_r = stage_q + tile_queries_k * pitch_k;       // [128][pitch]
     float* tile_d = reinterpret_cast<float*>(lds);                    // [64][129], aliases the staging area after the products
-    constexpr std::uint32_t staging_bytes = (tile_queries_k + tile_rows_k) * pitch_k;
-    constexpr std::uint32_t tile_bytes = tile_queries_k * (tile_rows_k + 1) * 4;
-    constexpr std::uint32_t shared_bytes = staging_bytes > tile_bytes ? staging_bytes : tile_bytes;
-    float* top_d = reinterpret_cast<float*>(lds + shared_bytes);      // [64][max_wanted_k]
+    float* top_d = reinterpret_cast<float*>(lds + staged_tile_bytes(tile_queries_k, tile_rows_k)); // [64][max_wanted_k]
     std::uint32_t* top_s = reinterpret_cast<std::uint32_t*>(top_d + tile_queries_k * max_wanted_k);
     std::uint32_t* top_n = top_s + tile_queries_k * max_wanted_k;      // [64]
     std::uint32_t* norms_q = top_n + tile_queries_k;                   // [64]
@@ -248,17 +144,7 @@ __global__ __launch_bounds__(256) void exact_tiled_kernel(const snapshot_view_t 
                 }
             }
             __syncthreads();
-            // ---- four steps of 32 bytes: lane half h of every fragment owns bytes [32·step + 16h, +16) of its row
-#pragma unroll
-            for (std::uint32_t step = 0; step < chunk_bytes_k / 32; ++step) {
-                const std::uint32_t offset = step * 32 + (lane >> 5) * 16;
-                const uint4 b = *reinterpret_cast<const uint4*>(stage_r + (wave * 32 + (lane & 31)) * pitch_k + offset);
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const uint4 a = *reinterpret_cast<const uint4*>(stage_q + (t * 32 + (lane & 31)) * pitch_k + offset);
-                    acc[t] = multiply<scalar_ak>(a, b, acc[t]);
-                }
-            }
+            multiply_staged_chunk<scalar_ak>(stage_q, stage_r, wave, lane, acc);
             __syncthreads();
         }
 
@@ -267,9 +153,9 @@ __global__ __launch_bounds__(256) void exact_tiled_kernel(const snapshot_view_t 
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const std::uint32_t i = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const std::uint32_t j = wave * 32 + (lane & 31);
-                const float distance = closing_distance<metric_ak, scalar_ak>(acc[t][r], norms_q[i], norms_r[j]);
+                const std::uint32_t i = t * 32 + accumulator_row(r, lane);
+                const std::uint32_t j = wave * 32 + accumulator_column(lane);
+                const float distance = tile_distance<metric_ak, scalar_ak>(acc[t][r], norms_q[i], norms_r[j]);
                 tile_d[i * (tile_rows_k + 1) + j] = valid_r[j] ? distance : __builtin_inff();
             }
         }
@@ -359,16 +245,6 @@ constexpr int wide_fills_k = wide_stage_rows_k / 8 / (wide_threads_k / 64);     
 constexpr std::uint32_t wide_lds_bytes(bool lds_lists, std::uint32_t wanted) {
     return wide_buffers_k * wide_stage_bytes_k + wide_queries_k * 4 * 5 + 2 * wide_rows_k * 4 + 2 * 512 * 4 +
            (lds_lists ? wide_queries_k * wanted * 8 : 0);
-}
-
-/// A float as an unsigned integer of the same order (negative distances exist: 1 − Σab), so that `atomicMin` keeps the smallest.
-__device__ __forceinline__ std::uint32_t ordered_bits(float x) {
-    const std::uint32_t bits = __builtin_bit_cast(std::uint32_t, x);
-    return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-/// All ones ("nothing published yet") decode to a NaN.
-__device__ __forceinline__ float from_ordered_bits(std::uint32_t ordered) {
-    return __builtin_bit_cast(float, ordered ^ ((ordered >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
 
 /// Where the 16-byte piece `piece` of staged row `row` sits inside the row's 128 bytes. A `ds_read_b128` is served in groups of 16
@@ -484,14 +360,14 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
     }
     __syncthreads();
 
-    // ---- per lane: the 16 queries its accumulator registers belong to (register r ↔ query 32·wave + (r&3) + 8(r>>2) + 4(lane>>5))
+    // ---- per lane: the 16 queries its accumulator registers belong to (register r ↔ query 32·wave + accumulator_row(r, lane))
     std::uint32_t exists = 0;   // bit r: that query is inside the batch
     std::uint32_t query_norm[16];
     float bound[16];            // the query's shared bound as of the last tile head (+inf: nobody has k results yet)
     float threshold[16];        // cos: (1 − bound − 10⁻⁵)·√Σa², what Σab·rsq(Σb²) has to reach; +inf for a query outside the batch
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const std::uint32_t i = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const std::uint32_t i = wave * 32 + accumulator_row(r, lane);
         const bool inside = first_query + i < query_count;
         exists |= (inside ? 1u : 0u) << r;
         query_norm[r] = norms_q[i];
@@ -841,7 +717,7 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
             if (!(knock & 8u) || work_tile == 0)
                 refresh_thresholds(shared, own, roots);
         }
-        const std::uint32_t tile_norms = lds_base + (std::uint32_t)((std::uint8_t*)(norms_r + (work_tile & 1u) * wide_rows_k + (lane_here & 31)) - lds);
+        const std::uint32_t tile_norms = lds_base + (std::uint32_t)((std::uint8_t*)(norms_r + (work_tile & 1u) * wide_rows_k + accumulator_column(lane_here)) - lds);
         std::uint32_t tile_b2[wide_blocks_k];
         asm volatile("ds_read_b32 %0, %8\n\t"
                      "ds_read_b32 %1, %8 offset:128\n\t"
@@ -860,7 +736,7 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
         for (int u = 0; u < wide_blocks_k; ++u) {
             if (knock & 16u)
                 continue;
-            const std::uint64_t my_row = tile_row + u * 32 + (lane & 31);
+            const std::uint64_t my_row = tile_row + u * 32 + accumulator_column(lane);
             bool live = my_row < last_row;
             if (check_members) {
                 if (ix.has_tombstones && live)
@@ -874,7 +750,7 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
             //      compares "may"). One multiply and one compare per sum; the compares' lane masks are ORed on the scalar unit.
             auto may_enter = [&](int r) -> bool {
                 if constexpr (metric_ak == metric_l2sq_k)
-                    return closing_distance<metric_ak, scalar_ak>(acc[u][r], query_norm[r], b2) <= bound[r];
+                    return tile_distance<metric_ak, scalar_ak>(acc[u][r], query_norm[r], b2) <= bound[r];
                 else if constexpr (metric_ak == metric_ip_k)
                     return 1.f - (float)acc[u][r] <= bound[r];
                 else // cos: 1 − Σab/(√Σa²·√Σb²) ≤ bound + 10⁻⁵; an integer Σab = 0 closes to 0 whatever the norms
@@ -913,15 +789,15 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
                 while (pending) {
                     const std::uint32_t source = (std::uint32_t)__ffsll((long long)pending) - 1;
                     pending &= pending - 1;
-                    const std::uint32_t i = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (source >> 5);
-                    const std::uint32_t s = (std::uint32_t)(tile_row + u * 32 + (source & 31));
+                    const std::uint32_t i = wave * 32 + accumulator_row(r, source);
+                    const std::uint32_t s = (std::uint32_t)(tile_row + u * 32 + accumulator_column(source));
                     sum_t sum = 0;
 #pragma unroll
                     for (int rr = 0; rr < 16; ++rr) // the register index is a loop variable: select, then broadcast
                         sum = rr == r ? acc[u][rr] : sum;
                     sum = __shfl(sum, (int)source, 64);
                     const std::uint32_t source_b2 = (std::uint32_t)__shfl((int)b2, (int)source, 64);
-                    const float d = closing_distance<metric_ak, scalar_ak>(sum, lds_read(norms_q + i), source_b2);
+                    const float d = tile_distance<metric_ak, scalar_ak>(sum, lds_read(norms_q + i), source_b2);
                     offer(i, s, d);
                 }
             }
@@ -987,7 +863,7 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
         const u32x4_t query_operand = {((std::uint32_t)__builtin_bit_cast(std::uint16_t, threshold16) ^ 0x8000u) & low_half, 0u, 0u, 0u};
         std::uint32_t tile_b2[wide_blocks_k] = {};
         if constexpr (metric_ak == metric_cos_k) {
-            const std::uint32_t tile_norms = lds_base + (std::uint32_t)((std::uint8_t*)(norms_r + (work_tile & 1u) * wide_rows_k + (lane_here & 31)) - lds);
+            const std::uint32_t tile_norms = lds_base + (std::uint32_t)((std::uint8_t*)(norms_r + (work_tile & 1u) * wide_rows_k + accumulator_column(lane_here)) - lds);
             asm volatile("ds_read_b32 %0, %8\n\t"
                          "ds_read_b32 %1, %8 offset:128\n\t"
                          "ds_read_b32 %2, %8 offset:256\n\t"
@@ -1022,8 +898,8 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
         const std::uint32_t rows_here = last_row - tile_row < wide_rows_k ? (std::uint32_t)(last_row - tile_row) : (std::uint32_t)wide_rows_k;
 #pragma unroll
         for (int u = 0; u < wide_blocks_k; ++u) {
-            const std::uint64_t my_row = tile_row + u * 32 + (lane_here & 31);
-            bool live = u * 32 + (lane_here & 31) < rows_here;
+            const std::uint64_t my_row = tile_row + u * 32 + accumulator_column(lane_here);
+            bool live = u * 32 + accumulator_column(lane_here) < rows_here;
             if (check_members) {
                 if (ix.has_tombstones && live)
                     live = ix.keys[my_row] != free_key_k;
@@ -1054,7 +930,7 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
 #pragma unroll
                 for (int rr = 1; rr < 16; ++rr)
                     sum = r == (std::uint32_t)rr ? acc[u][rr] : sum;
-                const std::uint32_t i = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane_here >> 5);
+                const std::uint32_t i = wave * 32 + accumulator_row(r, lane_here);
                 std::uint32_t put_in_bits, norm_bits, limit_bits;
                 asm volatile("ds_read_b32 %0, %3\n\t"
                              "ds_read_b32 %1, %4\n\t"
@@ -1064,12 +940,12 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
                              : "v"(lds_address(folded + i)), "v"(lds_address(norms_q + i)), "v"(lds_address(limit + i))
                              : "memory");
                 sum = __builtin_fmaf(__builtin_bit_cast(float, put_in_bits), put_in_row[u], sum); // Σab again
-                const float d = closing_distance<metric_ak, scalar_ak>(sum, norm_bits, tile_b2[u]);
+                const float d = tile_distance<metric_ak, scalar_ak>(sum, norm_bits, tile_b2[u]);
                 std::uint64_t pending = __ballot(candidate && !(d > __builtin_bit_cast(float, limit_bits)));
                 while (pending) {
                     const std::uint32_t source = (std::uint32_t)__ffsll((long long)pending) - 1;
                     pending &= pending - 1;
-                    offer((std::uint32_t)__shfl((int)i, (int)source, 64), (std::uint32_t)(tile_row + u * 32 + (source & 31)),
+                    offer((std::uint32_t)__shfl((int)i, (int)source, 64), (std::uint32_t)(tile_row + u * 32 + accumulator_column(source)),
                           __shfl(d, (int)source, 64));
                 }
             }
@@ -1197,9 +1073,7 @@ hipError_t launch_wide(const snapshot_view_t& view, const std::uint8_t* queries,
 }
 
 constexpr std::uint32_t tiled_lds_bytes() {
-    constexpr std::uint32_t staging = (tile_queries_k + tile_rows_k) * pitch_k;
-    constexpr std::uint32_t tile = tile_queries_k * (tile_rows_k + 1) * 4;
-    return (staging > tile ? staging : tile) + tile_queries_k * max_wanted_k * 8 + tile_queries_k * 4 + tile_queries_k * 4 +
+    return staged_tile_bytes(tile_queries_k, tile_rows_k) + tile_queries_k * max_wanted_k * 8 + tile_queries_k * 4 + tile_queries_k * 4 +
            tile_rows_k * 4 + tile_rows_k * 4;
 }
 
@@ -1224,15 +1098,7 @@ hipError_t launch_tiled(const snapshot_view_t& view, const std::uint8_t* queries
     return hipGetLastError();
 }
 
-template <int scalar_ak>
-hipError_t launch_norms(const std::uint8_t* rows, std::uint64_t count, std::uint64_t stride, std::uint32_t bytes,
-                        std::uint32_t* out, hipStream_t stream) {
-    if (!count)
-        return hipSuccess;
-    hipLaunchKernelGGL(row_norms_kernel<scalar_ak>, dim3((unsigned)std::min<std::uint64_t>((count + 3) / 4, 1u << 20)), dim3(256), 0,
-                       stream, rows, count, stride, bytes, out);
-    return hipGetLastError();
-}
+constexpr std::uint32_t norms_blocks_k = 1u << 20; ///< the grid of the Σx² launches at most
 
 } // namespace
 
@@ -1288,9 +1154,11 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
     hipError_t e = hipSuccess;
 #define UA_TILED(m, sc)                                                                                                 \
     if (e == hipSuccess && metric == m && scalar == sc) {                                                              \
-        e = launch_norms<sc>(view.vectors, view.size, view.row_stride, view.bytes_per_vector, row_norms, stream);      \
+        e = launch_row_norms<sc>(view.vectors, view.size, view.row_stride, view.bytes_per_vector, row_norms,        \
+                                  norms_blocks_k, stream);                                                             \
         if (e == hipSuccess)                                                                                           \
-            e = launch_norms<sc>(query_bytes, count, stride_bytes, view.bytes_per_vector, query_norms, stream);        \
+            e = launch_row_norms<sc>(query_bytes, count, stride_bytes, view.bytes_per_vector, query_norms,          \
+                                      norms_blocks_k, stream);                                                         \
         if (e == hipSuccess && wide)                                                                                   \
             e = launch_wide<m, sc>(view, query_bytes, stride_bytes, padded_queries, (std::uint32_t)count,              \
                                    (std::uint32_t)wanted, plan, row_norms, query_norms,                                 \

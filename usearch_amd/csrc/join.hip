@@ -21,6 +21,7 @@
 #include <map>
 #include <mutex>
 
+#include "device_math.hpp" // ordered_bits: the unsigned order of the result = the float order of d (negative ip distances included)
 #include "device_scratch.hpp"
 #include "host_util.hpp"
 
@@ -35,15 +36,6 @@ constexpr std::uint64_t exact_width_limit_k = 4096;         ///< `exact_search_d
 
 enum : unsigned { touched_k = 0, lazy_k = 1, next_free_k = 2, counters_k = 4 };
 enum : unsigned { proposals_k = 0, engagements_k = 1, sum_visited_k = 2, sum_computed_k = 3, totals_k = 4 };
-
-/// Unsigned order of the result = float order of `d` (negative distances of `ip` included).
-__device__ inline std::uint32_t ordered_bits(float d) {
-    const std::uint32_t u = __builtin_bit_cast(std::uint32_t, d);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float from_ordered_bits(std::uint32_t o) {
-    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
 
 /// Appends `value` for every lane with `take` to `list`: one atomic per wave (ballot + rank among the taking lanes). Every lane of
 /// the wave must reach it. Returns the lane's position in `list` (meaningless where `take` is false).

@@ -24,9 +24,9 @@
  *    cast         rows of the caller's kind → quantised rows, zero padded to 16 bytes (`cast_vector`'s bits; the i8 magnitude is an
  *                 f64 sum in ascending dimension order, one lane per row);
  *    assignment   f16 / bf16 / i8: a tile of 64 points × 128 centroids per step on `v_mfma_f32_32x32x16_{f16,bf16}` /
- *                 `v_mfma_i32_32x32x32_i8`, fragment layout as documented at the top of exact_tiled.hip (A and B fragments take
- *                 16 consecutive bytes of "their" row; C/D: column = lane & 31, row = (reg & 3) + 8·(reg >> 2) + 4·(lane >> 5)),
- *                 Σx² and the closing arithmetic of that file, so i8 distances are bit-identical to the wave kernel's. The
+ *                 `v_mfma_i32_32x32x32_i8`. The product of a staged chunk, the fragment layout, Σx² and the closing arithmetic
+ *                 are device_math.hpp's — the very code the 64-query tile of exact search (exact_tiled.hip) runs, so the two close
+ *                 a pair to the same bits (tests/test_gpu_kmeans.py) and i8 distances are bit-identical to the wave kernel's. The
  *                 epilogue keeps ONE (distance, index) per point under (distance ↑, centroid index ↑). The centroids (k · row
  *                 bytes, a few MB) stay in L2; the points are read from HBM once per iteration.
  *                 f32: a plain wave per point (f32 FMAs over 64 lanes, shuffle reduction), within the f32 tolerance.
@@ -51,6 +51,7 @@
 
 #include "casts.hpp"
 #include "common.hpp"
+#include "device_math.hpp"
 #include "device_scratch.hpp"
 #include "host_util.hpp"
 #include "kmeans.hpp"
@@ -61,50 +62,20 @@ namespace {
 
 constexpr int tile_points_k = 64;     ///< points per workgroup
 constexpr int tile_centroids_k = 128; ///< centroids per inner tile
-constexpr int chunk_bytes_k = 128;    ///< bytes of every row staged per step of the summation loop (4 MFMA steps of 32 bytes)
-constexpr int pitch_k = chunk_bytes_k + 16; ///< LDS row pitch: keeps 16-byte reads of consecutive rows off the same banks
 constexpr float float_max_k = 3.402823466e+38f;
-
-using f32x16_t = float __attribute__((ext_vector_type(16)));
-using i32x16_t = int __attribute__((ext_vector_type(16)));
-using f16x8_t = _Float16 __attribute__((ext_vector_type(8)));
-using bf16x8_t = __bf16 __attribute__((ext_vector_type(8)));
-using i32x4_t = int __attribute__((ext_vector_type(4)));
-
-template <int scalar_ak> struct accumulator_gt {
-    using type = f32x16_t;
-};
-template <> struct accumulator_gt<scalar_i8_k> {
-    using type = i32x16_t;
-};
-
-template <int scalar_ak>
-__device__ __forceinline__ typename accumulator_gt<scalar_ak>::type multiply(uint4 a, uint4 b,
-                                                                             typename accumulator_gt<scalar_ak>::type c) {
-    if constexpr (scalar_ak == scalar_f16_k)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    else if constexpr (scalar_ak == scalar_bf16_k)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4_t, a), __builtin_bit_cast(i32x4_t, b), c, 0, 0, 0);
-}
+constexpr std::uint32_t norms_blocks_k = 65536; ///< the grid of the Σx² launches at most
 
 // ---------------------------------------------------------------------------------------------------------------------
-//  Scalars
+//  Scalars (the four 16-bit conversions are casts.hpp's own, for host and device)
 // ---------------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ float f16_bits_to_float(std::uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ std::uint16_t float_to_f16_bits(float f) { return __builtin_bit_cast(std::uint16_t, (_Float16)f); }
-__device__ __forceinline__ float bf16_bits_to_float(std::uint16_t h) { return __builtin_bit_cast(float, (std::uint32_t)h << 16); }
-__device__ __forceinline__ std::uint16_t float_to_bf16_bits(float f) { return (std::uint16_t)(__builtin_bit_cast(std::uint32_t, f) >> 16); }
-
-/// `load_scalar` of casts.hpp.
+/// `load_scalar` of casts.hpp, with aligned loads.
 __device__ __forceinline__ double load_scalar_device(int kind, const std::uint8_t* p, std::uint32_t i) {
     switch (kind) {
     case scalar_f64_k: return reinterpret_cast<const double*>(p)[i];
     case scalar_f32_k: return reinterpret_cast<const float*>(p)[i];
-    case scalar_f16_k: return f16_bits_to_float(reinterpret_cast<const std::uint16_t*>(p)[i]);
-    case scalar_bf16_k: return bf16_bits_to_float(reinterpret_cast<const std::uint16_t*>(p)[i]);
+    case scalar_f16_k: return f16_bits_to_f32(reinterpret_cast<const std::uint16_t*>(p)[i]);
+    case scalar_bf16_k: return bf16_bits_to_f32(reinterpret_cast<const std::uint16_t*>(p)[i]);
     case scalar_i8_k: return (double)(std::int8_t)p[i];
     default: return 0;
     }
@@ -114,8 +85,8 @@ __device__ __forceinline__ double load_scalar_device(int kind, const std::uint8_
 __device__ __forceinline__ void store_scalar_device(int kind, std::uint8_t* p, std::uint32_t i, float as_float) {
     switch (kind) {
     case scalar_f32_k: reinterpret_cast<float*>(p)[i] = as_float; break;
-    case scalar_f16_k: reinterpret_cast<std::uint16_t*>(p)[i] = float_to_f16_bits(as_float); break;
-    case scalar_bf16_k: reinterpret_cast<std::uint16_t*>(p)[i] = float_to_bf16_bits(as_float); break;
+    case scalar_f16_k: reinterpret_cast<std::uint16_t*>(p)[i] = f32_to_f16_bits(as_float); break;
+    case scalar_bf16_k: reinterpret_cast<std::uint16_t*>(p)[i] = f32_to_bf16_bits(as_float); break;
     default: break;
     }
 }
@@ -125,9 +96,9 @@ template <int scalar_ak> __device__ __forceinline__ double decompress(const std:
     if constexpr (scalar_ak == scalar_i8_k)
         return (double)(std::int8_t)row[i] / 127.f;
     else if constexpr (scalar_ak == scalar_f16_k)
-        return f16_bits_to_float(reinterpret_cast<const std::uint16_t*>(row)[i]);
+        return f16_bits_to_f32(reinterpret_cast<const std::uint16_t*>(row)[i]);
     else if constexpr (scalar_ak == scalar_bf16_k)
-        return bf16_bits_to_float(reinterpret_cast<const std::uint16_t*>(row)[i]);
+        return bf16_bits_to_f32(reinterpret_cast<const std::uint16_t*>(row)[i]);
     else
         return reinterpret_cast<const float*>(row)[i];
 }
@@ -152,9 +123,9 @@ __global__ __launch_bounds__(256) void cast_elements_kernel(const std::uint8_t* 
             if (to == scalar_f32_k)
                 value = (float)x / 127.f;
             else if (to == scalar_f16_k) // f16_t(int) then a float division, rounded back to f16
-                value = f16_bits_to_float(float_to_f16_bits((float)x)) / 127.f;
+                value = f16_bits_to_f32(f32_to_f16_bits((float)x)) / 127.f;
             else
-                value = bf16_bits_to_float(float_to_bf16_bits((float)x)) / 127.f;
+                value = bf16_bits_to_f32(f32_to_bf16_bits((float)x)) / 127.f;
             store_scalar_device(to, target, i, value);
         } else {
             store_scalar_device(to, target, i, (float)load_scalar_device(from, source, i));
@@ -200,68 +171,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const std::uint8_t* so
 //  Assignment
 // ---------------------------------------------------------------------------------------------------------------------
 
-/// Σx² of every row, as the closing arithmetic wants it: f32 for the float kinds, exact int32 for i8 (stored as bits) — the
-/// `row_norms_kernel` of exact_tiled.hip.
-template <int scalar_ak>
-__global__ __launch_bounds__(256) void row_norms_kernel(const std::uint8_t* rows, std::uint64_t count, std::uint64_t stride,
-                                                        std::uint32_t bytes, std::uint32_t* out) {
-    const std::uint32_t lane = threadIdx.x % 64;
-    for (std::uint64_t row = blockIdx.x * 4ull + threadIdx.x / 64; row < count; row += (std::uint64_t)gridDim.x * 4) {
-        const std::uint8_t* p = rows + row * stride;
-        float sum = 0.f;
-        int exact = 0;
-        for (std::uint32_t b = lane * 2; b < bytes; b += 128) {
-            if constexpr (scalar_ak == scalar_i8_k) {
-                const int x = (std::int8_t)p[b], y = b + 1 < bytes ? (std::int8_t)p[b + 1] : 0;
-                exact += x * x + y * y;
-            } else {
-                const std::uint32_t bits = (std::uint32_t)p[b] | ((std::uint32_t)p[b + 1] << 8);
-                const float x = scalar_ak == scalar_bf16_k ? __builtin_bit_cast(float, bits << 16)
-                                                           : (float)__builtin_bit_cast(_Float16, (std::uint16_t)bits);
-                sum = __builtin_fmaf(x, x, sum);
-            }
-        }
-#pragma unroll
-        for (int offset = 32; offset >= 1; offset >>= 1) {
-            sum += __shfl_xor(sum, offset, 64);
-            exact += __shfl_xor(exact, offset, 64);
-        }
-        if (lane == 0)
-            out[row] = scalar_ak == scalar_i8_k ? (std::uint32_t)exact : __builtin_bit_cast(std::uint32_t, sum);
-    }
-}
-
-/// The metric's closing arithmetic from the matrix unit's sum Σab and the two stored Σx² — the expressions of
-/// `closing_distance` in exact_tiled.hip (= `finalize_distance` of kernels.hpp).
-template <int metric_ak, int scalar_ak, typename sum_at>
-__device__ __forceinline__ float closing_distance(sum_at sum, std::uint32_t a2_bits, std::uint32_t b2_bits) {
-    if constexpr (scalar_ak == scalar_i8_k) {
-        const int ab = sum, a2 = (int)a2_bits, b2 = (int)b2_bits;
-        if constexpr (metric_ak == metric_cos_k) { // metric_cos_i8_t, index_plugins.hpp:1583-1607, incl. `ab == 0 → 0`
-            const float a2f = __builtin_sqrtf((float)a2), b2f = __builtin_sqrtf((float)b2);
-            return ab != 0 ? 1.f - (float)ab / (a2f * b2f) : 0.f;
-        } else if constexpr (metric_ak == metric_ip_k) {
-            return 1.f - (float)ab;
-        } else { // metric_l2sq_i8_t 1613-1630
-            return (float)(a2 + b2 - 2 * ab);
-        }
-    } else {
-        const float ab = sum, a2 = __builtin_bit_cast(float, a2_bits), b2 = __builtin_bit_cast(float, b2_bits);
-        if constexpr (metric_ak == metric_cos_k) { // metric_cos_gt, index_plugins.hpp:1334-1359
-            if (a2 == 0.f && b2 == 0.f)
-                return 0.f;
-            if (a2 == 0.f || b2 == 0.f)
-                return 1.f;
-            return 1.f - ab / (__builtin_sqrtf(a2) * __builtin_sqrtf(b2));
-        } else if constexpr (metric_ak == metric_l2sq_k) { // Σ(a−b)² as Σa² + Σb² − 2Σab, never below 0
-            const float d = a2 + b2 - 2.f * ab;
-            return d < 0.f ? 0.f : d; // (a NaN stays a NaN: it must never win)
-        } else {
-            return 1.f - ab;
-        }
-    }
-}
-
 /// What every assignment kernel ends in for its point: the new index and distance, and whether the index moved.
 __device__ __forceinline__ void publish_assignment(std::uint32_t point, bool inside, std::uint32_t index, float distance,
                                                    std::uint32_t* assignments, float* distances, std::uint32_t* shifted,
@@ -287,10 +196,7 @@ __global__ __launch_bounds__(256) void assign_tiled_kernel(const std::uint8_t* p
                                                            const std::uint32_t* point_norms, const std::uint32_t* centroid_norms,
                                                            std::uint32_t* assignments, float* distances, std::uint32_t* shifted) {
     using accumulator_t = typename accumulator_gt<scalar_ak>::type;
-    constexpr std::uint32_t staging_bytes = (tile_points_k + tile_centroids_k) * pitch_k;
-    constexpr std::uint32_t tile_bytes = tile_points_k * (tile_centroids_k + 1) * 4;
-    constexpr std::uint32_t shared_bytes = staging_bytes > tile_bytes ? staging_bytes : tile_bytes;
-    __shared__ __attribute__((aligned(16))) std::uint8_t lds[shared_bytes];
+    __shared__ __attribute__((aligned(16))) std::uint8_t lds[staged_tile_bytes(tile_points_k, tile_centroids_k)];
     __shared__ float part_d[4][tile_points_k];         // the best of every quarter of a centroid tile, per point
     __shared__ std::uint32_t part_i[4][tile_points_k];
     __shared__ std::uint32_t norms_p[tile_points_k];
@@ -360,17 +266,7 @@ __global__ __launch_bounds__(256) void assign_tiled_kernel(const std::uint8_t* p
                 fetch(tile, chunk + 1);
             else if (tile + tile_centroids_k < clusters)
                 fetch(tile + tile_centroids_k, 0);
-            // ---- four steps of 32 bytes: lane half h of every fragment owns bytes [32·step + 16h, +16) of its row
-#pragma unroll
-            for (std::uint32_t step = 0; step < chunk_bytes_k / 32; ++step) {
-                const std::uint32_t offset = step * 32 + (lane >> 5) * 16;
-                const uint4 b = *reinterpret_cast<const uint4*>(stage_c + (wave * 32 + (lane & 31)) * pitch_k + offset);
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const uint4 a = *reinterpret_cast<const uint4*>(stage_p + (t * 32 + (lane & 31)) * pitch_k + offset);
-                    acc[t] = multiply<scalar_ak>(a, b, acc[t]);
-                }
-            }
+            multiply_staged_chunk<scalar_ak>(stage_p, stage_c, wave, lane, acc);
             __syncthreads();
         }
 
@@ -379,9 +275,10 @@ __global__ __launch_bounds__(256) void assign_tiled_kernel(const std::uint8_t* p
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const std::uint32_t i = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const std::uint32_t j = wave * 32 + (lane & 31);
-                const float distance = closing_distance<metric_ak, scalar_ak>(acc[t][r], norms_p[i], norms_c[j]);
+                const std::uint32_t i = t * 32 + accumulator_row(r, lane);
+                const std::uint32_t j = wave * 32 + accumulator_column(lane);
+                // (l2sq over floats: a NaN stays a NaN — it must never win the scan below; device_math.hpp)
+                const float distance = closing_distance<metric_ak, scalar_ak, l2sq_nan_stays_k>(acc[t][r], norms_p[i], norms_c[j]);
                 tile_d[i * (tile_centroids_k + 1) + j] = tile + j < clusters ? distance : __builtin_inff();
             }
         }
@@ -718,14 +615,12 @@ const char* quantize_rows(const std::uint8_t* rows, std::size_t count, std::size
 
 const char* launch_norms(scalar_kind_t quantization, const std::uint8_t* rows, std::size_t count, std::size_t stride, std::uint32_t bytes,
                          std::uint32_t* norms) {
-    const std::uint32_t grid = grid_for(count, 4);
     if (quantization == scalar_f16_k)
-        row_norms_kernel<scalar_f16_k><<<grid, 256>>>(rows, count, stride, bytes, norms);
+        UA_HIP(launch_row_norms<scalar_f16_k>(rows, count, stride, bytes, norms, norms_blocks_k, nullptr));
     else if (quantization == scalar_bf16_k)
-        row_norms_kernel<scalar_bf16_k><<<grid, 256>>>(rows, count, stride, bytes, norms);
+        UA_HIP(launch_row_norms<scalar_bf16_k>(rows, count, stride, bytes, norms, norms_blocks_k, nullptr));
     else if (quantization == scalar_i8_k)
-        row_norms_kernel<scalar_i8_k><<<grid, 256>>>(rows, count, stride, bytes, norms);
-    UA_HIP(hipGetLastError());
+        UA_HIP(launch_row_norms<scalar_i8_k>(rows, count, stride, bytes, norms, norms_blocks_k, nullptr));
     return nullptr;
 }
 
