@@ -77,6 +77,12 @@ def lib() -> C.CDLL:
         L.uo_cluster_many.argtypes = [C.POINTER(_Index), C.c_void_p, C.c_uint8, C.c_size_t, C.c_size_t, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.uo_set_frontier_in_top.argtypes = [C.c_int]
+        L.uo_trace_hops.argtypes = [C.c_uint32]
+        L.uo_trace_size.restype = C.c_size_t
+        L.uo_trace_copy.restype = C.c_size_t
+        L.uo_trace_copy.argtypes = [C.c_void_p, C.c_size_t]
+        L.uo_sum_of_squares.restype = C.c_float
+        L.uo_sum_of_squares.argtypes = [C.c_uint8, C.c_void_p, C.c_uint64, C.c_int]
         L.uo_merge_into.restype = C.c_size_t
         L.uo_merge_into.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                     C.c_size_t]
@@ -157,6 +163,32 @@ class OracleIndex:
                 lib().uo_set_frontier_in_top(0)
         return keys, dists, counts, visited, computed
 
+    def search_traced(self, queries: np.ndarray, k: int, dtype: Optional[str] = None, expansion: int = 64, lanes: int = 0,
+                      frontier_in_top: bool = False, tile_cells: int = 64):
+        """`search` with the hop trace on (`uo_trace_hops`) → (the five arrays of `search`, traces): traces[q] is the list of query
+        q's level-0 segments in walk order, each (top was full, radius, first segment of its hop, fresh slots uint32[] in list order)."""
+        queries = np.ascontiguousarray(queries)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        L = lib()
+        L.uo_trace_hops(tile_cells)  # (this thread's trace: the search below runs on this thread)
+        try:
+            found = self.search(queries, k, dtype=dtype, expansion=expansion, lanes=lanes, frontier_in_top=frontier_in_top)
+            words = np.zeros(L.uo_trace_size(), dtype=np.uint32)
+            assert L.uo_trace_copy(_ptr(words), len(words)) == len(words)
+        finally:
+            L.uo_trace_hops(0)
+        traces, at = [], 0
+        while at < len(words):
+            flags, count = int(words[at]), int(words[at + 2])
+            if flags & 4:
+                traces.append([])
+            traces[-1].append((bool(flags & 1), float(words[at + 1:at + 2].view(np.float32)[0]), bool(flags & 2),
+                               words[at + 3:at + 3 + count].copy()))
+            at += 3 + count
+        assert len(traces) == len(queries), "one level-0 walk per query"
+        return found, traces
+
     def cluster(self, queries: np.ndarray, level: int, dtype: Optional[str] = None, lanes: int = 0):
         """`index_dense_gt::cluster(query, level)` for a batch → (keys[Q], distances[Q], visited[Q], computed[Q])."""
         dtype = dtype or self.dtype
@@ -192,6 +224,12 @@ def distance(a: np.ndarray, b: np.ndarray, metric: str, dtype: str, ndim: int, l
     a = np.ascontiguousarray(a)
     b = np.ascontiguousarray(b)
     return float(lib().uo_distance(METRIC[metric], SCALAR[dtype], _ptr(a), _ptr(b), ndim, lanes))
+
+
+def sum_of_squares(a: np.ndarray, dtype: str, ndim: int, lanes: int = 0) -> np.float32:
+    """Σa² in f32 arithmetic in the summation layout of `lanes` lanes per row: what a kernel holds for its query."""
+    a = np.ascontiguousarray(a)
+    return np.float32(lib().uo_sum_of_squares(SCALAR[dtype], _ptr(a), ndim, lanes))
 
 
 def cast(vector: np.ndarray, from_dtype: str, to_dtype: str, ndim: int) -> Optional[np.ndarray]:

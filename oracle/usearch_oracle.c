@@ -392,6 +392,12 @@ float uo_distance(uint8_t metric_kind, uint8_t scalar_kind, const void* av, cons
     }
 }
 
+/* Σa² of one vector as the f32 kernels hold it for a query: the A2 chain of the sums above, in the layout of `lanes`. */
+float uo_sum_of_squares(uint8_t scalar_kind, const void* av, uint64_t dims, int lanes) {
+    f32_acc_t s = f32_sums(scalar_kind, (const uint8_t*)av, (const uint8_t*)av, dims, lanes, 0);
+    return s.sum[UO_A2];
+}
+
 /* ------------------------------------------------------------------------------------------------------------------
  *  Casts (index_plugins.hpp:1105-1224)
  * ---------------------------------------------------------------------------------------------------------------- */
@@ -640,6 +646,48 @@ static uint32_t search_for_one(ctx_t* c, uint32_t closest, int begin_level, int 
     return closest;
 }
 
+/* Optional trace of the level-0 hops on this thread (tests of the device's sketch: which candidates a hop found fresh, and the
+ * state the device tests them against). Off by default; it records, it changes no result. `uo_trace_hops(tile)` with tile > 0 turns
+ * it on and empties it, 0 turns it off. The device takes a list `tile` cells at a time (64: one per lane) and reads `top`'s state at
+ * the start of each such tile, after the commits of the tiles before it; so the trace is cut the same way. One SEGMENT per tile of a
+ * hop's list, as 32-bit words: flags (bit 0: `top` was full at the segment's start, bit 1: first segment of a hop, bit 2: first
+ * segment of a query's level-0 walk), the radius at the segment's start (float bits), the number of fresh slots, then the slots
+ * `visits_set` found fresh, in list order. */
+static __thread uint32_t* trace_words = NULL;
+static __thread size_t trace_size = 0, trace_cap = 0, trace_count_at = 0;
+static __thread uint32_t trace_tile = 0;
+void uo_trace_hops(uint32_t tile_cells) { trace_tile = tile_cells, trace_size = 0; }
+size_t uo_trace_size(void) { return trace_size; }
+size_t uo_trace_copy(uint32_t* out, size_t cap) {
+    size_t n = trace_size < cap ? trace_size : cap;
+    if (n) memcpy(out, trace_words, n * sizeof(uint32_t));
+    return n;
+}
+static void trace_push(uint32_t word) {
+    if (trace_size == trace_cap) {
+        size_t cap = trace_cap ? trace_cap * 2 : 4096;
+        uint32_t* words = (uint32_t*)realloc(trace_words, cap * sizeof(uint32_t));
+        if (!words) return;
+        trace_words = words, trace_cap = cap;
+    }
+    trace_words[trace_size++] = word;
+}
+/* before list cell `cell` of a hop is looked at: opens a segment where a tile begins */
+static void trace_cell(uint32_t cell, int first_hop, int full, float radius) {
+    if (!trace_tile || cell % trace_tile) return;
+    uint32_t bits;
+    memcpy(&bits, &radius, 4);
+    trace_push((full ? 1u : 0u) | (cell == 0 ? 2u : 0u) | (cell == 0 && first_hop ? 4u : 0u));
+    trace_push(bits);
+    trace_count_at = trace_size;
+    trace_push(0);
+}
+static void trace_fresh(uint32_t slot) {
+    if (!trace_tile || trace_count_at >= trace_size) return;
+    trace_push(slot);
+    trace_words[trace_count_at]++;
+}
+
 /* The frontier mode of the device kernels (usearch_amd/csrc/kernels.hpp, frontier_top_k), restated so that the GPU can be
  * checked bit for bit in it: there is no `next` container; the frontier is the not-yet-expanded part of `top` (bit 31 of a
  * kept candidate's slot says "expanded"). A candidate enters `next` and `top` together (index.hpp:4233-4240) and what `top`
@@ -673,8 +721,10 @@ static void search_to_find_in_base_frontier_in_top(ctx_t* c, uint32_t start, siz
         uint32_t n = uo_neighbors(c->ix, expanded, 0, nbrs, 4096);
         for (uint32_t i = 0; i < n; ++i) {
             uint32_t successor = nbrs[i];
+            trace_cell(i, stat_shape[0] == 1, c->top.size == top_limit, radius);
             if (visits_set(&c->visits, successor))
                 continue;
+            trace_fresh(successor);
             float d = measure(c, successor);
             stat_shape[3] += 1;
             if (c->top.size < top_limit || d < radius) {
@@ -734,8 +784,10 @@ static void search_to_find_in_base(ctx_t* c, uint32_t start, size_t top_limit) {
         uint32_t n = uo_neighbors(c->ix, candidate.slot, 0, nbrs, 4096);
         for (uint32_t i = 0; i < n; ++i) {
             uint32_t successor = nbrs[i];
+            trace_cell(i, stat_shape[0] == 1, c->top.size == top_limit, radius);
             if (visits_set(&c->visits, successor)) /* 4229 */
                 continue;
+            trace_fresh(successor);
             float d = measure(c, successor);
             stat_shape[3] += 1;
             if (c->top.size < top_limit || d < radius) { /* 4233: strict `<` */

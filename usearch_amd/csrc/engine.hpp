@@ -183,8 +183,15 @@ struct workspace_t {
     void destroy();
 };
 
+/// Launches the sketch's record builder (sketch.hip) over rows [first, size) of `vectors` on `stream`: records[row][128] for those rows,
+/// rows below `first` untouched. `directions`: [dimensions][64] f32 on the device, `gram_defect` as `sketch_orthonormalise` reports it.
+void launch_sketch_records(const std::uint8_t* vectors, std::uint32_t row_stride, std::uint32_t dimensions, scalar_kind_t scalar,
+                           std::uint64_t first, std::uint64_t size, const float* directions, double gram_defect, std::uint8_t* records,
+                           hipStream_t stream);
+
 class snapshot_t {
   public:
+    friend struct sketch_test_access_t; ///< test_hooks.hip: reads the sketch back for tests/test_gpu_sketch_records.py
     snapshot_t() = default;
     ~snapshot_t();
     snapshot_t(const snapshot_t&) = delete;

@@ -111,6 +111,25 @@ __global__ __launch_bounds__(256) void sketch_records_kernel(const std::uint8_t*
     }
 }
 
+/// Records of rows [first, size) of `vectors` into `records` ([size][128], rows below `first` are left alone), on `stream`: the one place
+/// that launches `sketch_records_kernel` (`make_sketch`, and the test hooks on a caller's rows). The launch's error is the caller's to read.
+void launch_sketch_records(const std::uint8_t* vectors, std::uint32_t row_stride, std::uint32_t dimensions, scalar_kind_t scalar,
+                           std::uint64_t first, std::uint64_t size, const float* directions, double gram_defect, std::uint8_t* records,
+                           hipStream_t stream) {
+    if (first >= size)
+        return;
+    const std::uint64_t blocks = (size - first + 255) / 256;
+    if (scalar == scalar_f32_k)
+        hipLaunchKernelGGL(sketch_records_kernel<scalar_f32_k>, dim3((unsigned)blocks), dim3(256), 0, stream, vectors, row_stride, dimensions,
+                           first, size, directions, gram_defect, records);
+    else if (scalar == scalar_f16_k)
+        hipLaunchKernelGGL(sketch_records_kernel<scalar_f16_k>, dim3((unsigned)blocks), dim3(256), 0, stream, vectors, row_stride, dimensions,
+                           first, size, directions, gram_defect, records);
+    else
+        hipLaunchKernelGGL(sketch_records_kernel<scalar_bf16_k>, dim3((unsigned)blocks), dim3(256), 0, stream, vectors, row_stride, dimensions,
+                           first, size, directions, gram_defect, records);
+}
+
 void snapshot_t::drop_sketch() {
     view_.sketch = nullptr;
     view_.sketch_directions = nullptr;
@@ -174,19 +193,8 @@ const char* snapshot_t::make_sketch() {
         sketch_capacity_ = capacity;
     }
     if (sketch_rows_ < view_.size) {
-        const std::uint64_t blocks = (view_.size - sketch_rows_ + 255) / 256;
-        const std::uint8_t* vectors = static_cast<const std::uint8_t*>(d_vectors_);
-        std::uint8_t* records = static_cast<std::uint8_t*>(d_sketch_);
-        const float* directions = static_cast<const float*>(d_sketch_directions_);
-        if (scalar_ == scalar_f32_k)
-            hipLaunchKernelGGL(sketch_records_kernel<scalar_f32_k>, dim3((unsigned)blocks), dim3(256), 0, stream_, vectors, row_stride, dimensions,
-                               sketch_rows_, view_.size, directions, sketch_gram_defect_, records);
-        else if (scalar_ == scalar_f16_k)
-            hipLaunchKernelGGL(sketch_records_kernel<scalar_f16_k>, dim3((unsigned)blocks), dim3(256), 0, stream_, vectors, row_stride, dimensions,
-                               sketch_rows_, view_.size, directions, sketch_gram_defect_, records);
-        else
-            hipLaunchKernelGGL(sketch_records_kernel<scalar_bf16_k>, dim3((unsigned)blocks), dim3(256), 0, stream_, vectors, row_stride, dimensions,
-                               sketch_rows_, view_.size, directions, sketch_gram_defect_, records);
+        launch_sketch_records(static_cast<const std::uint8_t*>(d_vectors_), row_stride, dimensions, scalar_, sketch_rows_, view_.size,
+                              static_cast<const float*>(d_sketch_directions_), sketch_gram_defect_, static_cast<std::uint8_t*>(d_sketch_), stream_);
         UA_HIP(hipGetLastError());
         UA_HIP(hipStreamSynchronize(stream_));
         sketch_rows_ = view_.size;

@@ -10,12 +10,14 @@
 #include <vector>
 
 #include "device_scratch.hpp"
+#include "engine.hpp"
 #include "exact_plan.hpp"
 #include "host_util.hpp"
 #include "kernels.hpp"
 #include "kmeans.hpp"
 #include "placement.hpp"
 #include "search_plan.hpp"
+#include "sketch.hpp"
 #include "usearch_amd.h"
 
 typedef char const* usearch_amd_error_t;
@@ -386,4 +388,145 @@ extern "C" __attribute__((visibility("default"))) int usearch_amd_test_plan_exac
 //      common.hpp. → 1 or 0.
 extern "C" __attribute__((visibility("default"))) int usearch_amd_test_exact_tiled_pair(int metric, int scalar, uint64_t wanted) {
     return usearch_amd::exact_tiled_pair((usearch_amd::metric_kind_t)metric, (usearch_amd::scalar_kind_t)scalar, wanted) ? 1 : 0;
+}
+
+// ---- the sketch on the device and its twins piece by piece, for tests/test_gpu_sketch_records.py, tests/test_gpu_sketch_counts.py and
+//      tests/test_sketch_truth.py. `scalar_kind`: scalar_kind_t of common.hpp (f32, f16, bf16); `directions`: [dimensions][64] f32.
+namespace usearch_amd {
+struct sketch_test_access_t {
+    static const void* records(const snapshot_t& s) { return s.d_sketch_; }
+    static const void* directions(const snapshot_t& s) { return s.d_sketch_directions_; }
+    static std::uint64_t rows(const snapshot_t& s) { return s.d_sketch_ && s.d_sketch_directions_ ? s.sketch_rows_ : 0; }
+    static double gram_defect(const snapshot_t& s) { return s.sketch_gram_defect_; }
+};
+} // namespace usearch_amd
+
+namespace {
+bool sketch_scalar_kind(int scalar_kind) {
+    return scalar_kind == scalar_f32_k || scalar_kind == scalar_f16_k || scalar_kind == scalar_bf16_k;
+}
+sketch_directions_t sketch_directions_of(const float* transposed, size_t dimensions, double gram_defect) {
+    sketch_directions_t d;
+    d.transposed.assign(transposed, transposed + dimensions * sketch_columns_k);
+    d.rank = sketch_rank_k, d.gram_defect = gram_defect;
+    return d;
+}
+} // namespace
+
+/** `sketch_records_kernel` over rows [first, count) of the caller's `rows` ([count][stride] bytes) under the caller's directions: `records`
+ *  ([count][128], the caller's pattern in it) goes to the device, the kernel runs as `make_sketch` runs it, and everything comes back: rows
+ *  below `first` must still hold the pattern. */
+extern "C" __attribute__((visibility("default"))) void usearch_amd_test_sketch_device_records(const void* rows, size_t count, size_t stride,
+                                                                                              size_t dimensions, int scalar_kind, size_t first,
+                                                                                              const float* directions, double gram_defect,
+                                                                                              void* records, usearch_amd_error_t* error) {
+    if (!sketch_scalar_kind(scalar_kind))
+        return fail(error, "The sketch covers f32, f16 and bf16 rows");
+    fail(error, [&]() -> const char* {
+        if (!count || first > count)
+            return "No rows, or `first` beyond them";
+        if (stride < bytes_per_vector((scalar_kind_t)scalar_kind, dimensions) || stride > 0xFFFFFFFFull)
+            return "Rows shorter than their dimensions";
+        device_scratch_t scratch(current_device_k);
+        std::uint8_t *d_rows = nullptr, *d_records = nullptr;
+        float* d_directions = nullptr;
+        const size_t directions_bytes = dimensions * sketch_columns_k * sizeof(float);
+        UA_HIP(scratch.allocate(&d_rows, count * stride));
+        UA_HIP(scratch.allocate(&d_records, count * sketch_record_bytes_k));
+        UA_HIP(scratch.allocate(&d_directions, directions_bytes));
+        UA_HIP(hipMemcpy(d_rows, rows, count * stride, hipMemcpyHostToDevice));
+        UA_HIP(hipMemcpy(d_records, records, count * sketch_record_bytes_k, hipMemcpyHostToDevice));
+        UA_HIP(hipMemcpy(d_directions, directions, directions_bytes, hipMemcpyHostToDevice));
+        launch_sketch_records(d_rows, (std::uint32_t)stride, (std::uint32_t)dimensions, (scalar_kind_t)scalar_kind, first, count, d_directions,
+                              gram_defect, d_records, nullptr);
+        UA_HIP(hipGetLastError());
+        UA_HIP(hipDeviceSynchronize());
+        UA_HIP(hipMemcpy(records, d_records, count * sketch_record_bytes_k, hipMemcpyDeviceToHost));
+        return nullptr;
+    }());
+}
+
+/** The directions `sketch_orthonormalise` draws from `rows` as the engine draws them (up to 62 rows at the seeded slots) → `transposed`
+ *  [dimensions][64] f32, the number of directions and the gram defect. */
+extern "C" __attribute__((visibility("default"))) void usearch_amd_test_sketch_directions(const void* rows, size_t count, size_t stride,
+                                                                                          size_t dimensions, int scalar_kind, float* transposed,
+                                                                                          uint32_t* rank, double* gram_defect,
+                                                                                          usearch_amd_error_t* error) {
+    if (!sketch_scalar_kind(scalar_kind))
+        return fail(error, "The sketch covers f32, f16 and bf16 rows");
+    const std::uint8_t* row_bytes = static_cast<const std::uint8_t*>(rows);
+    const std::uint32_t samples = (std::uint32_t)std::min<std::size_t>(sketch_rank_k, count);
+    std::vector<double> wide((std::size_t)samples * dimensions);
+    for (std::uint32_t s = 0; s < samples; ++s)
+        for (std::size_t i = 0; i < dimensions; ++i)
+            wide[(std::size_t)s * dimensions + i] =
+                (double)sketch_scalar(row_bytes + sketch_sample_slot(s, count) * stride, (std::uint32_t)i, (scalar_kind_t)scalar_kind);
+    const sketch_directions_t directions = sketch_orthonormalise(wide, samples, (std::uint32_t)dimensions);
+    std::copy(directions.transposed.begin(), directions.transposed.end(), transposed);
+    *rank = directions.rank, *gram_defect = directions.gram_defect;
+}
+
+/** `sketch_record_host` for every row of `rows` under the caller's directions → `records` [count][128]. */
+extern "C" __attribute__((visibility("default"))) void usearch_amd_test_sketch_twin_records(const void* rows, size_t count, size_t stride,
+                                                                                            size_t dimensions, int scalar_kind,
+                                                                                            const float* directions, double gram_defect,
+                                                                                            void* records, usearch_amd_error_t* error) {
+    if (!sketch_scalar_kind(scalar_kind))
+        return fail(error, "The sketch covers f32, f16 and bf16 rows");
+    const sketch_directions_t d = sketch_directions_of(directions, dimensions, gram_defect);
+    for (std::size_t r = 0; r < count; ++r)
+        sketch_record_host(static_cast<const std::uint8_t*>(rows) + r * stride, (scalar_kind_t)scalar_kind, (std::uint32_t)dimensions, d,
+                           static_cast<std::uint8_t*>(records) + r * sketch_record_bytes_k);
+}
+
+/** `sketch_query_host` and `sketch_bound_host`: for query q ([query_count][stride] in the storage kind) with the Σa² the kernel has for it
+ *  (`sums_of_squares[q]`) → `used[q]` (0 = the query walks without the sketch) and `bounds[q][r]` against every one of `records`
+ *  ([count][128]); a query that does not use the sketch gets −∞ everywhere. */
+extern "C" __attribute__((visibility("default"))) void usearch_amd_test_sketch_twin_bounds(const void* queries, size_t query_count, size_t stride,
+                                                                                           const float* sums_of_squares, size_t dimensions,
+                                                                                           int scalar_kind, const float* directions,
+                                                                                           const void* records, size_t count, float* bounds,
+                                                                                           uint8_t* used, usearch_amd_error_t* error) {
+    if (!sketch_scalar_kind(scalar_kind))
+        return fail(error, "The sketch covers f32, f16 and bf16 rows");
+    const sketch_directions_t d = sketch_directions_of(directions, dimensions, 0.0); // (the query side does not read the gram defect)
+    std::vector<float> query(dimensions), coefficients(sketch_columns_k);
+    for (std::size_t q = 0; q < query_count; ++q) {
+        for (std::size_t i = 0; i < dimensions; ++i)
+            query[i] = sketch_scalar(static_cast<const std::uint8_t*>(queries) + q * stride, (std::uint32_t)i, (scalar_kind_t)scalar_kind);
+        const bool on = sketch_query_host(query.data(), sums_of_squares[q], (std::uint32_t)dimensions, d, coefficients.data());
+        used[q] = on ? 1 : 0;
+        for (std::size_t r = 0; r < count; ++r)
+            bounds[q * count + r] = on ? sketch_bound_host(coefficients.data(), static_cast<const std::uint8_t*>(records) + r * sketch_record_bytes_k,
+                                                           (std::uint32_t)dimensions)
+                                       : -INFINITY;
+    }
+}
+
+/** A snapshot's sketch read back: → the number of records it holds (0: no sketch); with `records` ([that many][128]), `directions`
+ *  ([dimensions][64] f32) and `rows` ([that many][bytes per vector], the stored rows the records were made from) non-null, copies of them;
+ *  `gram_defect`: what the records were made with. Call it once for the count, then with room. */
+extern "C" __attribute__((visibility("default"))) uint64_t usearch_amd_test_sketch_read_back(const void* snapshot, void* records, float* directions,
+                                                                                             void* rows, double* gram_defect,
+                                                                                             usearch_amd_error_t* error) {
+    const snapshot_t& s = *static_cast<const snapshot_t*>(snapshot);
+    const std::uint64_t count = sketch_test_access_t::rows(s);
+    fail(error, [&]() -> const char* {
+        if (!count)
+            return nullptr;
+        const snapshot_view_t& view = s.view();
+        UA_HIP(hipSetDevice(s.device()));
+        UA_HIP(hipDeviceSynchronize());
+        if (gram_defect)
+            *gram_defect = sketch_test_access_t::gram_defect(s);
+        if (records)
+            UA_HIP(hipMemcpy(records, sketch_test_access_t::records(s), count * sketch_record_bytes_k, hipMemcpyDeviceToHost));
+        if (directions)
+            UA_HIP(hipMemcpy(directions, sketch_test_access_t::directions(s), (std::size_t)view.dimensions * sketch_columns_k * sizeof(float),
+                             hipMemcpyDeviceToHost));
+        if (rows)
+            UA_HIP(hipMemcpy2D(rows, view.bytes_per_vector, view.vectors, view.row_stride, view.bytes_per_vector, count, hipMemcpyDeviceToHost));
+        return nullptr;
+    }());
+    return count;
 }

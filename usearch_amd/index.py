@@ -1253,6 +1253,16 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_sketch_bounds.restype = None
         _test_hooks.usearch_amd_test_sketch_bounds.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
                                                                C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p)]
+        error = C.POINTER(C.c_char_p)
+        for name, restype, arguments in (
+                ("device_records", None, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_double, C.c_void_p]),
+                ("directions", None, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
+                ("twin_records", None, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_double, C.c_void_p]),
+                ("twin_bounds", None, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_void_p]),
+                ("read_back", C.c_uint64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)])):
+            hook = getattr(_test_hooks, f"usearch_amd_test_sketch_{name}")
+            hook.restype, hook.argtypes = restype, arguments + [error]
         _test_hooks.usearch_amd_test_plan_search.restype = C.c_size_t
         _test_hooks.usearch_amd_test_plan_search.argtypes = [C.POINTER(PlanShape), C.POINTER(PlanTuning), C.c_void_p, C.c_size_t,
                                                              C.POINTER(PlanKnobs), C.POINTER(Plan), C.POINTER(PlanRung),
@@ -1368,6 +1378,93 @@ def test_sketch_bounds(rows: np.ndarray, queries: np.ndarray, dtype: str):
                                                 rows.strides[0], _pointer(bounds), C.byref(rank), C.byref(err))
     _raise(err, "usearch_amd_test_sketch_bounds")
     return bounds, int(rank.value)
+
+
+_SKETCH_KINDS = {"f32": 11, "f16": 12, "bf16": 4}  # scalar_kind_t of csrc/common.hpp
+SKETCH_COLUMNS, SKETCH_RECORD_BYTES = 64, 128
+
+
+def _sketch_rows(rows: np.ndarray, directions: Optional[np.ndarray] = None):
+    rows = np.ascontiguousarray(rows)
+    assert rows.ndim == 2
+    if directions is None:
+        return rows
+    directions = np.ascontiguousarray(directions, dtype=np.float32)
+    assert directions.shape == (rows.shape[1], SKETCH_COLUMNS), "directions are [dimensions][64] f32"
+    return rows, directions
+
+
+def test_sketch_directions(rows: np.ndarray, dtype: str):
+    """The directions the engine draws from `rows` (csrc/sketch.hpp `sketch_orthonormalise` over the rows at the seeded slots), no GPU
+    involved → (transposed [dimensions, 64] f32, number of directions, gram defect)."""
+    rows = _sketch_rows(rows)
+    transposed = np.zeros((rows.shape[1], SKETCH_COLUMNS), dtype=np.float32)
+    rank, defect, err = C.c_uint32(), C.c_double(), C.c_char_p()
+    test_hooks().usearch_amd_test_sketch_directions(_pointer(rows), len(rows), rows.strides[0], rows.shape[1], _SKETCH_KINDS[dtype],
+                                                    _pointer(transposed), C.byref(rank), C.byref(defect), C.byref(err))
+    _raise(err, "usearch_amd_test_sketch_directions")
+    return transposed, int(rank.value), float(defect.value)
+
+
+def test_sketch_twin_records(rows: np.ndarray, dtype: str, directions: np.ndarray, gram_defect: float) -> np.ndarray:
+    """`sketch_record_host` (the host twin of the record builder) for every row under `directions`, no GPU involved → uint8 [rows, 128]."""
+    rows, directions = _sketch_rows(rows, directions)
+    records = np.zeros((len(rows), SKETCH_RECORD_BYTES), dtype=np.uint8)
+    err = C.c_char_p()
+    test_hooks().usearch_amd_test_sketch_twin_records(_pointer(rows), len(rows), rows.strides[0], rows.shape[1], _SKETCH_KINDS[dtype],
+                                                      _pointer(directions), float(gram_defect), _pointer(records), C.byref(err))
+    _raise(err, "usearch_amd_test_sketch_twin_records")
+    return records
+
+
+def test_sketch_twin_bounds(queries: np.ndarray, sums_of_squares: np.ndarray, dtype: str, directions: np.ndarray, records: np.ndarray):
+    """`sketch_query_host` and `sketch_bound_host` (the host twins of the walk's side), no GPU involved: `queries` in the storage kind,
+    `sums_of_squares[q]` the f32 Σa² the kernel has for query q → (bounds [queries, records] f32, −inf for a query that does not use the
+    sketch; used [queries] bool)."""
+    queries, directions = _sketch_rows(queries, directions)
+    records = np.ascontiguousarray(records, dtype=np.uint8)
+    sums = np.ascontiguousarray(sums_of_squares, dtype=np.float32)
+    assert records.ndim == 2 and records.shape[1] == SKETCH_RECORD_BYTES and sums.shape == (len(queries),)
+    bounds = np.zeros((len(queries), len(records)), dtype=np.float32)
+    used = np.zeros(len(queries), dtype=np.uint8)
+    err = C.c_char_p()
+    test_hooks().usearch_amd_test_sketch_twin_bounds(_pointer(queries), len(queries), queries.strides[0], _pointer(sums), queries.shape[1],
+                                                     _SKETCH_KINDS[dtype], _pointer(directions), _pointer(records), len(records),
+                                                     _pointer(bounds), _pointer(used), C.byref(err))
+    _raise(err, "usearch_amd_test_sketch_twin_bounds")
+    return bounds, used.astype(bool)
+
+
+def test_sketch_device_records(rows: np.ndarray, dtype: str, directions: np.ndarray, gram_defect: float, first: int = 0,
+                               pattern: int = 0xA5) -> np.ndarray:
+    """The device's record builder (csrc/sketch.hip `sketch_records_kernel`, launched as `make_sketch` launches it) over rows
+    [first, len(rows)) under `directions` → uint8 [rows, 128]; the buffer is filled with `pattern` first, which rows below `first` keep."""
+    rows, directions = _sketch_rows(rows, directions)
+    records = np.full((len(rows), SKETCH_RECORD_BYTES), pattern, dtype=np.uint8)
+    err = C.c_char_p()
+    test_hooks().usearch_amd_test_sketch_device_records(_pointer(rows), len(rows), rows.strides[0], rows.shape[1], _SKETCH_KINDS[dtype],
+                                                        int(first), _pointer(directions), float(gram_defect), _pointer(records),
+                                                        C.byref(err))
+    _raise(err, "usearch_amd_test_sketch_device_records")
+    return records
+
+
+def test_sketch_read_back(index: "Index"):
+    """The sketch a snapshot holds, copied to the host → (records uint8 [members, 128], directions f32 [dimensions, 64], gram defect,
+    stored rows uint8 [members, bytes per vector]), or None when the snapshot has no sketch."""
+    err = C.c_char_p()
+    hook = test_hooks().usearch_amd_test_sketch_read_back
+    count = int(hook(index._handle, None, None, None, None, C.byref(err)))
+    _raise(err, "usearch_amd_test_sketch_read_back")
+    if not count:
+        return None
+    records = np.zeros((count, SKETCH_RECORD_BYTES), dtype=np.uint8)
+    directions = np.zeros((index.ndim, SKETCH_COLUMNS), dtype=np.float32)
+    rows = np.zeros((count, index.bytes_per_vector), dtype=np.uint8)
+    defect = C.c_double()
+    hook(index._handle, _pointer(records), _pointer(directions), _pointer(rows), C.byref(defect), C.byref(err))
+    _raise(err, "usearch_amd_test_sketch_read_back")
+    return records, directions, float(defect.value), rows
 
 
 def test_device_scratch(home: int, current: int) -> dict:
