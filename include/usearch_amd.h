@@ -549,6 +549,8 @@ typedef struct usearch_amd_build_config_t {
     uint64_t seed;              /**< level draw; 0 = a fixed default */
 } usearch_amd_build_config_t;
 
+/** Every field is cumulative: it counts over the builder's life — the build and every `extend` and `update` after it — whatever
+ *  happens to the link workspace in between. The work of one call is the difference of two readings. */
 typedef struct usearch_amd_build_stats_t {
     uint64_t batches, passes;
     uint64_t search_distances, search_hops;   /**< counters of the insertion searches (index.hpp:4011-4079) */
@@ -576,7 +578,8 @@ USEARCH_AMD_EXPORT void usearch_amd_build_free(usearch_amd_builder_t builder, us
 USEARCH_AMD_EXPORT void usearch_amd_build_extend(usearch_amd_builder_t builder, void const* vectors, size_t count, size_t stride,
                                                  usearch_amd_key_t const* keys, usearch_amd_error_t* error);
 /** Overwrites the members in `slots[0 .. count)` with new rows and keys and links them anew where they stand (a recycled slot:
- *  index.hpp:4087-4170). */
+ *  index.hpp:4087-4170). A slot that is no member ("No such member") and the same slot twice in one call ("The same slot twice in
+ *  one update") are refused before anything is overwritten: the index is as it was. */
 USEARCH_AMD_EXPORT void usearch_amd_build_update(usearch_amd_builder_t builder, uint32_t const* slots, size_t count, void const* vectors,
                                                  size_t stride, usearch_amd_key_t const* keys, usearch_amd_error_t* error);
 /** The snapshot the build produced; owned by the builder, valid until `usearch_amd_build_free`. */

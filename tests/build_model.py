@@ -17,6 +17,12 @@ The rules, and where they come from:
   the graph as it stood before the batch; `build_select_kernel` = `refine` to M plus one reverse-link request per pick;
   `build_reverse_kernel` = append in ascending requester order while the list has room, else old ∪ requesters sorted by
   (distance, slot) and refined to the capacity.
+- `extend`: `builder_t::extend`: the same batch rule from `max(first, 1)` on a graph that exists; `build` is "member 0 is the entry
+  point, then `extend` from 1".
+- `update`: `builder_t::update` (`index_gt::update`, index.hpp:2916-2999): the slots of a call, `max_batch` at a time in the order
+  given, are linked anew against the whole index: the walk never names the member itself (`exclude_own`), select REPLACES the
+  member's list, its inbound links stay, and a requester the target's list names already files nothing ("not new" in both
+  branches of `build_reverse_kernel`). The reference pin of these rules and the two stated deviations: tests/test_build_model.py.
 
 Ties. Wherever two DIFFERENT members meet at the same distance and a strict `<` or an order between them decides something —
 the descent's `d < closest`, the beam's `d < radius`, which of two equally far members stays in the final `top`, two equally far
@@ -111,10 +117,11 @@ def _heap_pop(heap: List[Candidate]) -> Candidate:
 
 
 def beam(graph: Graph, levels: Sequence[int], entry: int, max_level: int, query_slot: int, level: int, ef: int,
-         frontier: int, dist: Distance, exclude_own: bool = False) -> List[Candidate]:
+         frontier: int, dist: Distance, exclude_own: bool = False, routed: List[int] = None) -> List[Candidate]:
     """The insertion search of one node on one level → ≤ `ef` (distance, slot), ascending. Only members below `frontier` exist:
     a list that names another one is a broken graph, not something to skip. `exclude_own`: the query's own slot routes but never
-    becomes a candidate (`search_to_update_`)."""
+    becomes a candidate (`search_to_update_`, index.hpp:4087-4168: it enters the frontier and the visited set, not `top`, and
+    leaves the radius alone). `routed`: a list that receives `query_slot` when the walk expanded the query's own slot."""
     def neighbours(slot: int, on: int) -> List[int]:
         assert levels[slot] >= on, f"member {slot} is not on level {on}"
         found = graph[slot][on]
@@ -168,6 +175,8 @@ def beam(graph: Graph, levels: Sequence[int], entry: int, max_level: int, query_
         if d > radius and len(top) == ef:  # index.hpp:4210, strict
             break
         _heap_pop(nearest)
+        if routed is not None and candidate == query_slot:
+            routed.append(query_slot)
         for successor in neighbours(candidate, level):
             if successor in visited:
                 continue
@@ -184,11 +193,20 @@ def beam(graph: Graph, levels: Sequence[int], entry: int, max_level: int, query_
 
 
 @dataclass
+class Operation:
+    """What one call (`build`, `extend` or `update`) added to the builder's life-long counts."""
+    kind: str
+    batches: int = 0
+    passes: int = 0
+    repruned_lists: int = 0
+
+
+@dataclass
 class BuildResult:
     graph: Graph                    # graph[slot][level] → ordered neighbour list
     entry: int
     max_level: int
-    batches: int = 0
+    batches: int = 0                # these three count over the result's life, like `usearch_amd_build_stats_t`
     passes: int = 0
     repruned_lists: int = 0
     # what the build went through, for tests that must know a case reached the branch it is named for
@@ -198,69 +216,158 @@ class BuildResult:
     most_requesters_repruned: int = 0  # … among the targets that were re-pruned
     widest_reprune: int = 0         # most candidates (old neighbours + requesters) one re-prune sorted
     candidate_counts: List[int] = field(default_factory=list)  # every select step's candidate count
+    # requests whose requester the target's list already named (only a relink files such), by (list capacity, had the list room?)
+    named_requests: Dict[Tuple[int, bool], int] = field(default_factory=dict)
+    own_slot_routed: int = 0        # walks of `update` that expanded the member's own slot as a route (`exclude_own` did something)
+    entry_point_updated: bool = False  # an `update` named the entry point
+    operations: List[Operation] = field(default_factory=list)  # one per call, in order
+    memo: Dict[Tuple[int, int], float] = field(default_factory=dict)  # (query slot, row slot) → distance
+
+    @property
+    def named_with_room(self) -> int:
+        return sum(count for (_, room), count in self.named_requests.items() if room)
+
+    @property
+    def named_when_full(self) -> int:
+        return sum(count for (_, room), count in self.named_requests.items() if not room)
 
 
-def build(vectors, levels: Sequence[int], dist: Distance, connectivity: int, connectivity_base: int = 0,
-          expansion_add: int = 128, max_batch: int = 65536, batch_divisor: int = 16) -> BuildResult:
-    """`builder_t::build` for `len(vectors)` members whose levels are given (the level draw is not modelled)."""
-    n = len(vectors)
-    assert n == len(levels) and n >= 1
-    m = connectivity
-    m0 = connectivity_base or 2 * m
-    ef = max(max(m, m0) + 1, expansion_add)  # index.hpp:2799-2800
-    batch_divisor, max_batch = max(1, batch_divisor), max(1, min(max_batch, n))
+def _link_pass(result: BuildResult, operation: Operation, nodes: Sequence[int], level: int, frontier: int, relink: bool,
+               levels: Sequence[int], distance: Distance, m: int, m0: int, ef: int) -> None:
+    """One pass of `link_batch`: the searches of all `nodes` on `level`, then select for all of them, then the reverse step."""
+    graph = result.graph
+    routed: List[int] = []
+    # every search of the pass sees the graph as it stood before the pass
+    found = {i: beam(graph, levels, result.entry, result.max_level, i, level, ef, frontier, distance, relink, routed)
+             for i in nodes}
+    result.own_slot_routed += len(routed)
+    inboxes: Dict[int, List[Candidate]] = {}
+    for i in nodes:  # select: the node's list BECOMES the picks (a relinked node's old list is gone), and one request per pick
+        result.candidate_counts.append(len(found[i]))
+        result.most_candidates = max(result.most_candidates, len(found[i]))
+        picks = refine(found[i], m, distance)
+        graph[i][level] = [slot for _, slot in picks]
+        for d, slot in picks:
+            inboxes.setdefault(slot, []).append((d, i))
+    capacity = m0 if level == 0 else m
+    for target, requests in inboxes.items():  # reverse: targets are independent of each other
+        existing = graph[target][level]  # as select left it: a relinked target's list is its new one
+        fresh = [(d, requester) for d, requester in requests if requester not in existing]
+        if len(fresh) != len(requests):  # a relinked member keeps its inbound links: it does not file twice
+            key = (capacity, len(existing) < capacity)
+            result.named_requests[key] = result.named_requests.get(key, 0) + len(requests) - len(fresh)
+        result.most_requesters = max(result.most_requesters, len(fresh))
+        if len(existing) + len(fresh) <= capacity:
+            existing.extend(sorted(requester for _, requester in fresh))  # ascending requester
+            continue
+        # old neighbours measured from the target, requesters with the distance they filed
+        pool = [(_check_number(distance(target, other)), other) for other in existing] + fresh
+        pool.sort()  # (distance, slot)
+        graph[target][level] = [slot for _, slot in refine(pool, capacity, distance)]
+        result.repruned_lists += 1
+        operation.repruned_lists += 1
+        result.most_requesters_repruned = max(result.most_requesters_repruned, len(fresh))
+        result.widest_reprune = max(result.widest_reprune, len(pool))
+    if level:
+        result.widest_upper_pass = max(result.widest_upper_pass, len(nodes))
+    result.passes += 1
+    operation.passes += 1
 
-    memo: Dict[Tuple[int, int], float] = {}
+
+def _memoised(result: BuildResult, dist: Distance) -> Distance:
+    memo = result.memo
 
     def distance(a: int, b: int) -> float:
         key = (a, b)
         if key not in memo:
             memo[key] = dist(a, b)
         return memo[key]
+    return distance
 
-    graph: Graph = [[[] for _ in range(int(levels[slot]) + 1)] for slot in range(n)]
-    result = BuildResult(graph=graph, entry=0, max_level=int(levels[0]))  # the first node only becomes the entry point
-    begin = 1
-    while begin < n:
+
+def extend(result: BuildResult, levels: Sequence[int], dist: Distance, first: int, total: int, connectivity: int,
+           connectivity_base: int = 0, expansion_add: int = 128, max_batch: int = 65536, batch_divisor: int = 16,
+           kind: str = "extend") -> BuildResult:
+    """`builder_t::extend` → `link_range(max(first, 1), total)`: continues `result` (members 0 … first − 1) with members
+    first … total − 1, in place. `levels` covers all `total` members. The distance memo lives on `result` and is carried on."""
+    assert len(result.graph) == first <= total <= len(levels) and first >= 1
+    m = connectivity
+    m0 = connectivity_base or 2 * m
+    ef = max(max(m, m0) + 1, expansion_add)  # index.hpp:2799-2800
+    batch_divisor, max_batch = max(1, batch_divisor), max(1, min(max_batch, total))
+    distance = _memoised(result, dist)
+    graph = result.graph
+    graph.extend([[] for _ in range(int(levels[slot]) + 1)] for slot in range(first, total))
+    operation = Operation(kind)
+    result.operations.append(operation)
+    begin = max(first, 1)
+    while begin < total:
         limit = max(1, min(max_batch, begin // batch_divisor))
-        end = min(n, begin + limit)
+        end = min(total, begin + limit)
         batch = list(range(begin, end))
         batch_top = max(int(levels[i]) for i in batch)
         for level in range(min(batch_top, result.max_level) + 1):  # bottom-up; the levels above were not touched yet
             nodes = [i for i in batch if levels[i] >= level]
-            if not nodes:
-                continue
-            # every search of the pass sees the graph as it stood before the batch
-            found = {i: beam(graph, levels, result.entry, result.max_level, i, level, ef, begin, distance) for i in nodes}
-            inboxes: Dict[int, List[Candidate]] = {}
-            for i in nodes:  # select: the new node's list, and one request per pick
-                result.candidate_counts.append(len(found[i]))
-                result.most_candidates = max(result.most_candidates, len(found[i]))
-                picks = refine(found[i], m, distance)
-                graph[i][level] = [slot for _, slot in picks]
-                for d, slot in picks:
-                    inboxes.setdefault(slot, []).append((d, i))
-            capacity = m0 if level == 0 else m
-            for target, requests in inboxes.items():  # reverse: targets are independent of each other
-                existing = graph[target][level]
-                fresh = [(d, requester) for d, requester in requests if requester not in existing]
-                result.most_requesters = max(result.most_requesters, len(fresh))
-                if len(existing) + len(fresh) <= capacity:
-                    existing.extend(sorted(requester for _, requester in fresh))  # ascending requester
-                    continue
-                # old neighbours measured from the target, requesters with the distance they filed
-                pool = [(_check_number(distance(target, other)), other) for other in existing] + fresh
-                pool.sort()  # (distance, slot)
-                graph[target][level] = [slot for _, slot in refine(pool, capacity, distance)]
-                result.repruned_lists += 1
-                result.most_requesters_repruned = max(result.most_requesters_repruned, len(fresh))
-                result.widest_reprune = max(result.widest_reprune, len(pool))
-            if level:
-                result.widest_upper_pass = max(result.widest_upper_pass, len(nodes))
-            result.passes += 1
+            if nodes:
+                _link_pass(result, operation, nodes, level, begin, False, levels, distance, m, m0, ef)
         if batch_top > result.max_level:  # index.hpp:2874-2877: a taller node becomes the entry point
             result.entry = next(i for i in batch if levels[i] == batch_top)
             result.max_level = batch_top
         result.batches += 1
+        operation.batches += 1
         begin = end
     return result
+
+
+def update(result: BuildResult, slots: Sequence[int], levels: Sequence[int], dist: Distance, connectivity: int,
+           connectivity_base: int = 0, expansion_add: int = 128, max_batch: int = 65536) -> BuildResult:
+    """`builder_t::update` → `link_range(size, size, slots)`: the members in `slots` have new rows and are linked anew, in place
+    (`index_gt::update`, index.hpp:2916-2999). Every row of the call is overwritten before the first batch is linked, so `dist`
+    is the distance over the NEW rows for the whole call; the pairs of the memo that name an updated slot are dropped here, on
+    entry, and the memo is carried on otherwise. `slots` is taken in the order given, `max_batch` at a time (no divisor rule);
+    the frontier is the whole index; levels, the entry point and the max level stay. The same slot twice is refused by the
+    builder, so it is no case of the model."""
+    slots = [int(slot) for slot in slots]
+    n = len(result.graph)
+    assert all(0 <= slot < n for slot in slots) and len(set(slots)) == len(slots)
+    m = connectivity
+    m0 = connectivity_base or 2 * m
+    ef = max(max(m, m0) + 1, expansion_add)
+    max_batch = max(1, min(max_batch, n))
+    updated = set(slots)
+    for pair in [pair for pair in result.memo if pair[0] in updated or pair[1] in updated]:
+        del result.memo[pair]
+    distance = _memoised(result, dist)
+    result.entry_point_updated = result.entry_point_updated or result.entry in updated
+    operation = Operation("update")
+    result.operations.append(operation)
+    for offset in range(0, len(slots), max_batch):
+        batch = slots[offset:offset + max_batch]
+        batch_top = max(int(levels[i]) for i in batch)
+        for level in range(min(batch_top, result.max_level) + 1):
+            nodes = [i for i in batch if levels[i] >= level]
+            if nodes:
+                _link_pass(result, operation, nodes, level, n, True, levels, distance, m, m0, ef)
+        result.batches += 1
+        operation.batches += 1
+    return result
+
+
+def build(vectors, levels: Sequence[int], dist: Distance, connectivity: int, connectivity_base: int = 0,
+          expansion_add: int = 128, max_batch: int = 65536, batch_divisor: int = 16) -> BuildResult:
+    """`builder_t::build` for `len(vectors)` members whose levels are given (the level draw is not modelled): member 0 is the
+    entry point, the rest is an `extend` from 1."""
+    n = len(vectors)
+    assert n == len(levels) and n >= 1
+    result = BuildResult(graph=[[[] for _ in range(int(levels[0]) + 1)]], entry=0, max_level=int(levels[0]))
+    if n == 1:
+        result.operations.append(Operation("build"))
+        return result
+    return extend(result, levels, dist, 1, n, connectivity, connectivity_base, expansion_add, max_batch, batch_divisor, "build")
+
+
+def from_lists(lists: Graph, entry: int, max_level: int) -> BuildResult:
+    """A graph read from an image (tests/compact_model.py `read_image`) as the state `extend` and `update` continue."""
+    return BuildResult(graph=[[list(cells) for cells in per_level] for per_level in lists], entry=entry, max_level=max_level)
+
+

@@ -237,3 +237,14 @@ def test_build_edge_cases():
         usearch_amd.build(util.make_vectors(10, 16, "f32", seed=1), "cos", "f32", connectivity=65)
     with pytest.raises(RuntimeError):
         usearch_amd.build(util.make_vectors(10, 16, "f32", seed=1), "cos", "f32", connectivity=16, connectivity_base=129)
+    # `update` refuses on the host, by name, before anything is overwritten: the index is as it was
+    vectors = util.make_vectors(103, 16, "f32", seed=3, clustered=False)
+    built = usearch_amd.build(vectors[:100], "l2sq", "f32", connectivity=4, expansion_add=40, max_batch=16)
+    before, batches = built.save_buffer().tobytes(), built.stats.batches
+    for slots, message in (([5, 9, 5], "The same slot twice in one update"), ([5, 100, 7], "No such member")):
+        with pytest.raises(RuntimeError, match=message):
+            built.update(np.array(slots, dtype=np.uint32), vectors[100:103], np.array([1, 2, 3], dtype=np.uint64))
+        assert built.save_buffer().tobytes() == before, f"a refused update ({message}) changed the index"
+        assert built.stats.batches == batches
+    built.update(np.array([9, 5], dtype=np.uint32), vectors[100:102], np.array([1, 2], dtype=np.uint64))  # and goes on working
+    assert built.save_buffer().tobytes() != before and built.stats.batches == batches + 1

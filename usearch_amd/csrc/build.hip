@@ -4,6 +4,7 @@
  */
 #include "build.hpp"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -348,6 +349,15 @@ const char* builder_t::update(const std::uint32_t* slots, std::uint64_t count, c
         return "Nothing to update";
     if (stride < bytes_per_vector(scalar_, dimensions_))
         return "Stride is smaller than one vector";
+    {   // refused before anything is overwritten: a slot that is no member, and the same slot twice (two waves of the select
+        // kernel would write one list, and which row and key stay would depend on the order of the uploads)
+        std::vector<std::uint32_t> sorted(slots, slots + count);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.back() >= size_)
+            return "No such member";
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return "The same slot twice in one update";
+    }
     if (identity_keys_) {
         keys_.resize(size_);
         for (std::uint64_t i = 0; i < size_; ++i)
@@ -355,8 +365,6 @@ const char* builder_t::update(const std::uint32_t* slots, std::uint64_t count, c
         identity_keys_ = false;
     }
     for (std::uint64_t i = 0; i < count; ++i) {
-        if (slots[i] >= size_)
-            return "No such member";
         keys_[slots[i]] = keys[i];
         if (const char* e = snapshot_.overwrite_member(slots[i], static_cast<const std::uint8_t*>(vectors) + i * stride, keys[i]))
             return e;
@@ -431,10 +439,13 @@ const char* builder_t::link_range(std::uint64_t begin, const std::uint64_t end_t
         }
         UA_HIP(allocate((void**)&d_deferred_count_, 16));
         UA_HIP(hipMemset(d_inbox_count_, 0, members * 4));
-        UA_HIP(hipMemset(d_counters_, 0, 64));
         workspace_nodes_ = members;
         workspace_batch_ = max_batch;
     }
+    // the device counters count this call only — the workspace they live in comes and goes (released after a one-shot build, re-made
+    // after growth) — and are added to the builder's life-long totals at the end
+    UA_HIP(hipMemset(d_counters_, 0, 64));
+    unfiled_requests_ = 0;
     const snapshot_view_t& view = snapshot_.view();
 
     build_args_t args{};
@@ -591,10 +602,10 @@ const char* builder_t::link_range(std::uint64_t begin, const std::uint64_t end_t
     }
     unsigned long long counters[4] = {0, 0, 0, 0};
     UA_HIP(hipMemcpy(counters, d_counters_, sizeof(counters), hipMemcpyDeviceToHost));
-    stats_.select_distances = counters[0];
-    stats_.reverse_distances = counters[1];
-    stats_.repruned_lists = counters[2];
-    stats_.dropped_requests = counters[3] + unfiled_requests_;
+    stats_.select_distances += counters[0];
+    stats_.reverse_distances += counters[1];
+    stats_.repruned_lists += counters[2];
+    stats_.dropped_requests += counters[3] + unfiled_requests_;
     return nullptr;
 }
 

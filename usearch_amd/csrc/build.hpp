@@ -33,6 +33,7 @@ struct build_config_t {
     bool multi = false;                   ///< several members may share a key: written into the image's head (index_dense.hpp:1046)
 };
 
+/// Cumulative: every field counts over the builder's life (build, then every `extend` and `update`).
 struct build_stats_t {
     std::uint64_t batches = 0, passes = 0;
     std::uint64_t search_distances = 0; ///< `computed_distances` of the insertion searches
@@ -71,7 +72,7 @@ class builder_t {
      *  slot into `free_keys_`, `add_` pops it and calls `index_gt::update`, index.hpp:2916-2999): member `slots[i]` gets vector i
      *  (host memory, `stride` bytes apart) and `keys[i]`, keeps its level, and is linked anew — insertion search that never names
      *  the member itself (`search_to_update_`), `form_links_to_closest_`, `form_reverse_links_`. Links other members still hold
-     *  to the slot stay, as in the reference.
+     *  to the slot stay, as in the reference. A slot that is no member, or the same slot twice, is refused before anything changes.
      */
     const char* update(const std::uint32_t* slots, std::uint64_t count, const void* vectors, std::size_t stride,
                        const std::uint64_t* keys);
