@@ -3,36 +3,9 @@ reference containers (max_heap_gt index.hpp:664-835, sorted_buffer_gt index.hpp:
 import numpy as np
 import pytest
 
+from tests.container_model import RefHeap
+
 pytestmark = pytest.mark.gpu
-
-
-class RefHeap:  # max-heap on key, reference sift rules
-    def __init__(self):
-        self.e = []
-
-    def push(self, key, slot):
-        self.e.append((key, slot))
-        i = len(self.e) - 1
-        while i and self.e[(i - 1) // 2][0] < self.e[i][0]:
-            self.e[(i - 1) // 2], self.e[i] = self.e[i], self.e[(i - 1) // 2]
-            i = (i - 1) // 2
-
-    def pop(self):
-        top = self.e[0]
-        self.e[0] = self.e[-1]
-        self.e.pop()
-        i, n = 0, len(self.e)
-        while True:
-            best, left, right = i, 2 * i + 1, 2 * i + 2
-            if left < n and self.e[best][0] < self.e[left][0]:
-                best = left
-            if right < n and self.e[best][0] < self.e[right][0]:
-                best = right
-            if best == i:
-                break
-            self.e[i], self.e[best] = self.e[best], self.e[i]
-            i = best
-        return top
 
 
 def ref_sorted_insert(buf, d, slot, limit):
@@ -65,6 +38,65 @@ def test_containers_match_reference_rules(seed, levels, count, limit):
     (pk, ps), (tk, ts) = ua.test_containers(kinds, keys, slots, limit)
     assert [(float(a), int(b)) for a, b in zip(pk, ps)] == popped
     assert [(float(a), int(b)) for a, b in zip(tk, ts)] == top
+
+
+@pytest.mark.parametrize("global_memory", [False, True])
+@pytest.mark.parametrize("form", ["distinct", "eight levels", "5% nan"])
+def test_deep_heap_matches_reference_rules(form, global_memory):
+    """2 600 pushes, then 1 500 pop / push pairs, in LDS and in device memory (`global_ak = true`): what is popped, then what remains,
+    cell by cell, equals `max_heap_gt`. The heap's rules are comparisons in a fixed order, which have a definite answer for NaN too, so
+    the 5 % NaN form is held to the same reference. `heap_pop` settles five levels per round: its third round needs more than 2 047
+    entries below the root, which the walks' frontiers reach only on filtered searches at large expansions."""
+    from usearch_amd import index as ua
+    rng = np.random.default_rng(11)
+    fill, pairs = 2600, 1500
+    count = fill + 2 * pairs
+    kinds = np.zeros(count, dtype=np.uint32)
+    kinds[fill::2] = 1
+    if form == "distinct":
+        keys = rng.permutation(count).astype(np.float32) * -0.125
+    else:
+        keys = rng.integers(0, 8, size=count).astype(np.float32) * -0.5
+        if form == "5% nan":
+            keys[rng.random(count) < 0.05] = np.nan
+    slots = np.arange(count, dtype=np.uint32)
+    heap, popped, deepest = RefHeap(), [], 0
+    for kind, key, slot in zip(kinds, keys, slots):
+        if kind == 0:
+            heap.push(float(key), int(slot))
+        else:
+            deepest = max(deepest, len(heap.e))
+            popped.append(heap.pop())
+    assert deepest > 2047 and len(popped) == pairs, "the script must reach the third round of `heap_pop`"
+    (pk, ps), (tk, ts), (hk, hs) = ua.test_containers(kinds, keys, slots, 1, global_memory=global_memory, remains=True)
+    bits = keys.view(np.uint32)
+    assert ps.tolist() == [slot for _, slot in popped]
+    assert pk.view(np.uint32).tolist() == [int(bits[slot]) for _, slot in popped]
+    assert hs.tolist() == [slot for _, slot in heap.e]
+    assert hk.view(np.uint32).tolist() == [int(bits[slot]) for _, slot in heap.e]
+    assert len(tk) == 0 and len(ts) == 0
+
+
+@pytest.mark.parametrize("seed,levels,count,limit", [(0, 4, 300, 16), (3, 8, 64, 1), (4, 3, 1000, 200)])
+def test_containers_in_device_memory_match_reference_rules(seed, levels, count, limit):
+    """The scripts of `test_containers_match_reference_rules` on the `global_ak = true` variants of the same containers."""
+    from usearch_amd import index as ua
+    rng = np.random.default_rng(seed)
+    kinds = rng.choice([0, 0, 0, 1, 2, 2], size=count).astype(np.uint32)
+    keys = rng.integers(0, levels, size=count).astype(np.float32) * 0.5 - 1.0
+    slots = np.arange(count, dtype=np.uint32)
+    heap, top, popped = RefHeap(), [], []
+    for kind, key, slot in zip(kinds, keys, slots):
+        if kind == 0:
+            heap.push(float(key), int(slot))
+        elif kind == 1 and heap.e:
+            popped.append(heap.pop())
+        elif kind == 2:
+            ref_sorted_insert(top, float(key), int(slot), limit)
+    (pk, ps), (tk, ts), (hk, hs) = ua.test_containers(kinds, keys, slots, limit, global_memory=True, remains=True)
+    assert [(float(a), int(b)) for a, b in zip(pk, ps)] == popped
+    assert [(float(a), int(b)) for a, b in zip(tk, ts)] == top
+    assert [(float(a), int(b)) for a, b in zip(hk, hs)] == heap.e
 
 
 def micro_benchmarks(waves=3, fill=32, count=64, limit=16):

@@ -43,6 +43,28 @@ def test_merge_kernel_matches_merge_into(shards, k, levels):
         assert np.all(got_k[i, n:] == 0) and np.all(np.isnan(got_d[i, n:]))
 
 
+@pytest.mark.parametrize("later_position_first", [True, False])
+@pytest.mark.parametrize("nan_share", [0.0, 0.1, 1.0])
+@pytest.mark.parametrize("shards", [3, 8])
+@pytest.mark.parametrize("k", [1, 7, 100])
+def test_merge_kernel_follows_the_model_with_nan(k, shards, nan_share, later_position_first):
+    """Lists in the shape the rule leaves them (NaNs first, then ascending; counts with 0 and k among them) through the merge kernel,
+    for both orders inside a shard: equal to inserting the lists one after the other under the rule (`merge_model`), which on NaN-free
+    lists is the oracle's `merge_into` (tests/test_container_model.py). The output buffers hold a sentinel before the launch: with two
+    elements at one rank a cell below the count would keep it. The same lists go through the host path of `merge_rank` there."""
+    from tests import container_model as model
+    from usearch_amd import index as ua
+    rng = np.random.default_rng(shards * 1000 + k)
+    distances, keys, counts = model.nan_first_lists(rng, shards, 64, k, nan_share)
+    sentinel = 0xABABABABABABABAB
+    got = ua.test_merge(distances, keys, counts, later_position_first, on_host=False, key_sentinel=sentinel)
+    model.assert_merge_follows_model(got, distances, keys, counts, later_position_first, sentinel)
+    if later_position_first:  # the product's own entry point runs the same kernel (its buffers start out unwritten device memory)
+        plain_k, plain_d, plain_c = ua.merge_many(distances, keys, counts)
+        assert np.array_equal(plain_k, got[0]) and np.array_equal(plain_d.view(np.uint32), got[1].view(np.uint32))
+        assert np.array_equal(plain_c, got[2])
+
+
 def test_sharded_pipeline_on_one_gpu(reference):
     from usearch_amd import Index
     from usearch_amd import index as ua

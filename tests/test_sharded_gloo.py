@@ -111,6 +111,20 @@ def worker(rank: int, port: int, results):
         stats, step = flaky.search_raw(None, queries.ctypes.data, Q, STRIDE, K, 64, 0, keys.ctypes.data,
                                        distances.ctypes.data, counts.ctypes.data, 0, 0)
         assert step.exchanges == 1
+
+        # lists that begin with NaNs through the same host merge (`merge_rank` walked by `merge_blocks_host`): NaN first, then
+        # distance ↑, shard ↓, position ↓ — equal to inserting the shards' lists one after the other under that rule.
+        # The output buffers hold a sentinel before the step: two elements at one rank would leave a cell unwritten
+        from tests import container_model as model
+        nan_distances, nan_keys, nan_counts = model.nan_first_lists(np.random.default_rng(41), WORLD, Q, K, 0.1)
+        assert np.isnan(nan_distances).any() and not np.isnan(nan_distances).all()
+        with_nan = Communicator.on_host(rank, WORLD, all_gather, broadcast,
+                                        lambda queries, count, wanted, expansion: (nan_keys[rank], nan_distances[rank], nan_counts[rank]))
+        sentinel = 0xABABABABABABABAB
+        keys[:], counts[:] = sentinel, sentinel
+        distances.view(np.uint32)[:] = 0xCDCDCDCD
+        with_nan.search_raw(None, queries.ctypes.data, Q, STRIDE, K, 64, 0, keys.ctypes.data, distances.ctypes.data, counts.ctypes.data, 0, 0)
+        model.assert_merge_follows_model((keys, distances, counts), nan_distances, nan_keys, nan_counts, True, sentinel)
         results[rank] = True
     finally:
         dist.destroy_process_group()

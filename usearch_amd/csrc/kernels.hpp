@@ -197,7 +197,9 @@ UA_DEVICE void heap_push_finish(cand_t* heap, std::uint32_t& size, const push_ti
     using mem = scratch_gt<global_ak>;
     const std::uint32_t lane = lane_id();
     const std::uint64_t overtaken = ballot(ticket.has && cand_distance(ticket.ancestor) < key);
-    const std::uint32_t rises = popcount64(overtaken);
+    // the rise ends at the first ancestor that is not overtaken (index.hpp:808-811); with a NaN on the path the overtaken ones are
+    // not a prefix of it, so the prefix is counted, not the ballot's bits (ancestors answer in lanes 1 … depth)
+    const std::uint32_t rises = (std::uint32_t)__ffsll((long long)~(overtaken >> 1)) - 1;
     // ONE store: lanes 1 … rises move their ancestor one level down, lane 0 puts the key where the last of them was (`rises` never
     // exceeds the number of ancestors, so every lane up to it holds one; the cells are distinct: levels 0 … rises of the path)
     if (lane <= rises) {
@@ -350,7 +352,7 @@ UA_DEVICE bool sorted_insert(cand_t* top, std::uint32_t& size, std::uint32_t lim
     std::uint32_t position = 0;
     for (std::uint32_t base = 0; base < size; base += 64) {
         const std::uint32_t j = base + lane;
-        const bool less = j < size && cand_distance(mem::load(top + j)) < d;
+        const bool less = j < size && d == d && !(cand_distance(mem::load(top + j)) >= d); // NaN first: see `top_gt::insert`
         position += popcount64(ballot(less));
     }
     if (position == limit)
@@ -433,14 +435,18 @@ template <int epl_ak, bool global_ak, bool flags_ak = false> struct top_gt {
             float below_d = lane_below_f32(d[epl_ak - 1]);
             const std::uint32_t below_s = lane_below_u32(s[epl_ak - 1]);
             below_d = lane == 0 ? -__builtin_inff() : below_d;
-            // lower_bound placement: the landing cell is the first one that is not smaller than `nd` (new before equal)
-            // (for lane 0 that holds whatever `nd` is: a NaN compares smaller than nothing, lands in the very first cell — where
+            // lower_bound placement: the landing cell is the first one that does not stay in front of `nd` (new before equal)
+            // (for lane 0 that holds whatever `nd` is: nothing stays in front of a NaN, it lands in the very first cell — where
             // the reference's lower_bound puts it, index.hpp:928-939 — and must not pull the cell "below" into the array)
+            // (NaN first, DESIGN.md §3.1a: `<` alone is not monotone over an array that holds a NaN beside numbers — [NaN, 1, 2] and
+            // the newcomer 1.5 made two landing cells and lost the NaN. A cell stays in front of a number when it is NOT >= it, which a
+            // NaN cell is; nothing stays in front of a NaN newcomer. One compare per cell as before, one wave-uniform condition)
+            const bool number = nd == nd;
             bool smaller[regs_k + 1];
-            smaller[0] = lane == 0 || below_d < nd;
+            smaller[0] = lane == 0 || (number && !(below_d >= nd));
 #pragma unroll
             for (int i = 0; i < epl_ak; ++i)
-                smaller[i + 1] = d[i] < nd;
+                smaller[i + 1] = number && !(d[i] >= nd);
 #pragma unroll
             for (int i = epl_ak - 1; i >= 0; --i) { // descending: cell i still reads the old cell i - 1
                 const float under_d = i > 0 ? d[i > 0 ? i - 1 : 0] : below_d;

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "device_scratch.hpp"
@@ -15,6 +16,7 @@
 #include "host_util.hpp"
 #include "kernels.hpp"
 #include "kmeans.hpp"
+#include "merge_core.hpp"
 #include "placement.hpp"
 #include "search_plan.hpp"
 #include "sketch.hpp"
@@ -30,35 +32,98 @@ void fail(usearch_amd_error_t* error, const char* message) {
 
 namespace usearch_amd {
 /**
- *  Container self-test: replays a scripted sequence of heap pushes / pops and sorted inserts on the LDS containers
+ *  Container self-test: replays a scripted sequence of heap pushes / pops and sorted inserts on the scratch-memory containers
  *  and records what comes out, so the GPU tests can compare the tie behaviour with the oracle's containers directly.
  *  ops[i] = {kind, slot}: kind 0 = push(key = keys[i]), 1 = pop, 2 = sorted_insert(keys[i]) with `limit`.
+ *  `global_ak`: heap and buffer live in the device memory behind `memory` (the all-global fallback's accessors), else in LDS.
+ *  At the end the heap's cells are read out as they lie.
  */
-__global__ __launch_bounds__(64) void containers_kernel(const std::uint32_t* kinds, const float* keys,
-                                                        const std::uint32_t* slots, std::uint32_t count,
-                                                        std::uint32_t limit, std::uint32_t capacity,
-                                                        std::uint64_t* popped, std::uint32_t* popped_count,
-                                                        std::uint64_t* top_out, std::uint32_t* top_count) {
+template <bool global_ak>
+__global__ __launch_bounds__(64) void containers_kernel(const std::uint32_t* kinds, const float* keys, const std::uint32_t* slots,
+                                                        std::uint32_t count, std::uint32_t limit, std::uint32_t capacity, cand_t* memory,
+                                                        std::uint64_t* popped, std::uint32_t* counts, std::uint64_t* top_out,
+                                                        std::uint64_t* heap_out) {
     extern __shared__ __attribute__((aligned(16))) std::uint8_t lds[];
-    cand_t* heap = reinterpret_cast<cand_t*>(lds);
+    using mem = scratch_gt<global_ak>;
+    cand_t* heap = global_ak ? memory : reinterpret_cast<cand_t*>(lds);
     cand_t* top = heap + capacity;
     std::uint32_t heap_size = 0, top_size = 0, pops = 0;
     for (std::uint32_t i = 0; i < count; ++i) {
         const std::uint32_t kind = kinds[i];
         if (kind == 0 && heap_size < capacity)
-            heap_push<false>(heap, heap_size, keys[i], slots[i]);
+            heap_push<global_ak>(heap, heap_size, keys[i], slots[i]);
         else if (kind == 1 && heap_size) {
-            const cand_t c = heap_pop<false>(heap, heap_size);
+            const cand_t c = heap_pop<global_ak>(heap, heap_size);
             if (lane_id() == 0)
                 popped[pops] = c;
             ++pops;
         } else if (kind == 2)
-            sorted_insert<false>(top, top_size, limit, keys[i], slots[i]);
+            sorted_insert<global_ak>(top, top_size, limit, keys[i], slots[i]);
     }
     for (std::uint32_t i = lane_id(); i < top_size; i += 64)
-        top_out[i] = top[i];
+        top_out[i] = mem::load(top + i);
+    for (std::uint32_t i = lane_id(); i < heap_size; i += 64)
+        heap_out[i] = mem::load(heap + i);
     if (lane_id() == 0)
-        *popped_count = pops, *top_count = top_size;
+        counts[0] = pops, counts[1] = top_size, counts[2] = heap_size;
+}
+
+/**
+ *  Self-test of `top` as the search kernels hold it, one wave over one `top_gt` layout. ops[i]: kind 0 = insert {keys[i], slots[i]}
+ *  under the traversal's acceptance rule, applied here as `search_one` applies it; 1 = the same with the member closed on arrival
+ *  (`slot | closed_bit_k`, the pipelined commit); 2 = `first_open` + `close` (the flagged layouts; elsewhere it does nothing).
+ *  records[i] = {accepted or found, size, radius bits, and for kind 2: distance bits, slot, owner_lane · epl + owner_cell — none_slot_k
+ *  where there is none}. At the end every cell goes out as it lies (registers: all 64 · epl of them, each lane its own; scratch
+ *  memory: the first `size`).
+ */
+constexpr std::uint32_t top_record_words_k = 6;
+template <int epl_ak, bool global_ak, bool flags_ak>
+__global__ __launch_bounds__(64) void top_kernel(const std::uint32_t* kinds, const float* keys, const std::uint32_t* slots,
+                                                 std::uint32_t count, std::uint32_t limit, cand_t* memory, std::uint32_t* records,
+                                                 std::uint32_t* cell_bits, std::uint32_t* cell_slots, std::uint32_t* final_size) {
+    extern __shared__ __attribute__((aligned(16))) std::uint8_t lds[];
+    top_gt<epl_ak, global_ak, flags_ak> top;
+    top.reset(global_ak ? memory : reinterpret_cast<cand_t*>(lds));
+    float radius = __builtin_inff();
+    for (std::uint32_t i = 0; i < count; ++i) {
+        const std::uint32_t kind = uniform_u32(kinds[i]);
+        std::uint32_t flag = 0, out_bits = 0, out_slot = none_slot_k, out_cell = none_slot_k;
+        if (kind <= 1) {
+            const float d = uniform_f32(keys[i]);
+            const std::uint32_t slot = uniform_u32(slots[i]);
+            if (top.size < limit || d < radius) {
+                top.insert(d, flags_ak && kind == 1 ? slot | top.closed_bit_k : slot, limit, radius);
+                flag = 1;
+            }
+        } else if constexpr (flags_ak) {
+            float distance = 0.f;
+            std::uint32_t slot = 0, owner_lane = 0, owner_cell = 0;
+            if (top.first_open(distance, slot, owner_lane, owner_cell)) {
+                top.close(owner_lane, owner_cell);
+                flag = 1, out_bits = __builtin_bit_cast(std::uint32_t, distance), out_slot = slot;
+                out_cell = owner_lane * (std::uint32_t)epl_ak + owner_cell;
+            }
+        }
+        if (lane_id() == 0) {
+            std::uint32_t* record = records + (std::uint64_t)i * top_record_words_k;
+            record[0] = flag, record[1] = top.size, record[2] = __builtin_bit_cast(std::uint32_t, radius);
+            record[3] = out_bits, record[4] = out_slot, record[5] = out_cell;
+        }
+    }
+    if constexpr (epl_ak == 0) {
+        for (std::uint32_t i = lane_id(); i < top.size; i += 64) {
+            const cand_t c = scratch_gt<global_ak>::load(top.cells + i);
+            cell_bits[i] = (std::uint32_t)c, cell_slots[i] = cand_slot(c);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < epl_ak; ++i) {
+            const std::uint32_t g = lane_id() * epl_ak + i;
+            cell_bits[g] = __builtin_bit_cast(std::uint32_t, top.d[i]), cell_slots[g] = top.s[i];
+        }
+    }
+    if (lane_id() == 0)
+        *final_size = top.size;
 }
 
 /**
@@ -178,41 +243,202 @@ __attribute__((visibility("default"))) void usearch_amd_bench_top(uint32_t epl, 
 /**
  *  Self-test hook: replays `count` scripted operations on the device-side containers (kind 0 = frontier push of
  *  {keys[i], slots[i]}, 1 = frontier pop, 2 = insert {keys[i], slots[i]} into the result buffer limited to `limit`) and
- *  returns what was popped and the final result buffer, each entry packed as (slot << 32 | float bits).
+ *  returns what was popped, the final result buffer and what remains in the heap, cell by cell, each entry packed as
+ *  (slot << 32 | float bits). `global_memory`: the containers live in device memory (`global_ak = true`), else in LDS.
+ *  `heap` needs room for one entry per push.
  */
 static const char* test_containers(uint32_t const* kinds, float const* keys, uint32_t const* slots, size_t count, size_t limit,
-                                   uint64_t* popped, size_t* popped_count, uint64_t* top, size_t* top_count) {
-    const size_t capacity = count + 1;
+                                   int global_memory, uint64_t* popped, size_t* popped_count, uint64_t* top, size_t* top_count,
+                                   uint64_t* heap, size_t* heap_count) {
+    size_t pushes = 0;
+    for (size_t i = 0; i < count; ++i)
+        pushes += kinds[i] == 0;
+    const size_t capacity = pushes + 1; // the heap never holds more than was pushed
+    const size_t cells = capacity + limit + 1;
+    if (!global_memory && cells * 8 > 64 * 1024)
+        return "The script's containers do not fit into LDS";
     uint32_t *d_kinds = nullptr, *d_slots = nullptr, *d_counts = nullptr;
     float* d_keys = nullptr;
-    uint64_t *d_popped = nullptr, *d_top = nullptr;
+    uint64_t *d_popped = nullptr, *d_top = nullptr, *d_heap = nullptr;
+    cand_t* d_memory = nullptr;
     device_scratch_t scratch(current_device_k);
     UA_HIP(scratch.allocate(&d_kinds, count * 4 + 4));
     UA_HIP(scratch.allocate(&d_slots, count * 4 + 4));
     UA_HIP(scratch.allocate(&d_keys, count * 4 + 4));
-    UA_HIP(scratch.allocate(&d_popped, capacity * 8));
+    UA_HIP(scratch.allocate(&d_popped, (count + 1) * 8));
     UA_HIP(scratch.allocate(&d_top, (limit + 1) * 8));
-    UA_HIP(scratch.allocate(&d_counts, 8));
+    UA_HIP(scratch.allocate(&d_heap, capacity * 8));
+    UA_HIP(scratch.allocate(&d_memory, cells * 8));
+    UA_HIP(scratch.allocate(&d_counts, 12));
     UA_HIP(hipMemcpy(d_kinds, kinds, count * 4, hipMemcpyHostToDevice));
     UA_HIP(hipMemcpy(d_slots, slots, count * 4, hipMemcpyHostToDevice));
     UA_HIP(hipMemcpy(d_keys, keys, count * 4, hipMemcpyHostToDevice));
-    const size_t lds = (capacity + limit + 1) * 8;
-    hipLaunchKernelGGL(containers_kernel, dim3(1), dim3(64), lds, nullptr, d_kinds, d_keys, d_slots, (uint32_t)count, (uint32_t)limit,
-                       (uint32_t)capacity, d_popped, d_counts, d_top, d_counts + 1);
+    UA_HIP(hipMemset(d_memory, 0, cells * 8));
+    if (global_memory)
+        hipLaunchKernelGGL(containers_kernel<true>, dim3(1), dim3(64), 0, nullptr, d_kinds, d_keys, d_slots, (uint32_t)count, (uint32_t)limit,
+                           (uint32_t)capacity, d_memory, d_popped, d_counts, d_top, d_heap);
+    else
+        hipLaunchKernelGGL(containers_kernel<false>, dim3(1), dim3(64), cells * 8, nullptr, d_kinds, d_keys, d_slots, (uint32_t)count,
+                           (uint32_t)limit, (uint32_t)capacity, d_memory, d_popped, d_counts, d_top, d_heap);
     UA_HIP(hipGetLastError());
     UA_HIP(hipDeviceSynchronize());
-    uint32_t host_counts[2] = {0, 0};
-    UA_HIP(hipMemcpy(host_counts, d_counts, 8, hipMemcpyDeviceToHost));
+    uint32_t host_counts[3] = {0, 0, 0};
+    UA_HIP(hipMemcpy(host_counts, d_counts, 12, hipMemcpyDeviceToHost));
     *popped_count = host_counts[0];
     *top_count = host_counts[1];
     UA_HIP(hipMemcpy(popped, d_popped, host_counts[0] * 8, hipMemcpyDeviceToHost));
     UA_HIP(hipMemcpy(top, d_top, host_counts[1] * 8, hipMemcpyDeviceToHost));
+    if (heap_count)
+        *heap_count = host_counts[2];
+    if (heap)
+        UA_HIP(hipMemcpy(heap, d_heap, host_counts[2] * 8, hipMemcpyDeviceToHost));
     return nullptr;
 }
 __attribute__((visibility("default"))) void usearch_amd_test_containers(uint32_t const* kinds, float const* keys, uint32_t const* slots, size_t count,
-                                 size_t limit, uint64_t* popped, size_t* popped_count, uint64_t* top, size_t* top_count,
-                                 usearch_amd_error_t* error) {
-    fail(error, test_containers(kinds, keys, slots, count, limit, popped, popped_count, top, top_count));
+                                 size_t limit, int global_memory, uint64_t* popped, size_t* popped_count, uint64_t* top, size_t* top_count,
+                                 uint64_t* heap, size_t* heap_count, usearch_amd_error_t* error) {
+    fail(error, test_containers(kinds, keys, slots, count, limit, global_memory, popped, popped_count, top, top_count, heap, heap_count));
+}
+
+/**
+ *  Self-test hook of `top` (`top_kernel` above): replays the script on the layout named by `epl` (1, 2, 4, 8, 16: registers; 0: scratch
+ *  memory), `flags` (the frontier flags, registers only) and `global_memory` (epl 0 only: device memory instead of LDS).
+ *  → `records` [count][6], `cell_bits` / `cell_slots` [64 · epl, or `limit` for epl 0] and the final size.
+ */
+static const char* test_top(uint32_t epl, int flags, int global_memory, uint32_t const* kinds, float const* keys, uint32_t const* slots,
+                            size_t count, size_t limit, uint32_t* records, uint32_t* cell_bits, uint32_t* cell_slots, uint32_t* final_size) {
+    if (epl != 0 && epl != 1 && epl != 2 && epl != 4 && epl != 8 && epl != 16)
+        return "No such layout of `top`";
+    if (!limit || (epl && limit > 64u * epl) || (!epl && flags) || (epl && global_memory))
+        return "The layout cannot hold this script";
+    if (!epl && !global_memory && (limit + 1) * 8 > 64 * 1024)
+        return "The buffer does not fit into LDS";
+    const size_t cells = epl ? 64u * epl : limit;
+    uint32_t *d_kinds = nullptr, *d_slots = nullptr, *d_records = nullptr, *d_bits = nullptr, *d_cell_slots = nullptr, *d_size = nullptr;
+    float* d_keys = nullptr;
+    cand_t* d_memory = nullptr;
+    device_scratch_t scratch(current_device_k);
+    UA_HIP(scratch.allocate(&d_kinds, count * 4 + 4));
+    UA_HIP(scratch.allocate(&d_slots, count * 4 + 4));
+    UA_HIP(scratch.allocate(&d_keys, count * 4 + 4));
+    UA_HIP(scratch.allocate(&d_records, count * top_record_words_k * 4 + 4));
+    UA_HIP(scratch.allocate(&d_bits, cells * 4));
+    UA_HIP(scratch.allocate(&d_cell_slots, cells * 4));
+    UA_HIP(scratch.allocate(&d_memory, (limit + 1) * 8));
+    UA_HIP(scratch.allocate(&d_size, 4));
+    UA_HIP(hipMemcpy(d_kinds, kinds, count * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_slots, slots, count * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_keys, keys, count * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_bits, cell_bits, cells * 4, hipMemcpyHostToDevice)); // the caller's pattern: a cell never written shows
+    UA_HIP(hipMemcpy(d_cell_slots, cell_slots, cells * 4, hipMemcpyHostToDevice));
+    const size_t lds = epl || global_memory ? 0 : (limit + 1) * 8;
+#define USEARCH_AMD_TOP_LAYOUT(E, G, F)                                                                                                       \
+    hipLaunchKernelGGL((top_kernel<E, G, F>), dim3(1), dim3(64), lds, nullptr, d_kinds, d_keys, d_slots, (uint32_t)count, (uint32_t)limit,      \
+                       d_memory, d_records, d_bits, d_cell_slots, d_size)
+#define USEARCH_AMD_TOP_REGISTERS(E)                                                                                                          \
+    case E:                                                                                                                                   \
+        if (flags)                                                                                                                            \
+            USEARCH_AMD_TOP_LAYOUT(E, false, true);                                                                                           \
+        else                                                                                                                                  \
+            USEARCH_AMD_TOP_LAYOUT(E, false, false);                                                                                          \
+        break
+    switch (epl) {
+        USEARCH_AMD_TOP_REGISTERS(1);
+        USEARCH_AMD_TOP_REGISTERS(2);
+        USEARCH_AMD_TOP_REGISTERS(4);
+        USEARCH_AMD_TOP_REGISTERS(8);
+        USEARCH_AMD_TOP_REGISTERS(16);
+    default:
+        if (global_memory)
+            USEARCH_AMD_TOP_LAYOUT(0, true, false);
+        else
+            USEARCH_AMD_TOP_LAYOUT(0, false, false);
+    }
+#undef USEARCH_AMD_TOP_REGISTERS
+#undef USEARCH_AMD_TOP_LAYOUT
+    UA_HIP(hipGetLastError());
+    UA_HIP(hipDeviceSynchronize());
+    UA_HIP(hipMemcpy(records, d_records, count * top_record_words_k * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(cell_bits, d_bits, cells * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(cell_slots, d_cell_slots, cells * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(final_size, d_size, 4, hipMemcpyDeviceToHost));
+    return nullptr;
+}
+__attribute__((visibility("default"))) void usearch_amd_test_top(uint32_t epl, int flags, int global_memory, uint32_t const* kinds,
+                                                                  float const* keys, uint32_t const* slots, size_t count, size_t limit,
+                                                                  uint32_t* records, uint32_t* cell_bits, uint32_t* cell_slots,
+                                                                  uint32_t* final_size, usearch_amd_error_t* error) {
+    fail(error, test_top(epl, flags, global_memory, kinds, keys, slots, count, limit, records, cell_bits, cell_slots, final_size));
+}
+
+/**
+ *  Self-test hook of the fold of per-shard lists: `distances` / `keys` [shards][queries][wanted] and `counts` [shards][queries] →
+ *  [queries][wanted] and [queries], with the order inside a shard the caller names (`later_position_first`, merge_core.hpp).
+ *  `on_host` = 0: `merge_kernel` through `merge_shards_device`; 1: `merge_rank` as the host path of the sharded step walks it
+ *  (`merge_blocks_host` of sharded.hip: every kept element, cells from `found` on padded). Either way the caller's output buffers are
+ *  the memory the merge writes into — on the device a copy of them — so a cell it never writes keeps the caller's pattern.
+ */
+static const char* test_merge(float const* distances, uint64_t const* keys, uint64_t const* counts, size_t shards, size_t queries, size_t wanted,
+                              int later_position_first, int on_host, float* out_distances, uint64_t* out_keys, uint64_t* out_counts) {
+    const size_t cells = shards * queries * wanted, rows = shards * queries;
+    if (!cells)
+        return nullptr;
+    if (on_host) {
+        std::vector<float> pool(shards * wanted);
+        std::vector<std::uint32_t> kept(shards);
+        for (size_t q = 0; q < queries; ++q) {
+            size_t available = 0;
+            for (size_t shard = 0; shard < shards; ++shard) {
+                kept[shard] = (std::uint32_t)std::min<std::uint64_t>(counts[shard * queries + q], wanted);
+                available += kept[shard];
+                std::copy_n(distances + (shard * queries + q) * wanted, wanted, pool.data() + shard * wanted);
+            }
+            const size_t found = std::min(available, wanted);
+            for (size_t shard = 0; shard < shards; ++shard)
+                for (std::uint32_t position = 0; position < kept[shard]; ++position) {
+                    const std::uint32_t rank = merge_rank(pool.data(), kept.data(), (std::uint32_t)shards, (std::uint32_t)wanted,
+                                                          (std::uint32_t)shard, position, later_position_first != 0);
+                    if (rank >= wanted)
+                        continue;
+                    out_distances[q * wanted + rank] = pool[shard * wanted + position];
+                    out_keys[q * wanted + rank] = keys[(shard * queries + q) * wanted + position];
+                }
+            for (size_t i = found; i < wanted; ++i) {
+                out_keys[q * wanted + i] = 0;
+                std::memcpy(out_distances + q * wanted + i, &signaling_nan_bits_k, 4);
+            }
+            out_counts[q] = found;
+        }
+        return nullptr;
+    }
+    float *d_distances = nullptr, *d_out_distances = nullptr;
+    uint64_t *d_keys = nullptr, *d_counts = nullptr, *d_out_keys = nullptr, *d_out_counts = nullptr;
+    device_scratch_t scratch(current_device_k);
+    UA_HIP(scratch.allocate(&d_distances, cells * 4));
+    UA_HIP(scratch.allocate(&d_keys, cells * 8));
+    UA_HIP(scratch.allocate(&d_counts, rows * 8));
+    UA_HIP(scratch.allocate(&d_out_distances, queries * wanted * 4));
+    UA_HIP(scratch.allocate(&d_out_keys, queries * wanted * 8));
+    UA_HIP(scratch.allocate(&d_out_counts, queries * 8));
+    UA_HIP(hipMemcpy(d_distances, distances, cells * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_keys, keys, cells * 8, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_counts, counts, rows * 8, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_out_distances, out_distances, queries * wanted * 4, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_out_keys, out_keys, queries * wanted * 8, hipMemcpyHostToDevice));
+    UA_HIP(hipMemcpy(d_out_counts, out_counts, queries * 8, hipMemcpyHostToDevice));
+    if (const char* message = merge_shards_device(d_distances, d_keys, d_counts, shards, queries, wanted, d_out_distances, d_out_keys,
+                                                  d_out_counts, nullptr, later_position_first != 0))
+        return message;
+    UA_HIP(hipMemcpy(out_distances, d_out_distances, queries * wanted * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(out_keys, d_out_keys, queries * wanted * 8, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(out_counts, d_out_counts, queries * 8, hipMemcpyDeviceToHost));
+    return nullptr;
+}
+__attribute__((visibility("default"))) void usearch_amd_test_merge(float const* distances, uint64_t const* keys, uint64_t const* counts,
+                                                                    size_t shards, size_t queries, size_t wanted, int later_position_first,
+                                                                    int on_host, float* out_distances, uint64_t* out_keys,
+                                                                    uint64_t* out_counts, usearch_amd_error_t* error) {
+    fail(error, test_merge(distances, keys, counts, shards, queries, wanted, later_position_first, on_host, out_distances, out_keys, out_counts));
 }
 
 /**

@@ -1247,9 +1247,15 @@ def test_hooks() -> C.CDLL:
             probe = getattr(_test_hooks, f"usearch_amd_test_{name}")
             probe.restype = C.c_float
             probe.argtypes = arguments + [C.POINTER(C.c_char_p)]
-        _test_hooks.usearch_amd_test_containers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
-                                                            C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t),
-                                                            C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_containers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                                            C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p,
+                                                            C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_merge.restype = None
+        _test_hooks.usearch_amd_test_merge.argtypes = [C.c_void_p] * 3 + [C.c_size_t] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [
+            C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_top.restype = None
+        _test_hooks.usearch_amd_test_top.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p)]
         _test_hooks.usearch_amd_test_sketch_bounds.restype = None
         _test_hooks.usearch_amd_test_sketch_bounds.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
                                                                C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p)]
@@ -1482,22 +1488,73 @@ def test_device_scratch(home: int, current: int) -> dict:
             "refused": int(refused.value), "refused_pointer": int(refused_pointer.value or 0)}
 
 
-def test_containers(kinds: np.ndarray, keys: np.ndarray, slots: np.ndarray, limit: int):
-    """Device container self-test hook → (popped[(key, slot)], top[(distance, slot)])."""
+def test_containers(kinds: np.ndarray, keys: np.ndarray, slots: np.ndarray, limit: int, global_memory: bool = False, remains: bool = False):
+    """Device container self-test hook → (popped[(key, slot)], top[(distance, slot)]), and with `remains` the heap's cells as they lie
+    after the script as a third pair. `global_memory`: heap and buffer in device memory (the all-global fallback's accessors), else LDS."""
     kinds = np.ascontiguousarray(kinds, dtype=np.uint32)
     keys = np.ascontiguousarray(keys, dtype=np.float32)
     slots = np.ascontiguousarray(slots, dtype=np.uint32)
     n = len(kinds)
     popped = np.zeros(n + 1, dtype=np.uint64)
     top = np.zeros(limit + 1, dtype=np.uint64)
-    popped_count, top_count = C.c_size_t(), C.c_size_t()
+    heap = np.zeros(int((kinds == 0).sum()) + 1, dtype=np.uint64)
+    popped_count, top_count, heap_count = C.c_size_t(), C.c_size_t(), C.c_size_t()
     err = C.c_char_p()
-    test_hooks().usearch_amd_test_containers(_pointer(kinds), _pointer(keys), _pointer(slots), n, limit, _pointer(popped),
-                                          C.byref(popped_count), _pointer(top), C.byref(top_count), C.byref(err))
+    test_hooks().usearch_amd_test_containers(_pointer(kinds), _pointer(keys), _pointer(slots), n, limit, int(bool(global_memory)),
+                                             _pointer(popped), C.byref(popped_count), _pointer(top), C.byref(top_count), _pointer(heap),
+                                             C.byref(heap_count), C.byref(err))
     _raise(err, "usearch_amd_test_containers")
 
     def unpack(a):
         bits = (a & np.uint64(0xFFFFFFFF)).astype(np.uint32)
         return bits.view(np.float32), (a >> np.uint64(32)).astype(np.uint32)
 
-    return unpack(popped[: popped_count.value]), unpack(top[: top_count.value])
+    pairs = unpack(popped[: popped_count.value]), unpack(top[: top_count.value])
+    return pairs + (unpack(heap[: heap_count.value]),) if remains else pairs
+
+
+TOP_CLOSED_BIT = 0x80000000  # `top_gt::closed_bit_k`: the frontier flag in a cell's slot word
+TOP_NONE = 0xFFFFFFFF  # `none_slot_k`
+
+
+def test_top(epl: int, flags: bool, global_memory: bool, kinds: np.ndarray, keys: np.ndarray, slots: np.ndarray, limit: int):
+    """Self-test hook of `top` as the search kernels hold it: one wave replays the script on `top_gt<epl, global_memory, flags>` (epl
+    1, 2, 4, 8, 16 = cells per lane in registers; 0 = scratch memory, LDS or with `global_memory` device memory). kinds: 0 = insert
+    under the traversal's acceptance rule, 1 = the same, closed on arrival (flagged layouts), 2 = `first_open` + `close`.
+    → (records uint32[n, 6] = accepted-or-found, size, radius bits, popped distance bits, popped slot, popped cell number;
+    cell distance bits and cell slot words, all 64 · epl cells of a register layout or the first `size` of a scratch one; size).
+    Cells the kernel does not write come back as 0xDEADBEEF."""
+    kinds = np.ascontiguousarray(kinds, dtype=np.uint32)
+    keys = np.ascontiguousarray(keys, dtype=np.float32)
+    slots = np.ascontiguousarray(slots, dtype=np.uint32)
+    n, cells = len(kinds), (64 * epl if epl else limit)
+    records = np.zeros((n, 6), dtype=np.uint32)
+    cell_bits = np.full(cells, 0xDEADBEEF, dtype=np.uint32)
+    cell_slots = np.full(cells, 0xDEADBEEF, dtype=np.uint32)
+    size, err = C.c_uint32(), C.c_char_p()
+    test_hooks().usearch_amd_test_top(epl, int(bool(flags)), int(bool(global_memory)), _pointer(kinds), _pointer(keys), _pointer(slots), n,
+                                      limit, _pointer(records), _pointer(cell_bits), _pointer(cell_slots), C.byref(size), C.byref(err))
+    _raise(err, "usearch_amd_test_top")
+    shown = cells if epl else int(size.value)
+    return records, cell_bits[:shown], cell_slots[:shown], int(size.value)
+
+
+def test_merge(distances: np.ndarray, keys: np.ndarray, counts: np.ndarray, later_position_first: bool = True, on_host: bool = False,
+               key_sentinel: int = 0xABABABABABABABAB, distance_sentinel_bits: int = 0xCDCDCDCD):
+    """Self-test hook of the fold of per-shard lists, `merge_many` with the order inside a shard exposed: `later_position_first` as
+    `merge_into` (the sharded step), False = the earlier position in front (the partitions of an exact search). `on_host`: `merge_rank`
+    walked as the sharded step's host path walks it, no device involved; else the merge kernel. The output buffers hold the sentinels
+    before the merge, so a cell it never writes shows. → ([Q, k] keys, distances, [Q] counts)."""
+    distances = np.ascontiguousarray(distances, dtype=np.float32)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    shards, queries, wanted = distances.shape
+    out_d = np.full((queries, wanted), distance_sentinel_bits, dtype=np.uint32).view(np.float32)
+    out_k = np.full((queries, wanted), key_sentinel, dtype=np.uint64)
+    out_c = np.full(queries, key_sentinel, dtype=np.uint64)
+    err = C.c_char_p()
+    test_hooks().usearch_amd_test_merge(_pointer(distances), _pointer(keys), _pointer(counts), shards, queries, wanted,
+                                        int(bool(later_position_first)), int(bool(on_host)), _pointer(out_d), _pointer(out_k),
+                                        _pointer(out_c), C.byref(err))
+    _raise(err, "usearch_amd_test_merge")
+    return out_k, out_d, out_c
