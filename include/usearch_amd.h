@@ -82,10 +82,9 @@ typedef struct usearch_amd_stats_t {
     float span_ms;           /**< with wave_clock: first wave start → last wave exit, device wall clock */
     uint32_t top_cells;      /**< cells of `top` per lane in registers (1, 4, 8, 16), 0 = `top` in scratch memory; with mode,
                                   variant and frontier this names the kernel instantiation of the first launch */
-    uint32_t probe_mode;     /**< short rows over a global visited-set slab: 0 = one compare-and-swap per probe, 1 = a load first and the
-                                  swap only to claim, 2 = no atomic at all (loads, plain stores, claims settled by bits in LDS) */
-    uint32_t seen_cells;     /**< … `seen` cells in LDS in front of the slab */
-    uint32_t claim_bits;     /**< … claim bits in LDS (probe_mode 2) */
+    uint32_t probe_mode;     /**< always 0, kept for layout (the visited-set slab is probed by compare-and-swap) */
+    uint32_t seen_cells;     /**< short rows over a global visited-set slab: `seen` cells in LDS in front of the slab */
+    uint32_t claim_bits;     /**< always 0, kept for layout */
     uint32_t early_rows;     /**< rows of ≤ 128 bytes: 1 = a hop's rows were gathered next to the probe of the visited set, not behind it */
     uint32_t plain;          /**< rows of ≤ 128 bytes: 1 = the launch ran the kernel build cut for plain batches (level 0, no predicate, no
                                   tombstones, lists of ≤ 64 cells); USEARCH_AMD_NO_PLAIN=1 keeps the general build. Same results */

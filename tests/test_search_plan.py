@@ -12,8 +12,8 @@ RECORDS = plans.load_golden()
 DECIDED = [name for name in plans.STAT_FIELDS if not name.startswith("sketch_")]  # (the sketch's two counters are measured)
 # `read_search_knobs` with nothing set (hash_load_pct: 50 for rows of 8 lanes, 75 below)
 NO_KNOBS = dict(lds_budget=160 * 1024, hash_cap=0, hash_load_pct=None, next_cap=0, mode=0, top_in_memory=0, no_two_cells=0, frontier=0, variant=0,
-                no_team=0, no_plain=0, waves_per_cu=32, no_small_batch_lds=0, early_rows=1, claim_bits=0, aside_cells=0,
-                plain_whatever_the_room=0, seen_cells=2 ** 64 - 1, probe_mode=0, probe_load_first=0)
+                no_team=0, no_plain=0, waves_per_cu=32, no_small_batch_lds=0, early_rows=1, aside_cells=0,
+                plain_whatever_the_room=0, seen_cells=2 ** 64 - 1)
 
 
 def planned(record, knobs=None):

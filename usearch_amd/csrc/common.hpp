@@ -150,7 +150,8 @@ struct search_args_t {
     std::uint32_t exclude_own;       ///< 1 = query q's own stored row (`query_ids[q]`) routes but never becomes a result candidate:
                                      ///< `search_to_update_` (index.hpp:4087-4170), the insertion search of a member that is
                                      ///< being re-linked in place
-    unsigned long long* phases;     ///< optional [8] diagnostic: shader-clock ticks per phase summed over all waves
+    unsigned long long* phases;     ///< optional [16] diagnostic (kernels.hpp `phase_clock_t`): shader-clock ticks per phase [0 … 5] and the
+                                    ///< clock's counters [6 … 15], summed over all waves
     std::uint32_t team_offset;      ///< team_search_kernel: where in the workgroup's LDS the shared `team_t` sits
     unsigned long long* wave_clock; ///< optional [grid][2] telemetry: 100-MHz wall clock at the start and the exit of every
                                     ///< persistent wave (how long the drain phase of a batch leaves the chip part-idle)
@@ -158,10 +159,9 @@ struct search_args_t {
     std::uint32_t seen_cells;       ///< sit, and how many (a power of two; 0 = none) — see `search_one`
     std::uint32_t early_rows;       ///< rows of ≤ 128 bytes (G = 2): 1 = a hop's rows are gathered next to the probe of the visited set
                                     ///< instead of behind it (`search_one`, the hop loop)
-    std::uint32_t probe_mode;       ///< how those walks probe the slab (`probe_mode_t`): compare-and-swap, a load first and the swap
-                                    ///< only to claim, or no atomic at all (loads + plain stores, claims settled in LDS)
-    std::uint32_t claim_offset;     ///< `probe_plain_k`: where in the wave's LDS the claim bits sit, and how many (a power of two,
-    std::uint32_t claim_bits;       ///< ≤ hash_cap; one bit per cell when equal, else cell & (bits − 1))
+    std::uint32_t probe_mode;       ///< always 0: what is left of the two ways to probe the slab that lost to compare-and-swap (DESIGN.md
+    std::uint32_t claim_offset;     ///< §3.2), with the one test of it in `search_one`. Kept because the general short-row builds allocate
+    std::uint32_t claim_bits;       ///< their registers differently without them (profiles/walk_cleanup/): to be removed with a measurement.
     std::uint32_t aside_offset;     ///< the cut for plain batches (`plain_ak`): where in the wave's LDS the members sit whose home cell in the
     std::uint32_t aside_cells;      ///< slab was taken, and how many cells (a power of two) — the slab is probed at the home cell only
     unsigned long long* sketch_counters; ///< [2]: candidates tested against the sketch / pruned by it, summed over the launch; null = this
@@ -170,13 +170,5 @@ struct search_args_t {
 };
 
 enum : std::uint32_t { status_done_k = 0, status_overflow_k = 1 };
-
-/// How a short-row walk probes its wave-private visited-set slab in global memory (kernels.hpp `search_one`).
-enum probe_mode_t : std::uint32_t {
-    probe_swap_k = 0,       ///< one compare-and-swap per probe (executed at the memory side: 27.5 G a second chip-wide)
-    probe_load_first_k = 1, ///< a load, and the swap only to claim an empty cell (round 5's experiment: two round trips per fresh slot)
-    probe_plain_k = 2,      ///< no atomic: a load that bypasses the vector cache, a plain store nobody waits for, and the claims of
-                            ///< one instruction's lanes on the same cell settled by an LDS bit per cell
-};
 
 } // namespace usearch_amd

@@ -22,22 +22,6 @@
 
 namespace usearch_amd {
 
-/// The block of per-wave visited-set slabs. (Round 5's experiment — the block in uncached or fine-grained device memory, to see whether
-/// the two-microsecond trip of a probe belongs to the memory type: it does not, profiles/r05_short_rows/ — compiles in only with
-/// -DUSEARCH_AMD_EXPERIMENT_SCRATCH_MEMORY: USEARCH_AMD_SCRATCH_MEMORY = 1 `hipDeviceMallocUncached`, 2 `hipDeviceMallocFinegrained`.)
-static hipError_t scratch_malloc(void** out, std::size_t bytes) {
-#ifdef USEARCH_AMD_EXPERIMENT_SCRATCH_MEMORY
-    const std::size_t kind = env_size("USEARCH_AMD_SCRATCH_MEMORY", 0);
-    if (kind == 1 || kind == 2) {
-        const hipError_t e = hipExtMallocWithFlags(out, bytes, kind == 1 ? hipDeviceMallocUncached : hipDeviceMallocFinegrained);
-        if (e == hipSuccess)
-            return e;
-        (void)hipGetLastError();
-    }
-#endif
-    return block_malloc(out, bytes);
-}
-
 void row_geometry(std::size_t bytes, std::uint32_t& lanes, std::uint32_t& row_stride, std::uint32_t& chunks) {
     // lanes per row (G): the smallest power of two covering the row's 16-byte chunks, at most 8 (= one 128-byte line per
     // load). USEARCH_AMD_LANES overrides (1, 2, 4, 8): fewer lanes per row = more rows per round trip.
@@ -144,7 +128,7 @@ const char* workspace_t::reserve(std::size_t queries_wanted, std::size_t scratch
             placed_free(d_scratch);
         d_scratch = nullptr;
         scratch_bytes = 0;
-        UA_HIP(scratch_malloc((void**)&d_scratch, scratch_wanted)); // big blocks for chip-filling launches are drawn by run_ladder
+        UA_HIP(block_malloc((void**)&d_scratch, scratch_wanted)); // big blocks for chip-filling launches are drawn by run_ladder
         scratch_bytes = scratch_wanted;
     }
     return nullptr;
@@ -829,7 +813,6 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
     if (rung.mode != scratch_global_k) {
         args.seen_offset = rung.seen_offset, args.seen_cells = rung.seen_cells;
         args.aside_offset = rung.aside_offset, args.aside_cells = rung.aside_cells;
-        args.probe_mode = rung.probe_mode, args.claim_offset = rung.claim_offset, args.claim_bits = rung.claim_bits;
         args.early_rows = rung.early_rows, args.sketch_offset = rung.sketch_offset, args.team_offset = rung.team_offset;
         const std::uint32_t grid = rung.grid;
         const std::uint64_t slab = rung.slab;
@@ -869,7 +852,7 @@ const char* snapshot_t::run_ladder(search_call_t& call) {
                 std::fprintf(stderr, " ms\n");
             }
             for (; drawn < scratch_draws && !failure; ++drawn) {
-                if (scratch_malloc(&candidates[drawn], slab * grid) != hipSuccess) {
+                if (block_malloc(&candidates[drawn], slab * grid) != hipSuccess) {
                     (void)hipGetLastError();
                     candidates[drawn] = nullptr;
                     break;

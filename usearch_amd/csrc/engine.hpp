@@ -55,9 +55,9 @@ struct search_stats_t {
                                          ///< that waves spent gone (the drain phase of the batch), first launch
     float span_ms = 0.f;                 ///< with `wave_clock`: first start → last exit on the device's 100-MHz clock
     std::uint32_t top_cells = 0;         ///< `top` cells per lane in registers of the first launch (0 = scratch memory)
-    std::uint32_t probe_mode = 0;        ///< short rows over a global slab: `probe_mode_t` of the last launch
-    std::uint32_t seen_cells = 0;        ///< … its `seen` cells in LDS
-    std::uint32_t claim_bits = 0;        ///< … its claim bits in LDS (`probe_plain_k`)
+    std::uint32_t probe_mode = 0;        ///< always 0, kept for layout (the slab is probed by compare-and-swap: DESIGN.md §3.2)
+    std::uint32_t seen_cells = 0;        ///< short rows over a global slab: the `seen` cells in LDS of the last launch
+    std::uint32_t claim_bits = 0;        ///< always 0, kept for layout
     std::uint32_t early_rows = 0;        ///< rows of ≤ 128 bytes: 1 = gathered next to the probe of the visited set, not behind it
     std::uint32_t plain = 0;             ///< short rows: 1 = the last launch ran the build cut for plain batches (kernels.hpp `plain_ak`)
     std::uint32_t aside_cells = 0;       ///< … and its LDS cells for the members whose home cell in the slab was taken
@@ -99,9 +99,8 @@ struct search_knobs_t {
     std::size_t lds_budget = 160 * 1024; ///< LDS_BUDGET: bytes of a compute unit's LDS the resident waves may share
     std::size_t hash_cap = 0, hash_load_pct = 50; ///< HASH_LOAD_PCT: 10 … 75, by default 50 for rows of 8 lanes and 75 below
     std::size_t next_cap = 0, mode = 0, top_in_memory = 0, no_two_cells = 0, frontier = 0, variant = 0, no_team = 0, no_plain = 0;
-    std::size_t waves_per_cu = 32, no_small_batch_lds = 0, early_rows = 1, claim_bits = 0, aside_cells = 0, plain_whatever_the_room = 0;
+    std::size_t waves_per_cu = 32, no_small_batch_lds = 0, early_rows = 1, aside_cells = 0, plain_whatever_the_room = 0;
     std::size_t seen_cells = (std::size_t)-1; ///< SEEN_CELLS: −1 = as many as cost no resident wave, 0 = none
-    std::size_t probe_mode = 0, probe_load_first = 0; ///< read under USEARCH_AMD_EXPERIMENT_PROBE_MODES only
 };
 
 /// What the planner needs to know about the index and the call.
@@ -121,7 +120,7 @@ struct search_plan_t {
     std::uint32_t plain_possible = 0; ///< short rows: nothing known before the first rung rules the build cut for plain batches out
     std::uint32_t sketch = 0;         ///< the walk tests candidates against the sketch, until a rung finds no LDS for its coefficients
     /// The decisions as `search_stats_t` reports them — `plan_search`: frontier, variant, top_cells; `plan_rung`: early_rows, plain,
-    /// aside_cells, over short rows probe_mode, seen_cells, claim_bits, and variant again when a team is demoted — next to which
+    /// aside_cells, over short rows seen_cells, and variant again when a team is demoted — next to which
     /// the engine writes what the device did.
     search_stats_t stats{};
 };
@@ -130,7 +129,7 @@ struct search_plan_t {
 struct search_rung_t {
     std::int32_t mode = 0, frontier = 0;
     std::uint32_t team = 0, plain = 0, entries_per_lane = 0, grid = 0, lds_bytes = 0, hash_cap = 0, next_cap = 0;
-    std::uint32_t early_rows = 0, probe_mode = 0, claim_offset = 0, claim_bits = 0, aside_offset = 0, aside_cells = 0, seen_offset = 0,
+    std::uint32_t early_rows = 0, aside_offset = 0, aside_cells = 0, seen_offset = 0,
         seen_cells = 0, sketch_offset = 0, team_offset = 0;
     std::uint64_t slab = 0;                            ///< bytes of global scratch per wave
     std::uint64_t visits_offset = 0, bitmap_bytes = 0; ///< the global rung: where in a slab the bitmap sits, which the host zeroes

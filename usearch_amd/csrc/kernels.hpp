@@ -1258,6 +1258,142 @@ UA_DEVICE void team_share(const snapshot_view_t& ix, const std::uint8_t* query_l
 }
 
 /**
+ *  The diagnostic phase clock of the walk (`make PHASES=1`, read with USEARCH_AMD_PHASES=1 at run time): shader-clock ticks per
+ *  phase — 0 setup + descent, 1 pop + list fetch, 2 visited set, 3 distances, 4 commit, 5 result dump — and a few counters, summed
+ *  over all waves into `search_args_t::phases`. The clock reads cost registers and waits, so a product build gets the second
+ *  definition: the same members with empty bodies, nothing of it reaches the kernels.
+ */
+#ifdef USEARCH_AMD_PHASES
+struct phase_clock_t {
+    unsigned long long* out;   // `args.phases`; null = the clock stands still
+    std::uint32_t row_groups;  // rows one round of one row per lane group holds (a sketch hop with more survivors is "wide")
+    std::uint64_t mark = 0, ticks[6] = {0, 0, 0, 0, 0, 0};
+    std::uint32_t pushes = 0, ready = 0, rechecks = 0, sketch_hops = 0, wide_hops = 0;
+    std::uint64_t push_ticks = 0, insert_ticks = 0, bound_ticks = 0;
+    std::uint64_t push_t0 = 0, push_t1 = 0;
+    std::uint64_t helper_busy = 0, helper_idle = 0, helper_hops = 0;
+    UA_DEVICE phase_clock_t(const search_args_t& args, std::uint32_t row_groups) : out(args.phases), row_groups(row_groups) {
+        mark = out ? __builtin_amdgcn_s_memtime() : 0;
+    }
+    UA_DEVICE void tick(int phase) {
+        if (out) {
+            const std::uint64_t now = __builtin_amdgcn_s_memtime();
+            ticks[phase] += now - mark;
+            mark = now;
+        }
+    }
+    /// The sketch's share of phase 3: records and bounds (the mark stays, phase 3 still sums to the whole), the hops that took the
+    /// sketch path and those of them with more survivors than one round of one row per lane group holds.
+    UA_DEVICE void tick_bounds(std::uint32_t kept) {
+        if (out) {
+            bound_ticks += __builtin_amdgcn_s_memtime() - mark;
+            ++sketch_hops;
+            wide_hops += kept > row_groups ? 1u : 0u;
+        }
+    }
+    UA_DEVICE void list_ready(bool was_ready) { ready += was_ready ? 1u : 0u; } ///< a hop whose list had been requested ahead
+    UA_DEVICE void recheck() { ++rechecks; }                                    ///< a candidate looked at again inside the commit
+    UA_DEVICE void push_begin() { ++pushes, push_t0 = __builtin_amdgcn_s_memtime(); }
+    UA_DEVICE void push_middle() { push_t1 = __builtin_amdgcn_s_memtime(); }
+    UA_DEVICE void push_end() { push_ticks += push_t1 - push_t0, insert_ticks += __builtin_amdgcn_s_memtime() - push_t1; }
+    /// `one_wave`: [11 … 15] belong to a team's helpers otherwise.
+    UA_DEVICE void flush(const search_args_t& args, std::uint32_t lane, bool one_wave) {
+        if (!args.phases || lane != 0)
+            return;
+#pragma unroll
+        for (int phase = 0; phase < 6; ++phase)
+            atomicAdd(args.phases + phase, (unsigned long long)ticks[phase]);
+        atomicAdd(args.phases + 6, (unsigned long long)pushes);
+        atomicAdd(args.phases + 7, (unsigned long long)ready);
+        atomicAdd(args.phases + 8, (unsigned long long)push_ticks);
+        atomicAdd(args.phases + 9, (unsigned long long)insert_ticks);
+        atomicAdd(args.phases + 10, (unsigned long long)rechecks);
+        if (one_wave) {
+            atomicAdd(args.phases + 11, (unsigned long long)bound_ticks);
+            atomicAdd(args.phases + 12, (unsigned long long)sketch_hops);
+            atomicAdd(args.phases + 13, (unsigned long long)wide_hops);
+        }
+    }
+    /// A team's helper: what it spent waiting for the leader to publish a hop, and measuring its share between the hop's two barriers.
+    UA_DEVICE void helper_woke() {
+        if (out) {
+            const std::uint64_t now = __builtin_amdgcn_s_memtime();
+            helper_idle += now - mark, mark = now;
+        }
+    }
+    UA_DEVICE void helper_measured() {
+        if (out) {
+            const std::uint64_t now = __builtin_amdgcn_s_memtime();
+            helper_busy += now - mark, mark = now, ++helper_hops;
+        }
+    }
+    /// [11 … 14] what each helper (waves 1 … 4) spent measuring, [15] the first one's hops.
+    UA_DEVICE void flush_helper(const search_args_t& args, std::uint32_t lane, std::uint32_t wave) {
+        if (!args.phases || lane != 0)
+            return;
+        atomicAdd(args.phases + 10 + wave, (unsigned long long)helper_busy);
+        if (wave == 1)
+            atomicAdd(args.phases + 15, (unsigned long long)helper_hops);
+    }
+};
+#else
+struct phase_clock_t {
+    UA_DEVICE phase_clock_t(const search_args_t&, std::uint32_t) {}
+    UA_DEVICE void tick(int) {}
+    UA_DEVICE void tick_bounds(std::uint32_t) {}
+    UA_DEVICE void list_ready(bool) {}
+    UA_DEVICE void recheck() {}
+    UA_DEVICE void push_begin() {}
+    UA_DEVICE void push_middle() {}
+    UA_DEVICE void push_end() {}
+    UA_DEVICE void flush(const search_args_t&, std::uint32_t, bool) {}
+    UA_DEVICE void helper_woke() {}
+    UA_DEVICE void helper_measured() {}
+    UA_DEVICE void flush_helper(const search_args_t&, std::uint32_t, std::uint32_t) {}
+};
+#endif
+
+/// A lane's probe of the visited set's hash in a global slab (`scratch_hash_k`) or in LDS, in two halves: a compare-and-swap on the
+/// home cell `h`, then linear probing (index.hpp:1085-1211) until the slot or an empty cell is met. Both return what the cell held:
+/// `none_slot_k` — the slot was inserted, it is fresh — or the slot itself: visited. A lane that does not ask probes nothing and reads
+/// as visited. The general beam of `search_one` puts work between the halves, in the shadow of the first round trip. (Two other ways
+/// to probe a slab — a load first and the swap only to claim, and no atomic at all — were measured slower in round 6: DESIGN.md §3.2.)
+UA_DEVICE std::uint32_t probe_first(std::uint32_t* visits, std::uint32_t h, std::uint32_t slot, bool asks) {
+    std::uint32_t old = slot;
+    if (asks)
+        old = atomicCAS(visits + h, none_slot_k, slot);
+    return old;
+}
+UA_DEVICE std::uint32_t probe_rest(std::uint32_t* visits, std::uint32_t mask, std::uint32_t h, std::uint32_t slot, std::uint32_t old) {
+    while (old != none_slot_k && old != slot) {
+        h = (h + 1) & mask;
+        old = atomicCAS(visits + h, none_slot_k, slot);
+    }
+    return old;
+}
+
+/// The sketch's bound for the candidate whose record the eight lanes of a group hold, 16 bytes each (every lane of the group gets it).
+UA_DEVICE float sketch_record_bound(const uint4 v, const float4 q0, const float4 q1, std::uint32_t sub, float margin) {
+    const std::uint32_t last = sub == 7u ? 0u : v.w; // the last lane's last word is ρ, not two coefficients
+    float dot = 0.f;
+    dot = __builtin_fmaf(half_bits_to_float(v.x & 0xFFFFu), q0.x, dot);
+    dot = __builtin_fmaf(half_bits_to_float(v.x >> 16), q0.y, dot);
+    dot = __builtin_fmaf(half_bits_to_float(v.y & 0xFFFFu), q0.z, dot);
+    dot = __builtin_fmaf(half_bits_to_float(v.y >> 16), q0.w, dot);
+    dot = __builtin_fmaf(half_bits_to_float(v.z & 0xFFFFu), q1.x, dot);
+    dot = __builtin_fmaf(half_bits_to_float(v.z >> 16), q1.y, dot);
+    dot = __builtin_fmaf(half_bits_to_float(last & 0xFFFFu), q1.z, dot);
+    dot = __builtin_fmaf(half_bits_to_float(last >> 16), q1.w, dot);
+    float residual = sub == 7u ? __builtin_bit_cast(float, v.w) : 0.f;
+#pragma unroll
+    for (int offset = 1; offset < 8; offset <<= 1) {
+        dot += xor_lane(dot, offset);
+        residual += xor_lane(residual, offset);
+    }
+    return sketch_lower_bound(dot, residual, margin);
+}
+
+/**
  *  One query, start to finish. `heaps` = top/next/candidate arrays (LDS, or the slab in `scratch_global_k`), `visits` = the
  *  visited set (LDS hash, slab hash or slab bitmap). Returns false on scratch overflow (nothing written but `status`).
  */
@@ -1288,35 +1424,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
     const std::uint32_t visits_mask = global_ak ? 0u : args.hash_cap - 1;
     const std::uint32_t visits_limit = global_ak ? 0xFFFFFFFFu : args.hash_cap - args.hash_cap / 4; // 75 % load
 
-    // diagnostic phase clock (USEARCH_AMD_PHASES=1): 0 setup+descent, 1 pop+list fetch, 2 visited set, 3 distances,
-    // 4 commit, 5 result dump
-#ifdef USEARCH_AMD_PHASES // diagnostic build only (`make PHASES=1`): the clock reads cost registers and waits
-    std::uint64_t phase_mark = args.phases ? __builtin_amdgcn_s_memtime() : 0;
-    std::uint64_t phase_ticks[6] = {0, 0, 0, 0, 0, 0};
-    std::uint32_t diagnostic_pushes = 0, diagnostic_ready = 0, diagnostic_rechecks = 0;
-    std::uint64_t diagnostic_push_ticks = 0, diagnostic_insert_ticks = 0;
-    auto tick = [&](int phase) {
-        if (args.phases) {
-            const std::uint64_t now = __builtin_amdgcn_s_memtime();
-            phase_ticks[phase] += now - phase_mark;
-            phase_mark = now;
-        }
-    };
-    // the sketch's share of phase 3: records and bounds (the mark stays, phase 3 still sums to the whole), the hops that took the
-    // sketch path and those of them with more survivors than one round of one row per lane group holds
-    std::uint64_t diagnostic_bound_ticks = 0;
-    std::uint32_t diagnostic_sketch_hops = 0, diagnostic_wide_hops = 0;
-    auto tick_bounds = [&](std::uint32_t kept) {
-        if (args.phases) {
-            diagnostic_bound_ticks += __builtin_amdgcn_s_memtime() - phase_mark;
-            ++diagnostic_sketch_hops;
-            diagnostic_wide_hops += kept > 64u / lanes_ak ? 1u : 0u;
-        }
-    };
-#else
-    auto tick = [](int) {};
-    auto tick_bounds = [](std::uint32_t) {};
-#endif
+    phase_clock_t clock(args, 64u / lanes_ak);
     const std::uint64_t query_row = !plain_ak && args.query_ids ? args.query_ids[q] : q;
     const query_norm_t a2 = stage_query<metric_ak, scalar_ak, lanes_ak>(
         ix, args.queries + query_row * args.query_stride, query_lds);
@@ -1326,14 +1434,10 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
         const uint4 empty = {none_slot_k, none_slot_k, none_slot_k, none_slot_k};
         for (std::uint32_t i = lane; i < args.hash_cap / 4; i += 64)
             cells[i] = empty;
-#ifdef USEARCH_AMD_EXPERIMENT_NO_SLAB_CLEAR_WAIT // profiles/r05_short_rows/: what a clear-free visited set could save at most in TIME — the
-        wave_sync<false>();                        // clear's stores still go out, nobody waits for them (a probe may meet an uncleared cell)
-#else
         if constexpr (mode_ak == scratch_hash_k) // the stores must have reached L2 before this wave's atomics probe the cells
             wave_sync<true>();
         else
             wave_sync<false>();
-#endif
     }
 
     // ---- `seen`: an exact, lossy memory of this query's probes in LDS, in front of the visited set in its global slab (short rows).
@@ -1355,11 +1459,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
     // Measured on 20M-vector slices (profiles/r06_short_rows/README.md §4): i8 × 96 at expansion 80 +9.4 % over the general build
     // (the cut with the `seen` cells alone: +3 %), at 64 +8.4 % (+4.9 %); b1 × 128, whose rows travel with the lists and whose hop has
     // nothing to put in the shadow of a second probe round anyway, −1 … −3 %: that cut keeps the `seen` cells alone.
-#ifdef USEARCH_AMD_EXPERIMENT_NO_ASIDE // scripts/ A/B runs: the cut for plain batches with the `seen` cells alone
-    constexpr bool aside_ak = false;
-#else
     constexpr bool aside_ak = plain_ak && lanes_ak == 2;
-#endif
     std::uint32_t* seen = nullptr;
     std::uint32_t seen_mask = 0;
     std::uint32_t* aside = nullptr;
@@ -1379,7 +1479,10 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 seen[i] = none_slot_k;
             wave_sync<false>();
         }
-        if (!plain_ak && args.probe_mode == probe_plain_k) { // the claim bits (zero between probe rounds; zeroed once more per query: free)
+        // (What is left of the probe without atomics, DESIGN.md §3.2: the engine never sets `probe_mode`, the test is always false. It
+        // stays, with its three fields of `search_args_t`, because taking it out moves the registers of the general short-row builds —
+        // some kernels grow, some start to spill: profiles/walk_cleanup/ — and that wants a measurement, not a clean-up.)
+        if (!plain_ak && args.probe_mode == 2u) {
             std::uint32_t* claim = reinterpret_cast<std::uint32_t*>(query_lds + args.claim_offset);
             for (std::uint32_t i = lane; i < args.claim_bits / 32; i += 64)
                 claim[i] = 0u;
@@ -1429,26 +1532,6 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
         measure_rows<metric_ak, scalar_ak, lanes_ak, loads_ak, global_ak, 1>(ix, query_lds, a2, cand_slots, cand_distances,
                                                                             count);
         computed += count;
-    };
-    // the sketch's bound for the candidate whose record the eight lanes of a group hold, 16 bytes each (every lane of the group gets it)
-    auto record_bound = [&](const uint4 v, const float4 q0, const float4 q1, std::uint32_t sub) -> float {
-        const std::uint32_t last = sub == 7u ? 0u : v.w; // the last lane's last word is ρ, not two coefficients
-        float dot = 0.f;
-        dot = __builtin_fmaf(half_bits_to_float(v.x & 0xFFFFu), q0.x, dot);
-        dot = __builtin_fmaf(half_bits_to_float(v.x >> 16), q0.y, dot);
-        dot = __builtin_fmaf(half_bits_to_float(v.y & 0xFFFFu), q0.z, dot);
-        dot = __builtin_fmaf(half_bits_to_float(v.y >> 16), q0.w, dot);
-        dot = __builtin_fmaf(half_bits_to_float(v.z & 0xFFFFu), q1.x, dot);
-        dot = __builtin_fmaf(half_bits_to_float(v.z >> 16), q1.y, dot);
-        dot = __builtin_fmaf(half_bits_to_float(last & 0xFFFFu), q1.z, dot);
-        dot = __builtin_fmaf(half_bits_to_float(last >> 16), q1.w, dot);
-        float residual = sub == 7u ? __builtin_bit_cast(float, v.w) : 0.f;
-#pragma unroll
-        for (int offset = 1; offset < 8; offset <<= 1) {
-            dot += xor_lane(dot, offset);
-            residual += xor_lane(residual, offset);
-        }
-        return sketch_lower_bound(dot, residual, sketch_margin);
     };
     // The rows the sketch could not rule out, `kept` of them compacted in `cand_slots`: about 3.4 of a hop's 22.8 fresh neighbours at the
     // headline shape, so nearly every hop fits ONE round of one row per lane group. The two-row form would give every active group
@@ -1599,7 +1682,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
     // rows of ≤ 128 bytes over a visited set in a global slab: gathered next to the probe instead of behind it (see the hop loop)
     constexpr bool early_ak = lanes_ak == 2 && mode_ak == scratch_hash_k && team_ak == 1;
     const bool early_rows = plain_ak ? early_ak : early_ak && args.early_rows != 0 && !inline_rows && cells <= 64;
-    tick(0);
+    clock.tick(0);
     // ---- a team over the in-`top` frontier with a wide `top` (≥ 8 cells per lane: expansions above 256, where a commit costs about
     // what measuring the hop's rows does) walks the beam as a PIPELINE (lists of ≤ 64 cells): the leader names the next member to
     // expand BEFORE it commits the hop just measured, probes its list, hands the gather to the helpers and commits while they
@@ -1681,7 +1764,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                     else if (lane < cells)
                         neighbor = list_of(expanded)[lane];
 #ifdef USEARCH_AMD_PHASES
-                    diagnostic_ready += expanded == ahead_slot ? 1u : 0u;
+                    clock.list_ready(expanded == ahead_slot);
 #endif
                     float likely_distance;
                     std::uint32_t likely_lane, likely_cell;
@@ -1694,7 +1777,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 const std::uint32_t present_count = popcount64(present_mask);
                 std::uint32_t count = 0;
                 bool fresh = false;
-                tick(1);
+                clock.tick(1);
                 if (present_count) {
                     if (visits_count + present_count > visits_limit) {
                         overflow = true;
@@ -1731,7 +1814,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                     if (likely != none_slot_k)
                         ahead_cell = lane < cells ? list_of(likely)[lane] : none_slot_k;
                 }
-                tick(2);
+                clock.tick(2);
                 if (pending)
                     commit(from_lane); // … while the leader probes and the hop before lands in `top`
                 // … and if that put a newcomer in front of the member whose list was just asked for, its list is asked for too
@@ -1746,7 +1829,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                             ahead_cell = lane < cells ? list_of(first)[lane] : none_slot_k;
                     }
                 }
-                tick(4);
+                clock.tick(4);
                 if (present_count) {
                     // the list of the member likeliest to be expanded next, for the helpers to touch its members' rows (`team_ahead_list`);
                     // the wait for that list sits where the leader would wait for the helpers anyway
@@ -1761,7 +1844,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                         pending = true;
                     }
                 }
-                tick(3);
+                clock.tick(3);
             }
         }
     }
@@ -1787,7 +1870,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
         const std::uint32_t* list = list_of(expanded);
         const bool list_ready = expanded == ahead_slot; // its first tile was requested one hop ago
 #ifdef USEARCH_AMD_PHASES
-        diagnostic_ready += list_ready ? 1u : 0u;
+        clock.list_ready(list_ready);
 #endif
         const std::uint32_t ready_cell = ahead_cell;
         std::uint32_t first_cell = none_slot_k;
@@ -1846,7 +1929,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 break;
             }
             // visits.set(successor) for the whole tile at once; duplicates inside a list were removed on upload
-            tick(1);
+            clock.tick(1);
             bool fresh;
             float early_mine = 0.f;          // inline rows: this lane's distance, computed in the shadow of the probe
             bool early_done = false;
@@ -1857,8 +1940,8 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
             if constexpr (mode_ak == scratch_global_k) {
                 fresh = visits_set<mode_ak>(visits, visits_mask, neighbor, present);
             } else {
-                std::uint32_t h = hash_slot(neighbor) & visits_mask;
-                std::uint32_t old = neighbor; // an absent lane probes nothing
+                const std::uint32_t h = hash_slot(neighbor) & visits_mask;
+                std::uint32_t old;
                 bool asks = present;
                 std::uint32_t seen_cell = 0;
                 if constexpr (seen_ak) {
@@ -1867,18 +1950,8 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                         asks = present && seen[seen_cell] != neighbor;
                     }
                 }
-                // How the slab is probed (`probe_mode_t`, short rows only; the engine's choice rides in `args.probe_mode`):
-                //  * `probe_swap_k` — a compare-and-swap per probe round, executed at the memory side.
-                //  * `probe_load_first_k` (round 5's experiment) — a cell is LOADED and an atomic spent only to claim an empty one: a slot
-                //    already in the set costs no atomic, a fresh one a load and the atomic — two round trips on the hop's chain.
-                //  * `probe_plain_k` — NO atomic. The slab is private to this wave, so the only accesses that can race are those of the
-                //    lanes of one instruction: a cell is loaded past the vector cache (`sc1`: nothing is allocated there per lane), an
-                //    empty one is claimed with a plain store nobody waits for, and lanes of one round that want the SAME cell settle
-                //    it in LDS — one bit per cell, `ds_or_rtn`: LDS serves the lanes of an instruction one after the other, the first
-                //    to set the bit has the cell, the others look at it again next round and read the winner's slot (a wave's accesses
-                //    to one address are served in issue order). The words touched go back to zero behind the ORs. A list holds every
-                //    slot once (duplicates were removed on upload), so no two lanes of a round insert the same slot. One round trip
-                //    per probe round, same members in the set, same answers (which CELL a member lands in is not observable).
+                // The slab is probed by compare-and-swap, one per probe round, executed at the memory side (`probe_first`, `probe_rest`).
+                // A load first with the swap only to claim, and no atomic at all, both lost to it: DESIGN.md §3.2.
                 bool shadow_done = false;
                 auto shadow_work = [&]() {
                     if (shadow_done)
@@ -1914,55 +1987,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                     }
                 }
                 };
-                std::uint32_t probe_mode = probe_swap_k;
-#ifdef USEARCH_AMD_EXPERIMENT_PROBE_MODES // modes 1 and 2 measured slower (profiles/r06_short_rows/): product builds compile them away
-                if constexpr (seen_ak)
-                    probe_mode = args.probe_mode;
-#endif
-                const bool load_first = probe_mode == probe_load_first_k;
-                if (probe_mode == probe_plain_k) {
-                    std::uint32_t* claim = reinterpret_cast<std::uint32_t*>(query_lds + args.claim_offset);
-                    const std::uint32_t claim_mask = args.claim_bits - 1;
-                    bool looking = asks;
-                    for (;;) {
-                        std::uint32_t cell_value = none_slot_k;
-                        if (looking)
-                            cell_value = __hip_atomic_load(visits + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (!popped)
-                            pop_now(); // LDS and register work in the shadow of the first round trip
-                        shadow_work();
-                        const bool wants = looking && cell_value == none_slot_k;
-                        if (looking && cell_value == neighbor)
-                            looking = false; // in the set (`old` still names the slot itself: not fresh)
-                        if (ballot(wants)) {
-                            const std::uint32_t bit = h & claim_mask;
-                            bool won = false;
-                            if (wants) {
-                                const std::uint32_t before = __hip_atomic_fetch_or(claim + (bit >> 5), 1u << (bit & 31u), __ATOMIC_RELAXED,
-                                                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
-                                won = ((before >> (bit & 31u)) & 1u) == 0u;
-                                claim[bit >> 5] = 0u;
-                            }
-                            if (won) {
-                                __hip_atomic_store(visits + h, neighbor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                old = none_slot_k, looking = false;
-                            }
-                        }
-                        if (looking && !wants)
-                            h = (h + 1) & visits_mask; // linear probing, index.hpp:1085-1211
-                        if (!ballot(looking))
-                            break;
-                    }
-                } else {
-                if (asks) {
-                    if (load_first) {
-                        old = __hip_atomic_load(visits + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (old == none_slot_k)
-                            old = atomicCAS(visits + h, none_slot_k, neighbor);
-                    } else {
-                        old = atomicCAS(visits + h, none_slot_k, neighbor);
-                    }
-                }
+                old = probe_first(visits, h, neighbor, asks);
                 // ---- the sketch's records beside the probe. Which records a hop needs depends on the LIST alone, not on the probe's
                 //      answer: with `top` full and a list of at most 32 cells (four rounds of eight lane groups cover it) the record of
                 //      every present neighbour is requested now, by list position — the slot comes from the lane that holds it — and is
@@ -2013,17 +2038,8 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                         aside_count += popcount64(ballot(lane_bit(taken_mask) && old == none_slot_k));
                     }
                 }
-                while (!aside_ak && old != none_slot_k && old != neighbor) { // linear probing, index.hpp:1085-1211
-                    h = (h + 1) & visits_mask;
-                    if (load_first) {
-                        old = __hip_atomic_load(visits + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (old == none_slot_k)
-                            old = atomicCAS(visits + h, none_slot_k, neighbor);
-                    } else {
-                        old = atomicCAS(visits + h, none_slot_k, neighbor);
-                    }
-                }
-                }
+                if constexpr (!aside_ak)
+                    old = probe_rest(visits, visits_mask, h, neighbor, old);
                 fresh = present && old == none_slot_k;
                 if constexpr (seen_ak) {
                     if (seen && asks)
@@ -2031,7 +2047,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 }
             }
             const std::uint64_t fresh_mask = ballot(fresh);
-            tick(2);
+            clock.tick(2);
             const std::uint32_t count = popcount64(fresh_mask);
             visits_count += count;
             if (!count)
@@ -2082,7 +2098,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                     for (int r = 0; r < 4; ++r) {
                         if (!((fresh_mask >> (r * 8)) & 0xFFu))
                             continue; // (wave-uniform) nobody of this round is fresh: its records are dropped unread
-                        const float lower = record_bound(early_record[r], q0, q1, sub);
+                        const float lower = sketch_record_bound(early_record[r], q0, q1, sub, sketch_margin);
                         if (sub == 0u)
                             cand_distances[(std::uint32_t)r * 8 + group] = lower;
                     }
@@ -2112,7 +2128,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                             if (base + (std::uint32_t)r * 8 >= count)
                                 break; // (wave-uniform) the eight candidates of this round and of the later ones lie beyond `count`
                             const std::uint32_t ci = base + (std::uint32_t)r * 8 + group;
-                            const float lower = record_bound(record[r], q0, q1, sub);
+                            const float lower = sketch_record_bound(record[r], q0, q1, sub, sketch_margin);
                             if (sub == 0u && ci < count)
                                 cand_distances[ci] = lower;
                         }
@@ -2123,7 +2139,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 const std::uint64_t survivors = ballot(member && !(bound >= radius)); // a NaN bound proves nothing
                 const std::uint32_t kept = popcount64(survivors);
                 sketch_tested += count, sketch_pruned += count - kept;
-                tick_bounds(kept);
+                clock.tick_bounds(kept);
                 const bool survivor = lane_bit(survivors);
                 wave_sync<false>(); // every lane has read its slot and its bound
                 if (survivor)
@@ -2145,7 +2161,7 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 mine_slot = lane < count ? mem::load(cand_slots + lane) : 0u;
                 candidate = lane < count;
             }
-            tick(3);
+            clock.tick(3);
 
             // commit in list order with the reference's tests (index.hpp:4233-4240)
             std::uint64_t pending = ballot(candidate && (top.size < ef || mine < radius)); // radius only shrinks
@@ -2153,35 +2169,25 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 const std::uint32_t i = (std::uint32_t)__ffsll((long long)pending) - 1;
                 pending &= pending - 1;
                 const float d = read_lane_f32(mine, i);
-#ifdef USEARCH_AMD_PHASES
-                ++diagnostic_rechecks;
-#endif
+                clock.recheck();
                 if (!(top.size < ef || d < radius))
                     continue;
                 const std::uint32_t successor = read_lane_u32(mine_slot, i);
-#ifdef USEARCH_AMD_PHASES
-                ++diagnostic_pushes;
-                const std::uint64_t t0 = __builtin_amdgcn_s_memtime();
-#endif
+                clock.push_begin();
                 // the frontier lives in LDS, `top` in registers: the insert runs while the push's reads are in flight
                 push_ticket_t ticket;
                 if constexpr (!in_top_ak)
                     ticket = heap_push_begin<global_ak>(next, next_size);
-#ifdef USEARCH_AMD_PHASES
-                const std::uint64_t t1 = __builtin_amdgcn_s_memtime();
-#endif
+                clock.push_middle();
                 if (in_top_ak || allowed(successor))
                     top.insert(d, successor, ef, radius); // radius = top.top() once full; the new cell is open
                 if constexpr (!in_top_ak)
                     heap_push_finish<global_ak>(next, next_size, ticket, -d, successor);
-#ifdef USEARCH_AMD_PHASES
-                const std::uint64_t t2 = __builtin_amdgcn_s_memtime();
-                diagnostic_push_ticks += t1 - t0, diagnostic_insert_ticks += t2 - t1;
-#endif
+                clock.push_end();
             }
             peak_next = next_size > peak_next ? next_size : peak_next;
             wave_sync<global_ak>();
-            tick(4);
+            clock.tick(4);
         }
         if (overflow)
             break;
@@ -2199,24 +2205,8 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
     }
     const std::uint32_t found = top.size < wanted ? top.size : wanted;
     top.dump(ix, args, q, found, wanted);
-    tick(5);
-#ifdef USEARCH_AMD_PHASES
-    if (args.phases && lane == 0) {
-#pragma unroll
-        for (int phase = 0; phase < 6; ++phase)
-            atomicAdd(args.phases + phase, (unsigned long long)phase_ticks[phase]);
-        atomicAdd(args.phases + 6, (unsigned long long)diagnostic_pushes);
-        atomicAdd(args.phases + 7, (unsigned long long)diagnostic_ready);
-        atomicAdd(args.phases + 8, (unsigned long long)diagnostic_push_ticks);
-        atomicAdd(args.phases + 9, (unsigned long long)diagnostic_insert_ticks);
-        atomicAdd(args.phases + 10, (unsigned long long)diagnostic_rechecks);
-        if constexpr (team_ak == 1) { // [11 … 15] belong to a team's helpers
-            atomicAdd(args.phases + 11, (unsigned long long)diagnostic_bound_ticks);
-            atomicAdd(args.phases + 12, (unsigned long long)diagnostic_sketch_hops);
-            atomicAdd(args.phases + 13, (unsigned long long)diagnostic_wide_hops);
-        }
-    }
-#endif
+    clock.tick(5);
+    clock.flush(args, lane, team_ak == 1);
     if constexpr (sketch_ak) {
         if (sketch_tested && lane == 0) {
             atomicAdd(args.sketch_counters, (unsigned long long)sketch_tested);
@@ -2236,11 +2226,6 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
     return true;
 }
 
-/**
- *  Persistent launch: every wave (= workgroup) pulls query indices from `args.queue` until the batch is drained, so a
- *  grid of (CUs × resident waves) covers any batch size with perfect dynamic balance and one scratch slab per wave.
- *  `scratch_global_k` is the exception: one wave per query, statically (its bitmaps are zeroed per launch by the host).
- */
 /**
  *  Register/latency trade-off of one instantiation: how many 16-byte loads a lane keeps in flight inside a row
  *  (`unroll`) against how many waves per SIMD the register allocator must leave room for (`waves`).
@@ -2283,6 +2268,11 @@ constexpr int kernel_waves(int variant, int epl, int frontier = 0, int lanes = 8
     return variant == variant_u4_w4_k ? (epl >= 8 ? 3 : 4) : variant == variant_u8_w3_k ? (epl >= 16 ? 2 : 3) : 2;
 }
 
+/**
+ *  Persistent launch: every wave (= workgroup) pulls query indices from `args.queue` until the batch is drained, so a
+ *  grid of (CUs × resident waves) covers any batch size with perfect dynamic balance and one scratch slab per wave.
+ *  `scratch_global_k` is the exception: one wave per query, statically (its bitmaps are zeroed per launch by the host).
+ */
 template <int metric_ak, int scalar_ak, int lanes_ak, int variant_ak, int mode_ak, int epl_ak, int frontier_ak, bool plain_ak = false>
 __global__ __launch_bounds__(64, kernel_waves(variant_ak, epl_ak, frontier_ak, lanes_ak, plain_ak)) void search_kernel(const snapshot_view_t ix,
                                                                                             const search_args_t args) {
@@ -2372,16 +2362,13 @@ __global__ __launch_bounds__(64 * team_waves_k) void team_search_kernel(const sn
         std::uint32_t* ahead = team_ahead_list(team);
         if (lane_id() < team_ahead_rows_k / (team_waves_k - 1))
             ahead[turn * (team_ahead_rows_k / (team_waves_k - 1)) + lane_id()] = none_slot_k; // until a pipelining leader publishes a list
-#ifdef USEARCH_AMD_PHASES // every helper's clock: what it spent between the two barriers of a hop
-        std::uint64_t helper_mark = args.phases ? __builtin_amdgcn_s_memtime() : 0, helper_busy = 0, helper_idle = 0, helper_hops = 0;
+#ifdef USEARCH_AMD_PHASES
+        phase_clock_t clock(args, 64u / lanes_ak); // every helper's own: what it spent between the two barriers of a hop
 #endif
         for (;;) {
             team_barrier(); // the leader has published a hop (or the end)
 #ifdef USEARCH_AMD_PHASES
-            if (args.phases) {
-                const std::uint64_t now = __builtin_amdgcn_s_memtime();
-                helper_idle += now - helper_mark, helper_mark = now;
-            }
+            clock.helper_woke();
 #endif
             const std::uint32_t count = uniform_u32(team->count);
             if (count == team_exit_k)
@@ -2394,21 +2381,14 @@ __global__ __launch_bounds__(64 * team_waves_k) void team_search_kernel(const sn
                 team_share<metric_ak, scalar_ak, lanes_ak, loads_ak>(ix, query_lds, a2, cand_slots, cand_distances, count, turn,
                                                                      team_ak - 1, true);
 #ifdef USEARCH_AMD_PHASES
-            if (args.phases) {
-                const std::uint64_t now = __builtin_amdgcn_s_memtime();
-                helper_busy += now - helper_mark, helper_mark = now, ++helper_hops;
-            }
+            clock.helper_measured();
 #endif
             team_landing_alive(landing); // past the gather's own waits
             team_barrier(); // every share is in LDS: the leader commits
             team_touch_rows(ix, ahead, turn, landing);
         }
 #ifdef USEARCH_AMD_PHASES
-        if (args.phases && lane_id() == 0) { // [11 … 14] what each helper spent measuring, [15] the first one's hops
-            atomicAdd(args.phases + 10 + wave, (unsigned long long)helper_busy);
-            if (wave == 1)
-                atomicAdd(args.phases + 15, (unsigned long long)helper_hops);
-        }
+        clock.flush_helper(args, lane_id(), wave);
 #endif
     }
 }

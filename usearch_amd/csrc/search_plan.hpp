@@ -14,8 +14,6 @@
 
 namespace usearch_amd {
 
-/// How the short-row walks probe their visited-set slabs unless USEARCH_AMD_PROBE_MODE says otherwise (common.hpp `probe_mode_t`).
-static constexpr std::uint32_t default_probe_mode_k = probe_swap_k;
 /// Rows of ≤ 128 bytes gathered next to the probe of the visited set (USEARCH_AMD_EARLY_ROWS = 0 | 1 overrides).
 static constexpr std::size_t default_early_rows_k = 1; // 20M x 96 i8: +6.4 % at ef 80, +5.1 % at ef 64, same keys / bits / counters (profiles/r06_short_rows/early_rows.log)
 
@@ -39,15 +37,9 @@ inline search_knobs_t read_search_knobs(std::uint32_t lanes) {
     k.frontier = env_size("USEARCH_AMD_FRONTIER", 0), k.variant = env_size("USEARCH_AMD_VARIANT", 0);
     k.no_team = env_size("USEARCH_AMD_NO_TEAM", 0), k.no_plain = env_size("USEARCH_AMD_NO_PLAIN", 0);
     k.waves_per_cu = env_size("USEARCH_AMD_WAVES_PER_CU", 32), k.no_small_batch_lds = env_size("USEARCH_AMD_NO_SMALL_BATCH_LDS", 0);
-    k.early_rows = env_size("USEARCH_AMD_EARLY_ROWS", default_early_rows_k), k.claim_bits = env_size("USEARCH_AMD_CLAIM_BITS", 0);
+    k.early_rows = env_size("USEARCH_AMD_EARLY_ROWS", default_early_rows_k);
     k.aside_cells = env_size("USEARCH_AMD_ASIDE_CELLS", 0), k.plain_whatever_the_room = env_size("USEARCH_AMD_PLAIN_WHATEVER_THE_ROOM", 0);
     k.seen_cells = env_size("USEARCH_AMD_SEEN_CELLS", (std::size_t)-1);
-    // how the slab is probed (common.hpp `probe_mode_t`): USEARCH_AMD_PROBE_MODE = 0 | 1 | 2
-    // (USEARCH_AMD_PROBE_LOAD_FIRST=1, round 5's name for mode 1, still answers)
-    k.probe_mode = default_probe_mode_k;
-#ifdef USEARCH_AMD_EXPERIMENT_PROBE_MODES // `make EXTRA=-DUSEARCH_AMD_EXPERIMENT_PROBE_MODES OUT=… OBJ=…`: the copy scripts/probe_mode_check.py loads
-    k.probe_mode = env_size("USEARCH_AMD_PROBE_MODE", default_probe_mode_k), k.probe_load_first = env_size("USEARCH_AMD_PROBE_LOAD_FIRST", 0);
-#endif
     return k;
 }
 
@@ -75,7 +67,7 @@ inline std::uint32_t waves_per_cu(const search_plan_t& plan, const search_knobs_
 /// hash knows it before it looks for LDS cells: the engine vouches for all of it (USEARCH_AMD_NO_PLAIN=1 keeps the general build).
 inline bool plain_wanted(const search_shape_t& shape, const search_plan_t& plan, const search_rung_t& rung) {
     return plan.plain_possible && !shape.query_ids && !shape.beam_level && !shape.descent_only && !shape.allow_bits && !shape.exclude_own &&
-           rung.probe_mode == probe_swap_k && (shape.lanes == 1 || rung.early_rows != 0);
+           (shape.lanes == 1 || rung.early_rows != 0);
 }
 
 /// Everything settled before the first launch. → nullptr, or why the call is refused.
@@ -262,7 +254,7 @@ inline void plan_rung(const search_shape_t& shape, const search_knobs_t& knobs, 
     // a team's workgroup carries the leader's LDS areas plus the shared block; one workgroup per query of the small batch
     std::uint64_t wave_bytes = lds_bytes_now();
     rung.team = plan.team, rung.frontier = plan.frontier, rung.entries_per_lane = plan.entries_per_lane;
-    rung.hash_cap = plan.hash_cap, rung.next_cap = plan.next_cap, rung.probe_mode = probe_swap_k;
+    rung.hash_cap = plan.hash_cap, rung.next_cap = plan.next_cap;
     // rows of ≤ 128 bytes gathered next to the probe of the visited set instead of behind it (kernels.hpp, the hop loop)
     rung.early_rows = plan.mode == scratch_hash_k && !plan.team && lanes == 2 && knobs.early_rows ? 1u : 0u;
     plan.stats.early_rows = rung.early_rows;
@@ -270,36 +262,12 @@ inline void plan_rung(const search_shape_t& shape, const search_knobs_t& knobs, 
     // resident wave (the walk lives on its residency), at most 2 048; USEARCH_AMD_SEEN_CELLS forces a number (0 = none)
     const bool short_rows_over_hash = plan.mode == scratch_hash_k && !plan.team && lanes <= 2;
     if (short_rows_over_hash) {
-        const std::size_t probe_mode = knobs.probe_load_first ? (std::size_t)probe_load_first_k : knobs.probe_mode;
-        if (probe_mode == probe_plain_k) {
-            // one claim bit per cell of the slab where that costs no resident wave, else as many as do not (a smaller bitmap only
-            // adds false alarms: a lane that loses a claim looks at its cell again); USEARCH_AMD_CLAIM_BITS forces a number
-            std::uint32_t bits = plan.hash_cap;
-            const std::size_t forced = knobs.claim_bits;
-            if (forced)
-                for (bits = 64; bits * 2 <= forced && bits < plan.hash_cap; bits *= 2) {}
-            else
-                while (bits > 512 && waves_for(align16(wave_bytes) + bits / 8) < waves_for(wave_bytes))
-                    bits /= 2;
-            if (align16(wave_bytes) + bits / 8 <= lds_budget) {
-                rung.probe_mode = (std::uint32_t)probe_mode;
-                rung.claim_offset = (std::uint32_t)align16(wave_bytes);
-                rung.claim_bits = bits;
-                wave_bytes = rung.claim_offset + bits / 8ull;
-            }
-        } else if (probe_mode == probe_load_first_k) {
-            rung.probe_mode = probe_load_first_k;
-        }
         // a plain `search` batch runs the build without the features it never uses (kernels.hpp `plain_ak`, `plain_wanted` above). That
         // build never probes the slab past a member's home cell and sets what collides aside in LDS: about visits² / (2 · cells of the
         // slab) members, visits ≈ 20 · expansion + 800 on the measured shapes (20M × 128 b1 at 64: median 1 521, maximum 2 225 of
         // 100 000 queries; 20M × 96 i8 at 80: 1 742 / 2 281) — 512 cells at three quarters' load must take them, and must cost no
         // resident wave; a query that outgrows them all the same is run again by the retry ladder
-#ifdef USEARCH_AMD_EXPERIMENT_NO_ASIDE
-        const bool aside_wanted = false;
-#else
         const bool aside_wanted = plain_wanted(shape, plan, rung) && lanes == 2; // (rows that travel with the lists gain nothing from it: kernels.hpp)
-#endif
         if (aside_wanted) {
             std::uint32_t aside_cells = 512;
             if (const std::size_t forced_cells = knobs.aside_cells) // tests: a table that is sure to fill up
@@ -329,15 +297,10 @@ inline void plan_rung(const search_shape_t& shape, const search_knobs_t& knobs, 
             rung.seen_cells = cells;
             wave_bytes = rung.seen_offset + cells * 4ull;
         }
-        plan.stats.probe_mode = rung.probe_mode, plan.stats.seen_cells = rung.seen_cells, plan.stats.claim_bits = rung.claim_bits;
+        plan.stats.seen_cells = rung.seen_cells;
         // decided with the LDS areas above: what the instantiation takes for granted must be there
-        if (plain_wanted(shape, plan, rung)) {
-#ifdef USEARCH_AMD_EXPERIMENT_NO_ASIDE
-            rung.plain = rung.seen_cells ? 1u : 0u;
-#else
+        if (plain_wanted(shape, plan, rung))
             rung.plain = (lanes == 2 ? rung.aside_cells : rung.seen_cells) ? 1u : 0u;
-#endif
-        }
     }
     plan.stats.plain = rung.plain, plan.stats.aside_cells = rung.aside_cells;
     // the query's 64 coefficients on the sketch's directions: 256 bytes behind the wave's other areas

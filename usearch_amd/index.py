@@ -1304,12 +1304,12 @@ PlanShape = _struct("PlanShape", (C.c_uint64, "size count wanted expansion"), (C
                                  "allow_bits exclude_own reference_frontier"))
 PlanTuning = _struct("PlanTuning", (C.c_uint32, "hash_cap next_cap variant mode waves_per_cu top_in_memory frontier wave_clock sketch"))
 PlanKnobs = _struct("PlanKnobs", (C.c_size_t, "lds_budget hash_cap hash_load_pct next_cap mode top_in_memory no_two_cells frontier variant "
-                                              "no_team no_plain waves_per_cu no_small_batch_lds early_rows claim_bits aside_cells "
-                                              "plain_whatever_the_room seen_cells probe_mode probe_load_first"))
+                                              "no_team no_plain waves_per_cu no_small_batch_lds early_rows aside_cells "
+                                              "plain_whatever_the_room seen_cells"))
 Plan = _struct("Plan", (C.c_uint32, "ef query_lds entries_per_lane waves_cap hash_cap next_cap"), (C.c_int32, "mode variant frontier"),
                (C.c_uint32, "team plain_possible sketch"), (Stats, "stats"))
 PlanRung = _struct("PlanRung", (C.c_int32, "mode frontier"),
-                   (C.c_uint32, "team plain entries_per_lane grid lds_bytes hash_cap next_cap early_rows probe_mode claim_offset claim_bits "
+                   (C.c_uint32, "team plain entries_per_lane grid lds_bytes hash_cap next_cap early_rows "
                                 "aside_offset aside_cells seen_offset seen_cells sketch_offset team_offset"),
                    (C.c_uint64, "slab visits_offset bitmap_bytes"))
 
