@@ -250,6 +250,54 @@ def test_calls_in_flight_share_a_launch(tmp_path):
 
 
 
+def test_a_refused_image_takes_the_key_table_of_the_image_before_along():
+    """`usearch_load_buffer` of a damaged image onto an index that was serving another image: the old image is gone, and so is its key
+    table: `contains`, `count` and `get` answer for the empty index that is left, not for slots that no longer exist."""
+    library = C.CDLL(os.path.join(ROOT, "usearch_amd", "lib", "libusearch_c.so"))
+    error_t = C.POINTER(C.c_char_p)
+    library.usearch_init.restype = C.c_void_p
+    library.usearch_init.argtypes = [C.c_void_p, error_t]
+    library.usearch_load_buffer.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, error_t]
+    library.usearch_contains.restype = C.c_bool
+    library.usearch_contains.argtypes = [C.c_void_p, C.c_uint64, error_t]
+    library.usearch_get.restype = C.c_size_t
+    library.usearch_get.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.c_void_p, C.c_int, error_t]
+    library.usearch_size.restype = C.c_size_t
+    library.usearch_size.argtypes = [C.c_void_p, error_t]
+    library.usearch_free.argtypes = [C.c_void_p, error_t]
+    image = np.ascontiguousarray(np.load(os.path.join(ROOT, "tests", "golden", "l2sq_f32_3.npz"))["image"])
+    error, row = C.c_char_p(), np.zeros(3, dtype=np.float32)
+    index = library.usearch_init(None, C.byref(error))
+    library.usearch_load_buffer(index, C.c_void_p(image.ctypes.data), len(image), C.byref(error))
+    assert not error.value and library.usearch_contains(index, 1000, C.byref(error))
+    assert library.usearch_get(index, 1000, 1, C.c_void_p(row.ctypes.data), 1, C.byref(error)) == 1 and not error.value
+    library.usearch_load_buffer(index, C.c_void_p(image.ctypes.data), len(image) - 5, C.byref(error))
+    assert error.value == b"Failed to pull nodes from the stream"
+    error = C.c_char_p()
+    assert library.usearch_size(index, C.byref(error)) == 0
+    assert not library.usearch_contains(index, 1000, C.byref(error)) and not error.value
+    assert library.usearch_get(index, 1000, 1, C.c_void_p(row.ctypes.data), 1, C.byref(error)) == 0 and not error.value
+    library.usearch_free(index, C.byref(error))
+
+
+def test_the_member_record_keeps_its_invariants_under_the_sanitizers(tmp_path, reference):
+    """The drop-in's host record of its members (usearch_amd/csrc/members.hpp: pure host logic) on its own, under AddressSanitizer and
+    UndefinedBehaviorSanitizer (tests/cpp/members_test.cpp): a seeded script over every operation, from an image of the reference's with
+    seven members removed (owned, borrowed and mapped) and from nothing; after each step the key table names exactly the slots in use,
+    the ring holds the freed slots oldest first, recycled slots exist, and every row is where its key is."""
+    import subprocess
+    from tests import util
+    removed = (1003, 1010, 1011, 1027, 1040, 1058, 1059)
+    image, _, _ = util.build_image(60, 4, "cos", "f32", connectivity=4, remove=removed)
+    path = tmp_path / "members.usearch"
+    path.write_bytes(np.ascontiguousarray(image).tobytes())
+    binary = str(tmp_path / "usearch_amd_members_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpp", "members_test.cpp"), "-o", binary])
+    out = subprocess.run([binary, str(path)] + [str(key) for key in removed], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "PASSED" in out.stdout, out.stdout + out.stderr[-3000:]
+
+
 def test_calls_in_flight_share_a_launch_under_the_thread_sanitizer(tmp_path):
     """The same program under ThreadSanitizer (clang's runtime: it knows `pthread_cond_clockwait`, which the launcher's timed wait
     for returning callers uses): no data race, no lock-order report in the combiner."""

@@ -13,8 +13,7 @@
  *  What the device cannot do is refused by name: a user-defined metric function (`usearch_change_metric`,
  *  `usearch_init_options_t::metric`), metrics / scalar kinds without a kernel.
  *
- *  The host keeps what the reference keeps in `index_dense_gt`: keys and vectors per slot (for `get`, `contains`,
- *  `count`, `rename`, `remove`), either inside a serialized image (after load / view) or in staging arrays (after add).
+ *  The host keeps what the reference keeps in `index_dense_gt`, keys and vectors per slot, in a record of its own: members.hpp.
  */
 #include "../../include/usearch_c_dropin.h"
 
@@ -46,81 +45,46 @@
 #include "filter.hpp"
 #include "host_util.hpp"
 #include "join.hpp"
+#include "members.hpp"
 
 using namespace usearch_amd;
 
 namespace {
 
-metric_kind_t metric_from_c(usearch_metric_kind_t kind) { // c/lib.cpp:26-42
-    switch (kind) {
-    case usearch_metric_cos_k: return metric_cos_k;
-    case usearch_metric_ip_k: return metric_ip_k;
-    case usearch_metric_l2sq_k: return metric_l2sq_k;
-    case usearch_metric_haversine_k: return metric_haversine_k;
-    case usearch_metric_divergence_k: return metric_divergence_k;
-    case usearch_metric_pearson_k: return metric_pearson_k;
-    case usearch_metric_jaccard_k: return metric_jaccard_k;
-    case usearch_metric_hamming_k: return metric_hamming_k;
-    case usearch_metric_tanimoto_k: return metric_tanimoto_k;
-    case usearch_metric_sorensen_k: return metric_sorensen_k;
-    default: return metric_unknown_k;
-    }
+/// The ABI's enumerators beside the engine's (c/lib.cpp:26-83): one table per kind, read in both directions.
+constexpr std::pair<usearch_metric_kind_t, metric_kind_t> metric_kinds_k[] = {
+    {usearch_metric_cos_k, metric_cos_k},           {usearch_metric_ip_k, metric_ip_k},
+    {usearch_metric_l2sq_k, metric_l2sq_k},         {usearch_metric_haversine_k, metric_haversine_k},
+    {usearch_metric_divergence_k, metric_divergence_k}, {usearch_metric_pearson_k, metric_pearson_k},
+    {usearch_metric_jaccard_k, metric_jaccard_k},   {usearch_metric_hamming_k, metric_hamming_k},
+    {usearch_metric_tanimoto_k, metric_tanimoto_k}, {usearch_metric_sorensen_k, metric_sorensen_k}};
+constexpr std::pair<usearch_scalar_kind_t, scalar_kind_t> scalar_kinds_k[] = {
+    {usearch_scalar_f32_k, scalar_f32_k}, {usearch_scalar_f64_k, scalar_f64_k}, {usearch_scalar_f16_k, scalar_f16_k},
+    {usearch_scalar_i8_k, scalar_i8_k},   {usearch_scalar_b1_k, scalar_b1x8_k}, {usearch_scalar_bf16_k, scalar_bf16_k}};
+template <typename pairs_at, typename given_at, typename unknown_at> unknown_at from_c(const pairs_at& pairs, given_at given, unknown_at unknown) {
+    for (const auto& pair : pairs)
+        if (pair.first == given)
+            return pair.second;
+    return unknown;
 }
-usearch_metric_kind_t metric_to_c(metric_kind_t kind) { // c/lib.cpp:44-59
-    switch (kind) {
-    case metric_cos_k: return usearch_metric_cos_k;
-    case metric_ip_k: return usearch_metric_ip_k;
-    case metric_l2sq_k: return usearch_metric_l2sq_k;
-    case metric_haversine_k: return usearch_metric_haversine_k;
-    case metric_divergence_k: return usearch_metric_divergence_k;
-    case metric_pearson_k: return usearch_metric_pearson_k;
-    case metric_jaccard_k: return usearch_metric_jaccard_k;
-    case metric_hamming_k: return usearch_metric_hamming_k;
-    case metric_tanimoto_k: return usearch_metric_tanimoto_k;
-    case metric_sorensen_k: return usearch_metric_sorensen_k;
-    default: return usearch_metric_unknown_k;
-    }
+template <typename pairs_at, typename given_at, typename unknown_at> unknown_at to_c(const pairs_at& pairs, given_at given, unknown_at unknown) {
+    for (const auto& pair : pairs)
+        if (pair.second == given)
+            return pair.first;
+    return unknown;
 }
-scalar_kind_t scalar_from_c(usearch_scalar_kind_t kind) { // c/lib.cpp:61-71
-    switch (kind) {
-    case usearch_scalar_f32_k: return scalar_f32_k;
-    case usearch_scalar_f64_k: return scalar_f64_k;
-    case usearch_scalar_f16_k: return scalar_f16_k;
-    case usearch_scalar_i8_k: return scalar_i8_k;
-    case usearch_scalar_b1_k: return scalar_b1x8_k;
-    case usearch_scalar_bf16_k: return scalar_bf16_k;
-    default: return scalar_unknown_k;
-    }
-}
-usearch_scalar_kind_t scalar_to_c(scalar_kind_t kind) { // c/lib.cpp:73-83
-    switch (kind) {
-    case scalar_f32_k: return usearch_scalar_f32_k;
-    case scalar_f64_k: return usearch_scalar_f64_k;
-    case scalar_f16_k: return usearch_scalar_f16_k;
-    case scalar_i8_k: return usearch_scalar_i8_k;
-    case scalar_b1x8_k: return usearch_scalar_b1_k;
-    case scalar_bf16_k: return usearch_scalar_bf16_k;
-    default: return usearch_scalar_unknown_k;
-    }
-}
+metric_kind_t metric_from_c(usearch_metric_kind_t kind) { return from_c(metric_kinds_k, kind, metric_unknown_k); }
+usearch_metric_kind_t metric_to_c(metric_kind_t kind) { return to_c(metric_kinds_k, kind, usearch_metric_unknown_k); }
+scalar_kind_t scalar_from_c(usearch_scalar_kind_t kind) { return from_c(scalar_kinds_k, kind, scalar_unknown_k); }
+usearch_scalar_kind_t scalar_to_c(scalar_kind_t kind) { return to_c(scalar_kinds_k, kind, usearch_scalar_unknown_k); }
 
 void fail(usearch_error_t* error, const char* message) {
     if (error && message)
         *error = message;
 }
 
-/// Runs `body`; an allocation failure or any other exception becomes an error string instead of crossing the C ABI.
-template <typename body_at> void guarded(usearch_error_t* error, body_at&& body) {
-    try {
-        body();
-    } catch (const std::bad_alloc&) {
-        fail(error, "Out of memory!");
-    } catch (const std::exception&) {
-        fail(error, "Unexpected failure inside the index");
-    }
-}
-
-/// Same for an entry point that returns something: `fallback` is what the caller gets next to the error string.
+/// Runs `body`; an allocation failure or any other exception becomes an error string instead of crossing the C ABI, and `fallback`
+/// is what the caller gets next to it.
 template <typename result_at, typename body_at> result_at guarded(usearch_error_t* error, result_at fallback, body_at&& body) {
     try {
         return body();
@@ -130,6 +94,10 @@ template <typename result_at, typename body_at> result_at guarded(usearch_error_
         fail(error, "Unexpected failure inside the index");
     }
     return fallback;
+}
+/// Same for an entry point that returns nothing.
+template <typename body_at> void guarded(usearch_error_t* error, body_at&& body) {
+    guarded(error, 0, [&] { return body(), 0; });
 }
 
 /// Callers of this library loop single queries from many threads (Go routines, C# tasks: the reference leases a context per thread,
@@ -147,6 +115,7 @@ struct hardware_queues_t {
     }
 } hardware_queues;
 
+using callback_t = int (*)(usearch_key_t key, void* filter_state); ///< the predicate of `usearch_filtered_search`
 using shared_lock_t = std::shared_lock<std::shared_mutex>;
 using unique_lock_t = std::unique_lock<std::shared_mutex>;
 
@@ -203,235 +172,115 @@ struct index_t {
     bool multi = false;
     int device = 0;
 
-    // (1) a serialized image: owned bytes, a borrowed buffer (`view_buffer`) or a mapped file (`view`)
-    std::vector<std::uint8_t> image_owned;
-    const std::uint8_t* image_bytes = nullptr;
-    std::size_t image_length = 0;
-    void* mapping = nullptr;
-    std::size_t mapping_length = 0;
-    image_t image;      ///< parsed header of `image_bytes` when `has_image`
-    bool has_image = false;
-    snapshot_t* snapshot = nullptr; ///< HBM copy of the image, taken at the first search
-
-    // (2) staging: keys and vectors per slot once anything was added / removed / renamed since the image
-    bool staged = false;
-    std::vector<std::uint64_t> keys;
-    std::vector<std::uint8_t> vectors; ///< storage scalar kind, `bytes_per_vector` per slot
-    builder_t* builder = nullptr;      ///< device index linked from the staging arrays (null = stale)
-    /// Slots `usearch_remove` freed, oldest first — the reference's `free_keys_` ring (index_dense.hpp:507, 1479-1511): the next
-    /// `usearch_add` takes the oldest instead of a new slot, and the member is linked anew in place (`builder_t::update`).
-    std::vector<std::uint32_t> free_slots;
-    std::size_t free_head = 0;
-    std::vector<std::uint32_t> recycled; ///< reused slots whose device copy still holds the member that was removed
-
-    // key → slots, rebuilt lazily
-    std::unordered_multimap<std::uint64_t, std::uint32_t> lookup;
-    bool lookup_valid = false;
+    /// The host's record of the members (members.hpp): an image as loaded or viewed, or keys and vectors per slot once anything changed.
+    members_t members;
+    std::unique_ptr<snapshot_t> snapshot; ///< HBM copy of the image, taken at the first search
+    std::unique_ptr<builder_t> builder;   ///< device index linked from the staging arrays (null = stale)
 
     /// Bumped by everything that changes the members or drops their HBM copy: a `usearch_filter_t` describes one version.
     std::uint64_t version = 0;
 
-    std::size_t bpv() const { return bytes_per_vector(scalar, dimensions); }
-    std::size_t size() const { return staged ? keys.size() : has_image ? (std::size_t)image.size : 0; }
-
     void drop_device() {
         ++version;
         memos.clear(); // the callers hold the index alone: no search is reading one
-        delete builder, builder = nullptr;
-        delete snapshot, snapshot = nullptr;
+        builder.reset(), snapshot.reset();
     }
-    void drop_image() {
-        if (mapping)
-            ::munmap(mapping, mapping_length), mapping = nullptr, mapping_length = 0;
-        image_owned.clear(), image_owned.shrink_to_fit();
-        image_bytes = nullptr, image_length = 0, has_image = false;
-        image = image_t{};
-    }
-    ~index_t() {
+    /// Nothing of the index's content is left on the device, and the image is let go: load, view and clear start here.
+    void unload() {
         drop_device();
-        drop_image();
+        members.drop_image();
     }
-
     /// Adopts `bytes` as the current image. Configuration comes from its header (c/lib.cpp `usearch_load`: the index takes
-    /// the file's metric, scalar kind and dimensions).
-    const char* open_image(const void* bytes, std::size_t length) {
+    /// the file's metric, scalar kind and dimensions). A refused image is let go.
+    const char* open_image(image_bytes_t bytes) {
         image_t parsed;
-        if (const char* e = parsed.open(bytes, length))
+        if (const char* e = parsed.open(bytes.get(), bytes.get_deleter().length))
             return e;
         if (!kernel_available(parsed.metric, parsed.scalar))
             return "No MI355X kernel for this metric / scalar kind combination";
-        image = parsed;
-        image_bytes = static_cast<const std::uint8_t*>(bytes);
-        image_length = length;
-        has_image = true;
+        members.open_image(std::move(bytes), parsed);
         metric = parsed.metric, scalar = parsed.scalar, dimensions = (std::size_t)parsed.dimensions;
         if (parsed.connectivity)
             connectivity = (std::size_t)parsed.connectivity;
         multi = parsed.multi;
-        staged = false;
-        keys.clear(), vectors.clear();
-        free_slots.clear(), free_head = 0, recycled.clear();
-        lookup_valid = false;
         capacity = std::max<std::size_t>(capacity, (std::size_t)parsed.size);
         return nullptr;
     }
 
-    /// Key of every slot of the image, in slot order (the node tapes are variable-length: one sequential pass).
-    void image_keys(std::vector<std::uint64_t>& out) const {
-        out.resize((std::size_t)image.size);
-        std::size_t offset = 0;
-        for (std::uint64_t i = 0; i < image.size; ++i) {
-            out[i] = image_t::load<std::uint64_t>(image.tapes + offset);
-            offset += image.node_bytes(image.level(i));
-        }
-    }
-
     /// Moves keys and vectors out of the image into the staging arrays: the index is about to be mutated.
     void materialize() {
-        if (staged)
-            return;
-        if (has_image) {
-            image_keys(keys);
-            vectors.assign(image.vectors, image.vectors + (std::size_t)image.size * image.cols);
-        }
-        free_slots.clear(), free_head = 0, recycled.clear();
-        for (std::size_t slot = 0; slot < keys.size(); ++slot) // what `reindex_keys_` does after a load (index_dense.hpp:2162-2200)
-            if (keys[slot] == free_key_k)
-                free_slots.push_back((std::uint32_t)slot);
-        staged = true;
-        drop_device();
-        drop_image();
-        lookup_valid = false;
+        if (!members.staged)
+            members.stage(), drop_device();
+    }
+
+    /// A fresh device object, kept in `slot` only if `build` says it came out whole.
+    template <typename device_at, typename build_at> static const char* make_device(std::unique_ptr<device_at>& slot, build_at&& build) {
+        std::unique_ptr<device_at> fresh = std::make_unique<device_at>();
+        if (const char* e = build(*fresh))
+            return e;
+        slot = std::move(fresh);
+        return nullptr;
     }
 
     /// `usearch_isolate` / `usearch_compact` on an index that is still its image: the image's graph goes to the device as it
     /// stands and a builder takes it over (`builder_t::adopt` — nothing is linked anew), keys and vectors move into the staging
     /// arrays, and the image is left behind: from here on the index is served and saved from its device state.
     const char* adopt_image() {
-        if (staged || !has_image)
+        if (members.staged || !members.has_image())
             return nullptr;
-        builder_t* fresh = new (std::nothrow) builder_t();
-        if (!fresh)
-            return "Out of memory!";
-        delete snapshot, snapshot = nullptr; // the HBM copy of the image: the builder uploads its own
+        snapshot.reset(); // the HBM copy of the image: the builder uploads its own
         build_config_t config;
         config.expansion_add = (std::uint32_t)expansion_add;
-        if (const char* e = fresh->adopt(image, config, device)) {
-            delete fresh;
+        if (const char* e = make_device(builder, [&](builder_t& fresh) { return fresh.adopt(members.image, config, device); }))
             return e;
-        }
-        image_keys(keys);
-        vectors.assign(image.vectors, image.vectors + (std::size_t)image.size * image.cols);
-        free_slots.clear(), free_head = 0, recycled.clear();
-        for (std::size_t slot = 0; slot < keys.size(); ++slot)
-            if (keys[slot] == free_key_k)
-                free_slots.push_back((std::uint32_t)slot);
-        staged = true;
-        ++version;
-        memos.clear();
-        delete builder, builder = fresh;
-        drop_image();
-        lookup_valid = false;
+        members.stage();
+        ++version, memos.clear();
         return nullptr;
-    }
-
-    const std::unordered_multimap<std::uint64_t, std::uint32_t>& key_lookup() {
-        if (!lookup_valid) {
-            lookup.clear();
-            std::vector<std::uint64_t> from_image;
-            const std::vector<std::uint64_t>* source = &keys;
-            if (!staged && has_image)
-                image_keys(from_image), source = &from_image;
-            lookup.reserve(source->size());
-            for (std::size_t slot = 0; slot < source->size(); ++slot)
-                if ((*source)[slot] != free_key_k)
-                    lookup.emplace((*source)[slot], (std::uint32_t)slot);
-            lookup_valid = true;
-        }
-        return lookup;
-    }
-
-    const std::uint8_t* vector_of(std::uint32_t slot) const {
-        return staged ? vectors.data() + (std::size_t)slot * bpv() : image.vectors + (std::size_t)slot * image.cols;
     }
 
     /// Is the device index up to date with the host-side content? (Shared lock suffices to ask.)
     bool device_current() const {
-        if (staged)
-            return keys.empty() || (builder && builder->size() == keys.size() && recycled.empty());
-        return !has_image || snapshot != nullptr;
+        if (members.staged)
+            return members.keys.empty() || (builder && builder->size() == members.keys.size() && !members.has_stale());
+        return !members.has_image() || snapshot != nullptr;
     }
-    snapshot_t* device_index() { return staged ? (builder ? &builder->snapshot() : nullptr) : snapshot; }
+    snapshot_t* device_index() { return members.staged ? (builder ? &builder->snapshot() : nullptr) : snapshot.get(); }
 
     /// Brings the device index up to date (unique lock): uploads the image, builds the staged members, or — after a build —
     /// links only the members added since (`builder_t::extend`, the batch-deferred form of index.hpp:2780-2879).
     const char* ready(snapshot_t** out) {
         *out = nullptr;
-        if (staged) {
-            if (!builder && !keys.empty()) {
-                builder_t* fresh = new (std::nothrow) builder_t();
-                if (!fresh)
-                    return "Out of memory!";
-                build_config_t config;
-                config.connectivity = (std::uint32_t)connectivity;
-                config.expansion_add = (std::uint32_t)expansion_add;
-                config.multi = multi;
-                if (const char* e = fresh->build(metric, scalar, dimensions, vectors.data(), keys.size(), bpv(), false,
-                                                 keys.data(), config, device)) {
-                    delete fresh;
-                    return e;
-                }
-                builder = fresh;
-                recycled.clear(); // a build from the staging arrays has every member as it is now
-            } else if (builder && !recycled.empty()) {
-                // slots a removal freed and an add took over: the members the device still holds there are replaced and linked anew
-                // (index_gt::update); slots beyond what is linked are simply part of the members still to come
-                std::vector<std::uint32_t> slots;
-                std::vector<std::uint64_t> new_keys;
-                std::vector<std::uint8_t> rows;
-                std::sort(recycled.begin(), recycled.end());
-                recycled.erase(std::unique(recycled.begin(), recycled.end()), recycled.end());
-                for (std::uint32_t slot : recycled)
-                    if (slot < builder->size() && keys[slot] != free_key_k) {
-                        slots.push_back(slot);
-                        new_keys.push_back(keys[slot]);
-                        rows.insert(rows.end(), vectors.data() + (std::size_t)slot * bpv(), vectors.data() + (std::size_t)(slot + 1) * bpv());
-                    }
-                if (const char* e = builder->update(slots.data(), slots.size(), rows.data(), bpv(), new_keys.data())) {
-                    delete builder, builder = nullptr;
-                    return e;
-                }
-                recycled.clear();
-            }
-            if (builder && builder->size() < keys.size()) {
-                const std::size_t linked = (std::size_t)builder->size();
-                if (const char* e = builder->extend(vectors.data() + linked * bpv(), keys.size() - linked, bpv(), false,
-                                                    keys.data() + linked)) {
-                    delete builder, builder = nullptr; // the arrays may be half grown: start over at the next call
-                    return e;
-                }
-            }
-            *out = builder ? &builder->snapshot() : nullptr;
-            if (*out && threads_search)
-                (*out)->set_concurrency(threads_search);
-            return nullptr;
-        }
-        if (has_image && !snapshot) {
-            snapshot_t* fresh = new (std::nothrow) snapshot_t();
-            if (!fresh)
-                return "Out of memory!";
-            if (const char* e = fresh->build(image, device)) {
-                delete fresh;
+        const std::vector<std::uint64_t>& keys = members.keys;
+        const std::size_t bpv = members.bytes_per_vector;
+        if (members.staged && !builder && !keys.empty()) {
+            build_config_t config;
+            config.connectivity = (std::uint32_t)connectivity, config.expansion_add = (std::uint32_t)expansion_add, config.multi = multi;
+            if (const char* e = make_device(builder, [&](builder_t& fresh) {
+                    return fresh.build(metric, scalar, dimensions, members.vectors.data(), keys.size(), bpv, false, keys.data(), config, device);
+                }))
                 return e;
-            }
-            snapshot = fresh;
+            members.settle_stale(); // a build from the staging arrays has every member as it is now
+        } else if (members.staged && builder && members.has_stale()) {
+            // slots a removal freed and an add took over: the members the device still holds there are replaced and linked anew
+            // (index_gt::update); slots beyond what is linked are simply part of the members still to come
+            const members_t::stale_t stale = members.stale((std::size_t)builder->size());
+            if (const char* e = builder->update(stale.slots.data(), stale.slots.size(), stale.rows.data(), bpv, stale.keys.data()))
+                return builder.reset(), e;
+            members.settle_stale();
         }
-        *out = snapshot;
+        if (members.staged && builder && builder->size() < keys.size()) {
+            const std::size_t linked = (std::size_t)builder->size();
+            if (const char* e = builder->extend(members.vectors.data() + linked * bpv, keys.size() - linked, bpv, false, keys.data() + linked))
+                return builder.reset(), e; // the arrays may be half grown: start over at the next call
+        }
+        if (!members.staged && members.has_image() && !snapshot)
+            if (const char* e = make_device(snapshot, [&](snapshot_t& fresh) { return fresh.build(members.image, device); }))
+                return e;
+        *out = device_index();
         if (*out && threads_search)
             (*out)->set_concurrency(threads_search);
         return nullptr;
     }
-
 };
 
 index_t* as_index(usearch_index_t handle) { return static_cast<index_t*>(handle); }
@@ -445,16 +294,12 @@ struct made_filter_t {
 
 /// The host callback over every member, as one bit per slot (what `usearch_filtered_search` has to do per call, and
 /// `usearch_filter_from_callback` once). Any lock on the index will do.
-static void callback_bits(index_t& index, int (*filter)(usearch_key_t key, void* filter_state), void* filter_state,
-                          std::vector<std::uint32_t>& bits) {
-    std::vector<std::uint64_t> from_image;
-    const std::vector<std::uint64_t>* member_keys = &index.keys;
-    if (!index.staged && index.has_image)
-        index.image_keys(from_image), member_keys = &from_image;
-    bits.assign((member_keys->size() + 31) / 32 + 1, 0);
-    for (std::size_t slot = 0; slot < member_keys->size(); ++slot)
-        if ((*member_keys)[slot] != free_key_k && filter((*member_keys)[slot], filter_state))
+static void callback_bits(index_t& index, callback_t filter, void* filter_state, std::vector<std::uint32_t>& bits) {
+    bits.assign((index.members.size() + 31) / 32 + 1, 0);
+    index.members.each_key([&](std::size_t slot, std::uint64_t key) {
+        if (key != free_key_k && filter(key, filter_state))
             bits[slot >> 5] |= 1u << (slot & 31);
+    });
 }
 
 /**
@@ -543,9 +388,8 @@ template <typename make_at> usearch_filter_t make_filter(usearch_index_t handle,
         snapshot_t* device_index = nullptr;
         if (const char* e = index.ready(&device_index))
             return fail(error, e), nullptr;
-        std::unique_ptr<made_filter_t> made(new made_filter_t());
-        made->index = &index;
-        made->version = index.version;
+        std::unique_ptr<made_filter_t> made = std::make_unique<made_filter_t>();
+        made->index = &index, made->version = index.version;
         if (device_index)
             if (const char* e = make(index, *device_index, made->bitmap))
                 return fail(error, e), nullptr;
@@ -553,11 +397,12 @@ template <typename make_at> usearch_filter_t make_filter(usearch_index_t handle,
     });
 }
 
-
-/// An index without nodes still serializes to its headers (index_dense.hpp:995-1062 with zero rows).
+/// An index without nodes still serializes to its headers (index_dense.hpp:995-1062 with zero rows): the matrix dimensions, the
+/// 64-byte head and the five words of the graph header.
+constexpr std::size_t empty_image_bytes_k = 8 + 64 + 40;
 void write_empty_image(const index_t& index, std::uint8_t* p) {
-    std::memset(p, 0, 8 + 64 + 40);
-    const std::uint32_t cols = (std::uint32_t)index.bpv();
+    std::memset(p, 0, empty_image_bytes_k);
+    const std::uint32_t cols = (std::uint32_t)index.members.bytes_per_vector;
     std::memcpy(p + 4, &cols, 4);
     p += 8;
     std::memcpy(p, "usearch", 7);
@@ -573,60 +418,39 @@ void write_empty_image(const index_t& index, std::uint8_t* p) {
     std::memcpy(p, header, 40);
 }
 
-/// Serialized form of the current content: the image as it was loaded, or what the device build writes.
+/// Serialized form of the current content: the image as it was loaded, or what the device build writes. It goes into a vector that
+/// grows to fit, into the caller's buffer, or nowhere (the length alone is asked for).
 const char* serialize(index_t& index, std::vector<std::uint8_t>* into_vector, void* into_buffer, std::size_t buffer_length,
                       std::size_t* length_out) {
-    if (!index.staged) {
-        const std::size_t length = index.has_image ? index.image_length : 8 + 64 + 40;
+    std::uint8_t* target = nullptr;
+    const auto claim = [&](std::size_t length) -> const char* { // reports the length; `target`: that many writable bytes, if any are wanted
         if (length_out)
             *length_out = length;
-        std::uint8_t* target = nullptr;
         if (into_vector)
             into_vector->resize(length), target = into_vector->data();
-        else if (into_buffer) {
-            if (buffer_length < length)
-                return "Buffer is too small";
+        else if (into_buffer && buffer_length < length)
+            return "Buffer is too small";
+        else
             target = static_cast<std::uint8_t*>(into_buffer);
-        }
-        if (target) {
-            if (index.has_image)
-                std::memcpy(target, index.image_bytes, length);
-            else
-                write_empty_image(index, target);
-        }
+        return nullptr;
+    };
+    if (!index.members.staged && index.members.has_image()) {
+        if (const char* e = claim(index.members.image_length()))
+            return e;
+        if (target)
+            std::memcpy(target, index.members.bytes.get(), index.members.image_length());
         return nullptr;
     }
     snapshot_t* device_index = nullptr;
-    if (const char* e = index.ready(&device_index))
+    if (index.members.staged)
+        if (const char* e = index.ready(&device_index))
+            return e;
+    const std::size_t length = index.builder ? index.builder->serialized_length() : empty_image_bytes_k;
+    if (const char* e = claim(length))
         return e;
-    if (!index.builder) { // staged but empty
-        if (length_out)
-            *length_out = 8 + 64 + 40;
-        std::uint8_t* target = nullptr;
-        if (into_vector)
-            into_vector->resize(8 + 64 + 40), target = into_vector->data();
-        else if (into_buffer) {
-            if (buffer_length < 8 + 64 + 40)
-                return "Buffer is too small";
-            target = static_cast<std::uint8_t*>(into_buffer);
-        }
-        if (target)
-            write_empty_image(index, target);
-        return nullptr;
-    }
-    const std::size_t length = index.builder->serialized_length();
-    if (length_out)
-        *length_out = length;
-    if (into_vector) {
-        into_vector->resize(length);
-        return index.builder->save_buffer(into_vector->data(), length);
-    }
-    if (into_buffer) {
-        if (buffer_length < length)
-            return "Buffer is too small";
-        return index.builder->save_buffer(into_buffer, length);
-    }
-    return nullptr;
+    if (target && !index.builder) // never staged, or staged but empty
+        write_empty_image(index, target);
+    return target && index.builder ? index.builder->save_buffer(target, length) : nullptr;
 }
 
 void fill_options(const image_t& image, usearch_init_options_t* options) { // c/lib.cpp:224-242
@@ -640,14 +464,150 @@ void fill_options(const image_t& image, usearch_init_options_t* options) { // c/
     options->multi = image.multi;
 }
 
-/// `dump_to`-style padding for queries that cannot match anything.
-void pad_results(usearch_key_t* keys, usearch_distance_t* distances, std::size_t count) {
-    for (std::size_t i = 0; i < count; ++i) {
-        if (keys)
-            keys[i] = 0;
-        if (distances)
-            std::memcpy(distances + i, &signaling_nan_bits_k, 4);
+/// Where the results of a batch land. The engine writes `count` keys and distances per query, densely; the caller's buffers are
+/// strided and either may be missing. A single query, or dense strides, needs no staging copy at all: the engine writes into the
+/// caller's buffers (a missing one gets spare space); anything else goes through dense arrays and `scatter`.
+struct results_t {
+    results_t(std::size_t queries, std::size_t count, usearch_key_t* keys, std::size_t keys_stride, usearch_distance_t* distances,
+              std::size_t distances_stride, std::size_t* counts)
+        : found(queries, 0), visited(queries, 0), computed(queries, 0), queries_(queries), count_(count), keys_stride_(keys_stride),
+          distances_stride_(distances_stride), counts_(counts), keys_(keys), distances_(distances),
+          direct_(queries == 1 || (keys_stride == count * 8 && distances_stride == count * 4)),
+          dense_keys_(direct_ && keys ? 0 : queries * count), dense_distances_(direct_ && distances ? 0 : queries * count) {}
+
+    std::vector<std::uint64_t> found, visited, computed; ///< per query, as the engine reports them
+    std::uint64_t* keys() { return direct_ && keys_ ? reinterpret_cast<std::uint64_t*>(keys_) : dense_keys_.data(); }
+    float* distances() { return direct_ && distances_ ? distances_ : dense_distances_.data(); }
+    /// Queries that cannot match anything (`dump_to`-style padding).
+    void pad() {
+        std::fill_n(keys(), queries_ * count_, std::uint64_t(0));
+        for (std::size_t i = 0; i < queries_ * count_; ++i)
+            std::memcpy(distances() + i, &signaling_nan_bits_k, 4);
     }
+    /// Keys, distances and counts back through the caller's strides, and the two totals. → what the first query found.
+    std::size_t scatter(std::size_t* visited_total = nullptr, std::size_t* computed_total = nullptr) {
+        std::size_t total_visited = 0, total_computed = 0;
+        for (std::size_t q = 0; q < queries_; ++q) {
+            if (!direct_ && keys_)
+                std::memcpy(reinterpret_cast<std::uint8_t*>(keys_) + q * keys_stride_, dense_keys_.data() + q * count_, count_ * 8);
+            if (!direct_ && distances_)
+                std::memcpy(reinterpret_cast<std::uint8_t*>(distances_) + q * distances_stride_, dense_distances_.data() + q * count_,
+                            count_ * 4);
+            if (counts_)
+                counts_[q] = (std::size_t)found[q];
+            total_visited += (std::size_t)visited[q], total_computed += (std::size_t)computed[q];
+        }
+        if (visited_total)
+            *visited_total = total_visited;
+        if (computed_total)
+            *computed_total = total_computed;
+        return (std::size_t)found[0];
+    }
+
+  private:
+    std::size_t queries_, count_, keys_stride_, distances_stride_, *counts_;
+    usearch_key_t* keys_;
+    usearch_distance_t* distances_;
+    bool direct_; ///< the engine writes into the caller's buffers
+    std::vector<std::uint64_t> dense_keys_;
+    std::vector<float> dense_distances_;
+};
+
+/// What the launch of a search gets for its predicate.
+struct predicate_t {
+    enum how_t {
+        everyone_k,    ///< no predicate
+        host_bits_k,   ///< `bits`, one per slot, which the launch uploads
+        device_bits_k, ///< `extras`: a bitmap that is in HBM already
+        answered_k,    ///< nothing: the last lazy round asked nothing, its results are the answer
+    } how = everyone_k;
+    std::vector<std::uint32_t> bits;
+    search_extras_t extras;
+    std::shared_ptr<filter_t> remembered; ///< keeps a memoised bitmap alive while this call reads it
+};
+
+/// USEARCH_AMD_FILTER_MEMO=1: the bitmap of (callback, state pointer, index version), from the memo or made now and remembered.
+const char* remembered_predicate(index_t& index, snapshot_t& device_index, callback_t filter, void* filter_state, predicate_t& out) {
+    std::lock_guard<std::mutex> memo_lock(index.memo_mutex); // one maker at a time; searches overlap
+    for (const index_t::filter_memo_t& memo : index.memos)
+        if (memo.filter == filter && memo.state == filter_state && memo.version == index.version)
+            out.remembered = memo.bitmap;
+    if (!out.remembered) {
+        callback_bits(index, filter, filter_state, out.bits);
+        std::unique_ptr<filter_t> fresh;
+        if (const char* e = filter_t::from_bits(device_index, out.bits.data(), out.bits.size(), fresh))
+            return e;
+        out.remembered = std::move(fresh);
+        std::vector<index_t::filter_memo_t> kept;
+        kept.push_back({filter, filter_state, index.version, out.remembered});
+        for (index_t::filter_memo_t& memo : index.memos) // bitmaps of older versions describe nothing now
+            if (memo.version == index.version && kept.size() < index_t::memo_limit_k)
+                kept.push_back(std::move(memo));
+        index.memos.swap(kept);
+    }
+    out.extras.allow_bits = out.remembered->bits();
+    out.how = predicate_t::device_bits_k;
+    return nullptr;
+}
+
+/// The callback only for the members the walk wants to admit (`lazy_predicate_t`): provisional runs of `launch` until one asks
+/// nothing; that one is the answer (`*settled`). A predicate that keeps pushing the walk outward is left unsettled.
+template <typename launch_at>
+const char* lazy_rounds(std::size_t members, int device, callback_t filter, void* filter_state, launch_at&& launch, bool* settled) {
+    lazy_predicate_t lazy;
+    if (const char* e = lazy.open(members, device))
+        return e;
+    *settled = false;
+    for (int round = 0; round < lazy_predicate_t::rounds_limit_k && !*settled; ++round) {
+        search_extras_t lazy_extras;
+        lazy.fill(lazy_extras);
+        if (const char* e = lazy.before_run())
+            return e;
+        if (const char* e = launch(nullptr, &lazy_extras))
+            return e;
+        std::size_t asked = 0;
+        bool overflow = false;
+        if (const char* e = lazy.after_run(filter, filter_state, &asked, &overflow))
+            return e;
+        *settled = asked == 0 && !overflow;
+        if (overflow)
+            break; // the walk is visiting a large part of the index (a predicate that rejects nearly everything)
+    }
+    return nullptr;
+}
+
+/// Turns what the caller gave — a made filter, a host callback, or nothing — into what the launch gets. `device_index` may be null
+/// (nothing indexed yet). A made filter is a bitmap in HBM already (usearch_filter_from_*): nothing per member happens here. A
+/// callback is a host function: remembered if the memo is on, else evaluated lazily through `launch`, else — or when the lazy
+/// rounds do not settle — run once per member into one bit per slot. The traversal applies the bits where the reference applies the
+/// callback (index.hpp:4200-4205, 4236-4240): the reference's results as long as the predicate is a pure function of the key. The
+/// last resort costs O(members) callbacks PER CALL, the reference makes a few thousand: callers that search more than once under
+/// one predicate make a `usearch_filter_t` instead, or switch the memo on (USEARCH_AMD_FILTER_MEMO=1).
+template <typename launch_at>
+const char* resolve_predicate(index_t& index, snapshot_t* device_index, const made_filter_t* made, callback_t filter,
+                              void* filter_state, launch_at&& launch, predicate_t& out) {
+    if (made) {
+        if (made->index != &index || made->version != index.version)
+            return "The index changed since the filter was made";
+        if (made->bitmap)
+            out.extras.allow_bits = made->bitmap->bits();
+        out.how = predicate_t::device_bits_k;
+        return nullptr;
+    }
+    if (!filter)
+        return nullptr;
+    if (index.filter_memo && device_index)
+        return remembered_predicate(index, *device_index, filter, filter_state, out);
+    if (index.filter_lazy && device_index) {
+        bool settled = false;
+        if (const char* e = lazy_rounds(index.members.size(), device_index->device(), filter, filter_state, launch, &settled))
+            return e;
+        if (settled)
+            return out.how = predicate_t::answered_k, nullptr;
+    }
+    callback_bits(index, filter, filter_state, out.bits);
+    out.how = predicate_t::host_bits_k;
+    return nullptr;
 }
 
 } // namespace
@@ -657,52 +617,36 @@ extern "C" {
 char const* usearch_version(void) { return "2.21.0"; }
 
 usearch_index_t usearch_init(usearch_init_options_t* options, usearch_error_t* error) {
-    index_t* index = new (std::nothrow) index_t();
-    if (!index) {
-        fail(error, "Out of memory!");
-        return nullptr;
-    }
-    index->combiner.window_limit(std::chrono::microseconds(env_size("USEARCH_AMD_COALESCE_WINDOW_US", 200)));
-    if (!options) // an empty shell to `usearch_load` / `usearch_view` into, c/lib.cpp:142-147
-        return index;
-    if (options->metric) {
-        fail(error, "User-defined metric functions cannot run on the device");
-        delete index;
-        return nullptr;
-    }
-    index->metric = metric_from_c(options->metric_kind);
-    index->scalar = scalar_from_c(options->quantization);
-    if (index->metric == metric_unknown_k || index->scalar == scalar_unknown_k) {
-        fail(error, index->metric == metric_unknown_k ? "Unknown metric kind!" : "Unknown scalar kind!");
-        delete index;
-        return nullptr;
-    }
-    if (!kernel_available(index->metric, index->scalar)) {
-        fail(error, "No MI355X kernel for this metric / scalar kind combination");
-        delete index;
-        return nullptr;
-    }
-    index->dimensions = options->dimensions;
-    if (options->connectivity)
-        index->connectivity = options->connectivity;
-    if (options->expansion_add)
-        index->expansion_add = options->expansion_add;
-    if (options->expansion_search)
-        index->expansion_search = options->expansion_search;
-    index->multi = options->multi;
-    // the device builder's limits, said here instead of at the first search (build.hip: a node's existing and incoming links
-    // are ranked by one wave)
-    if (2 * index->connectivity > builder_max_connectivity_base_k || index->connectivity < 2) {
-        fail(error, "Connectivity must be between 2 and 64 for the device builder (base connectivity 2·M ≤ 128)");
-        delete index;
-        return nullptr;
-    }
-    if (index->expansion_add > builder_max_expansion_k) {
-        fail(error, "Expansion (add) is too large for the device builder");
-        delete index;
-        return nullptr;
-    }
-    return index;
+    return guarded(error, usearch_index_t(nullptr), [&]() -> usearch_index_t {
+        std::unique_ptr<index_t> index = std::make_unique<index_t>();
+        index->combiner.window_limit(std::chrono::microseconds(env_size("USEARCH_AMD_COALESCE_WINDOW_US", 200)));
+        if (!options) // an empty shell to `usearch_load` / `usearch_view` into, c/lib.cpp:142-147
+            return index.release();
+        if (options->metric)
+            return fail(error, "User-defined metric functions cannot run on the device"), nullptr;
+        index->metric = metric_from_c(options->metric_kind);
+        index->scalar = scalar_from_c(options->quantization);
+        if (index->metric == metric_unknown_k || index->scalar == scalar_unknown_k)
+            return fail(error, index->metric == metric_unknown_k ? "Unknown metric kind!" : "Unknown scalar kind!"), nullptr;
+        if (!kernel_available(index->metric, index->scalar))
+            return fail(error, "No MI355X kernel for this metric / scalar kind combination"), nullptr;
+        index->dimensions = options->dimensions;
+        index->members.bytes_per_vector = bytes_per_vector(index->scalar, index->dimensions);
+        if (options->connectivity)
+            index->connectivity = options->connectivity;
+        if (options->expansion_add)
+            index->expansion_add = options->expansion_add;
+        if (options->expansion_search)
+            index->expansion_search = options->expansion_search;
+        index->multi = options->multi;
+        // the device builder's limits, said here instead of at the first search (build.hip: a node's existing and incoming links
+        // are ranked by one wave)
+        if (2 * index->connectivity > builder_max_connectivity_base_k || index->connectivity < 2)
+            return fail(error, "Connectivity must be between 2 and 64 for the device builder (base connectivity 2·M ≤ 128)"), nullptr;
+        if (index->expansion_add > builder_max_expansion_k)
+            return fail(error, "Expansion (add) is too large for the device builder"), nullptr;
+        return index.release();
+    });
 }
 
 void usearch_free(usearch_index_t handle, usearch_error_t*) { delete as_index(handle); }
@@ -712,7 +656,7 @@ size_t usearch_memory_usage(usearch_index_t handle, usearch_error_t*) {
     unique_lock_t lock(index.mutex);
     // what the host side holds (the handle itself, the reserved staging arrays, an owned image) plus the arrays in HBM; never
     // zero for a live index (c/test.c:83 expects as much of a freshly reserved one)
-    std::size_t bytes = sizeof(index_t) + index.image_owned.capacity() + index.vectors.capacity() + index.keys.capacity() * 8;
+    std::size_t bytes = sizeof(index_t) + index.members.host_bytes();
     if (index.snapshot)
         bytes += index.snapshot->device_bytes();
     if (index.builder)
@@ -722,10 +666,8 @@ size_t usearch_memory_usage(usearch_index_t handle, usearch_error_t*) {
 
 char const* usearch_hardware_acceleration(usearch_index_t, usearch_error_t* error) {
     int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) {
-        fail(error, "No HIP device: this library has no CPU path, every search will fail");
-        return "none";
-    }
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0)
+        return fail(error, "No HIP device: this library has no CPU path, every search will fail"), "none";
     return "gfx950";
 }
 
@@ -770,13 +712,9 @@ void usearch_load_buffer(usearch_index_t handle, void const* buffer, size_t leng
     index_t& index = *as_index(handle);
     guarded(error, [&] { // the copy of a large file may not fit: an error string, not an exception across the C ABI
         unique_lock_t lock(index.mutex);
-        index.drop_device();
-        index.drop_image();
-        index.image_owned.assign(static_cast<const std::uint8_t*>(buffer), static_cast<const std::uint8_t*>(buffer) + length);
-        if (const char* e = index.open_image(index.image_owned.data(), length)) {
-            index.drop_image();
+        index.unload();
+        if (const char* e = index.open_image(copied_bytes(buffer, length)))
             fail(error, e);
-        }
     });
 }
 
@@ -784,14 +722,14 @@ void usearch_view_buffer(usearch_index_t handle, void const* buffer, size_t leng
     index_t& index = *as_index(handle);
     guarded(error, [&] {
         unique_lock_t lock(index.mutex);
-        index.drop_device();
-        index.drop_image();
-        if (const char* e = index.open_image(buffer, length)) // the caller's buffer is borrowed for the index lifetime
+        index.unload();
+        if (const char* e = index.open_image(held_bytes(buffer, length, image_release_t::borrowed_k))) // the caller's buffer is borrowed for the index lifetime
             fail(error, e);
     });
 }
 
-static const char* map_file(char const* path, void** mapped, std::size_t* length) {
+/// The file at `path`, mapped read-only for as long as `mapped` lives.
+static const char* map_file(char const* path, image_bytes_t& mapped) {
     int fd = ::open(path, O_RDONLY);
     if (fd < 0)
         return "Can't open file!";
@@ -804,7 +742,7 @@ static const char* map_file(char const* path, void** mapped, std::size_t* length
     ::close(fd);
     if (m == MAP_FAILED)
         return "Can't memory-map the file";
-    *mapped = m, *length = (std::size_t)st.st_size;
+    mapped = held_bytes(m, (std::size_t)st.st_size, image_release_t::mapped_k);
     return nullptr;
 }
 
@@ -812,27 +750,20 @@ void usearch_view(usearch_index_t handle, char const* path, usearch_error_t* err
     index_t& index = *as_index(handle);
     guarded(error, [&] {
         unique_lock_t lock(index.mutex);
-        index.drop_device();
-        index.drop_image();
-        void* mapped = nullptr;
-        std::size_t length = 0;
-        if (const char* e = map_file(path, &mapped, &length))
+        index.unload();
+        image_bytes_t mapped;
+        if (const char* e = map_file(path, mapped))
             return fail(error, e);
-        index.mapping = mapped, index.mapping_length = length;
-        if (const char* e = index.open_image(mapped, length)) {
-            index.drop_image();
+        if (const char* e = index.open_image(std::move(mapped)))
             fail(error, e);
-        }
     });
 }
 
 void usearch_load(usearch_index_t handle, char const* path, usearch_error_t* error) {
-    void* mapped = nullptr;
-    std::size_t length = 0;
-    if (const char* e = map_file(path, &mapped, &length))
+    image_bytes_t mapped;
+    if (const char* e = map_file(path, mapped))
         return fail(error, e);
-    usearch_load_buffer(handle, mapped, length, error); // copies: the file may change or vanish afterwards
-    ::munmap(mapped, length);
+    usearch_load_buffer(handle, mapped.get(), mapped.get_deleter().length, error); // copies: the file may change or vanish afterwards
 }
 
 void usearch_metadata_buffer(void const* buffer, size_t length, usearch_init_options_t* options, usearch_error_t* error) {
@@ -845,29 +776,22 @@ void usearch_metadata_buffer(void const* buffer, size_t length, usearch_init_opt
 }
 
 void usearch_metadata(char const* path, usearch_init_options_t* options, usearch_error_t* error) {
-    void* mapped = nullptr;
-    std::size_t length = 0;
-    if (const char* e = map_file(path, &mapped, &length))
+    image_bytes_t mapped;
+    if (const char* e = map_file(path, mapped))
         return fail(error, e);
-    usearch_metadata_buffer(mapped, length, options, error);
-    ::munmap(mapped, length);
+    usearch_metadata_buffer(mapped.get(), mapped.get_deleter().length, options, error);
 }
 
 size_t usearch_size(usearch_index_t handle, usearch_error_t*) {
     index_t& index = *as_index(handle);
     unique_lock_t lock(index.mutex);
-    if (!index.staged)
-        return index.has_image ? (std::size_t)index.image.count_present : 0;
-    std::size_t present = 0;
-    for (std::uint64_t key : index.keys)
-        present += key != free_key_k;
-    return present;
+    return index.members.present();
 }
 
 size_t usearch_capacity(usearch_index_t handle, usearch_error_t*) {
     index_t& index = *as_index(handle);
     unique_lock_t lock(index.mutex);
-    return std::max(index.capacity, index.size());
+    return std::max(index.capacity, index.members.size());
 }
 
 size_t usearch_dimensions(usearch_index_t handle, usearch_error_t*) { return as_index(handle)->dimensions; }
@@ -877,10 +801,7 @@ void usearch_reserve(usearch_index_t handle, size_t capacity, usearch_error_t* e
     index_t& index = *as_index(handle);
     guarded(error, [&] {
         unique_lock_t lock(index.mutex);
-        if (index.staged || !index.has_image) { // the staging arrays are where `usearch_add` puts members
-            index.keys.reserve(capacity);
-            index.vectors.reserve(capacity * index.bpv());
-        }
+        index.members.reserve(capacity); // the staging arrays are where `usearch_add` puts members
         index.capacity = std::max(index.capacity, capacity); // only once the memory is there
     });
 }
@@ -936,40 +857,25 @@ void usearch_add(usearch_index_t handle, usearch_key_t key, void const* vector, 
             return fail(error, "Unknown scalar kind!");
         if (key == free_key_k)
             return fail(error, "Free key is reserved");
-        if (!index.dimensions || !index.bpv())
+        members_t& members = index.members;
+        if (!index.dimensions || !members.bytes_per_vector)
             return fail(error, "Index is not initialized");
         // a loaded / viewed image at capacity: the slots its tombstones hold are room too — the reference fills `free_keys_` right
         // after a load (`reindex_keys_`, index_dense.hpp:2162-2200) — and here they are only listed once the image is staged
-        if (index.size() >= index.capacity && !index.staged && index.has_image && index.key_lookup().size() < index.size())
+        if (members.size() >= index.capacity && !members.staged && members.has_image() && members.lookup().size() < members.size())
             index.materialize();
-        if (index.size() >= index.capacity && !(index.staged && index.free_head < index.free_slots.size()))
+        if (members.size() >= index.capacity && !members.has_free_slot())
             return fail(error, "Reserve capacity ahead of insertions!"); // index.hpp:2812-2818: no growth on its own; a freed slot is room
-        if (!index.multi && index.key_lookup().count(key))
+        if (!index.multi && members.lookup().count(key))
             return fail(error, "Duplicate keys not allowed in high-level wrappers");
         index.materialize();
-        const std::size_t bpv = index.bpv();
-        // a slot that a removal freed is taken first, oldest first (index_dense.hpp:1479-1511: `free_keys_.try_pop`)
-        const bool reuse = index.free_head < index.free_slots.size();
-        const std::size_t slot = reuse ? index.free_slots[index.free_head++] : index.keys.size();
-        if (slot + 1 >= none_slot_k)
+        std::uint8_t* target = members.take_slot(key);
+        if (!target)
             return fail(error, "Index is too large for 32-bit slots");
-        if (!reuse)
-            index.vectors.resize((slot + 1) * bpv);
-        std::uint8_t* target = index.vectors.data() + slot * bpv;
-        std::memset(target, 0, bpv);
+        std::memset(target, 0, members.bytes_per_vector);
         if (!cast_vector(kind, index.scalar, static_cast<const std::uint8_t*>(vector), index.dimensions, target))
-            std::memcpy(target, vector, bpv);
-        if (reuse) {
-            index.keys[slot] = key;
-            index.recycled.push_back((std::uint32_t)slot);
-            if (index.free_head == index.free_slots.size())
-                index.free_slots.clear(), index.free_head = 0;
-        } else {
-            index.keys.push_back(key);
-        }
+            std::memcpy(target, vector, members.bytes_per_vector);
         ++index.version;
-        if (index.lookup_valid)
-            index.lookup.emplace(key, (std::uint32_t)slot);
         // the device index, if there is one, stays: the next search links the members added since (builder_t::extend) — or this
         // call does, for hosts that want the reference's visibility (a member is findable the moment `add` returns)
         const std::uint64_t arrived = index.searches_arrived.load(std::memory_order_acquire);
@@ -987,7 +893,7 @@ bool usearch_contains(usearch_index_t handle, usearch_key_t key, usearch_error_t
     index_t& index = *as_index(handle);
     return guarded(error, false, [&] { // the key table is filled on first use
         unique_lock_t lock(index.mutex);
-        return index.key_lookup().count(key) != 0;
+        return index.members.lookup().count(key) != 0;
     });
 }
 
@@ -995,7 +901,7 @@ size_t usearch_count(usearch_index_t handle, usearch_key_t key, usearch_error_t*
     index_t& index = *as_index(handle);
     return guarded(error, std::size_t(0), [&] {
         unique_lock_t lock(index.mutex);
-        return (std::size_t)index.key_lookup().count(key);
+        return (std::size_t)index.members.lookup().count(key);
     });
 }
 
@@ -1004,8 +910,7 @@ size_t usearch_count(usearch_index_t handle, usearch_key_t key, usearch_error_t*
 static size_t search_shared(index_t& index, void const* queries, scalar_kind_t kind, std::size_t queries_count,
                             std::size_t queries_stride, std::size_t count, usearch_key_t* keys, std::size_t keys_stride,
                             usearch_distance_t* distances, std::size_t distances_stride, std::size_t* counts,
-                            std::size_t* visited_total, std::size_t* computed_total,
-                            int (*filter)(usearch_key_t key, void* filter_state), void* filter_state,
+                            std::size_t* visited_total, std::size_t* computed_total, callback_t filter, void* filter_state,
                             usearch_error_t* error, const made_filter_t* made = nullptr) {
     if (!queries_count || !count)
         return 0;
@@ -1017,117 +922,24 @@ static size_t search_shared(index_t& index, void const* queries, scalar_kind_t k
                 shared_lock_t shared(index.mutex);
                 if (index.device_current()) {
                     snapshot_t* device_index = index.device_index();
-                    // a single query that lands in the caller's dense buffers needs no staging copy at all
-                    const bool direct = queries_count == 1 || (keys_stride == count * 8 && distances_stride == count * 4);
-                    std::vector<std::uint64_t> found(queries_count, 0), visited(queries_count, 0), computed(queries_count, 0);
-                    std::vector<std::uint64_t> dense_keys(direct ? 0 : queries_count * count);
-                    std::vector<float> dense_distances(direct ? 0 : queries_count * count);
-                    std::uint64_t* out_keys = direct ? reinterpret_cast<std::uint64_t*>(keys) : dense_keys.data();
-                    float* out_distances = direct ? distances : dense_distances.data();
-                    std::vector<std::uint64_t> spare_keys;
-                    std::vector<float> spare_distances;
-                    if (!out_keys)
-                        spare_keys.resize(queries_count * count), out_keys = spare_keys.data();
-                    if (!out_distances)
-                        spare_distances.resize(queries_count * count), out_distances = spare_distances.data();
-                    std::vector<std::uint32_t> bits;
-                    search_extras_t extras;
-                    std::shared_ptr<filter_t> remembered; // keeps a memoised bitmap alive while this call reads it
-                    bool answered_lazily = false;
-                    if (made) {
-                        // the predicate is already a bitmap in HBM (usearch_filter_from_*): nothing per member happens here
-                        if (made->index != &index || made->version != index.version)
-                            return fail(error, "The index changed since the filter was made");
-                        if (made->bitmap)
-                            extras.allow_bits = made->bitmap->bits();
-                    } else if (filter) {
-                        // The callback is a host function: run it once per member and hand the device one bit per slot. The
-                        // traversal then applies it where the reference does (index.hpp:4200-4205, 4236-4240), so results are
-                        // the reference's as long as the predicate is a pure function of the key. O(members) callbacks PER
-                        // CALL — the reference makes a few thousand; callers that search more than once under one predicate
-                        // make a `usearch_filter_t` instead — or, if the predicate is pure for as long as its state pointer
-                        // stays the same, switch the memo on (USEARCH_AMD_FILTER_MEMO=1): the binary stays as it is.
-                        if (index.filter_memo && device_index) {
-                            std::lock_guard<std::mutex> memo_lock(index.memo_mutex); // one maker at a time; searches overlap
-                            for (const index_t::filter_memo_t& memo : index.memos)
-                                if (memo.filter == filter && memo.state == filter_state && memo.version == index.version)
-                                    remembered = memo.bitmap;
-                            if (!remembered) {
-                                callback_bits(index, filter, filter_state, bits);
-                                std::unique_ptr<filter_t> fresh;
-                                if (const char* e = filter_t::from_bits(*device_index, bits.data(), bits.size(), fresh))
-                                    return fail(error, e);
-                                remembered = std::move(fresh);
-                                std::vector<index_t::filter_memo_t> kept;
-                                kept.push_back({filter, filter_state, index.version, remembered});
-                                for (index_t::filter_memo_t& memo : index.memos) // bitmaps of older versions describe nothing now
-                                    if (memo.version == index.version && kept.size() < index_t::memo_limit_k)
-                                        kept.push_back(std::move(memo));
-                                index.memos.swap(kept);
-                            }
-                            extras.allow_bits = remembered->bits();
-                        } else if (index.filter_lazy && device_index) {
-                            // the callback only for the members the walk wants to admit (`lazy_predicate_t`): provisional runs until
-                            // one asks nothing; that one is the answer
-                            lazy_predicate_t lazy;
-                            if (const char* e = lazy.open(index.size(), device_index->device()))
-                                return fail(error, e);
-                            bool settled = false;
-                            for (int round = 0; round < lazy_predicate_t::rounds_limit_k && !settled; ++round) {
-                                search_extras_t lazy_extras;
-                                lazy.fill(lazy_extras);
-                                if (const char* e = lazy.before_run())
-                                    return fail(error, e);
-                                if (const char* e = device_index->search_host(queries, kind, queries_count, queries_stride, count,
-                                                                              index.expansion_search, out_keys, out_distances, found.data(),
-                                                                              visited.data(), computed.data(), search_tuning_t{}, nullptr,
-                                                                              nullptr, &lazy_extras))
-                                    return fail(error, e);
-                                std::size_t asked = 0;
-                                bool overflow = false;
-                                if (const char* e = lazy.after_run(filter, filter_state, &asked, &overflow))
-                                    return fail(error, e);
-                                settled = asked == 0 && !overflow;
-                                if (overflow)
-                                    break; // the walk is visiting a large part of the index (a predicate that rejects nearly everything)
-                            }
-                            answered_lazily = settled;
-                            if (!settled) // a predicate that keeps pushing the walk outward: every member, as before
-                                callback_bits(index, filter, filter_state, bits);
-                        } else {
-                            callback_bits(index, filter, filter_state, bits);
-                        }
-                    }
-                    if (answered_lazily) {
-                        // the last provisional run asked nothing: its results are the answer
+                    results_t results(queries_count, count, keys, keys_stride, distances, distances_stride, counts);
+                    const auto launch = [&](const std::uint32_t* bits, const search_extras_t* extras) {
+                        return device_index->search_host(queries, kind, queries_count, queries_stride, count, index.expansion_search,
+                                                         results.keys(), results.distances(), results.found.data(),
+                                                         results.visited.data(), results.computed.data(), search_tuning_t{}, nullptr,
+                                                         bits, extras);
+                    };
+                    predicate_t predicate;
+                    if (const char* e = resolve_predicate(index, device_index, made, filter, filter_state, launch, predicate))
+                        return fail(error, e);
+                    if (predicate.how == predicate_t::answered_k) {
                     } else if (!device_index) { // nothing indexed yet: index.hpp:3034-3037
-                        pad_results(reinterpret_cast<usearch_key_t*>(out_keys), out_distances, queries_count * count);
-                    } else if (const char* e = device_index->search_host(
-                                   queries, kind, queries_count, queries_stride, count, index.expansion_search, out_keys,
-                                   out_distances, found.data(), visited.data(), computed.data(), search_tuning_t{}, nullptr,
-                                   filter && !made && !remembered ? bits.data() : nullptr,
-                                   made || remembered ? &extras : nullptr)) {
+                        results.pad();
+                    } else if (const char* e = launch(predicate.how == predicate_t::host_bits_k ? predicate.bits.data() : nullptr,
+                                                      predicate.how == predicate_t::device_bits_k ? &predicate.extras : nullptr)) {
                         return fail(error, e);
                     }
-                    std::size_t total_visited = 0, total_computed = 0;
-                    for (std::size_t q = 0; q < queries_count; ++q) {
-                        if (!direct) {
-                            if (keys)
-                                std::memcpy(reinterpret_cast<std::uint8_t*>(keys) + q * keys_stride, dense_keys.data() + q * count,
-                                            count * 8);
-                            if (distances)
-                                std::memcpy(reinterpret_cast<std::uint8_t*>(distances) + q * distances_stride,
-                                            dense_distances.data() + q * count, count * 4);
-                        }
-                        if (counts)
-                            counts[q] = (std::size_t)found[q];
-                        total_visited += (std::size_t)visited[q], total_computed += (std::size_t)computed[q];
-                    }
-                    if (visited_total)
-                        *visited_total = total_visited;
-                    if (computed_total)
-                        *computed_total = total_computed;
-                    result = (std::size_t)found[0];
+                    result = results.scatter(visited_total, computed_total);
                     return;
                 }
             }
@@ -1144,10 +956,8 @@ size_t usearch_search(usearch_index_t handle, void const* query, usearch_scalar_
                       usearch_key_t* keys, usearch_distance_t* distances, usearch_error_t* error) {
     index_t& index = *as_index(handle);
     const scalar_kind_t kind = scalar_from_c(query_kind);
-    if (kind == scalar_unknown_k) {
-        fail(error, "Unknown scalar kind!");
-        return 0;
-    }
+    if (kind == scalar_unknown_k)
+        return fail(error, "Unknown scalar kind!"), 0;
     if (index.coalesce && query && keys && distances && count) {
         // callers that arrive while a launch is in flight go out together in the next one (csrc/combiner.hpp)
         combined_call_t call;
@@ -1233,10 +1043,8 @@ size_t usearch_filtered_search(usearch_index_t handle, void const* query, usearc
                                usearch_key_t* keys, usearch_distance_t* distances, usearch_error_t* error) {
     index_t& index = *as_index(handle);
     const scalar_kind_t kind = scalar_from_c(query_kind);
-    if (kind == scalar_unknown_k) {
-        fail(error, "Unknown scalar kind!");
-        return 0;
-    }
+    if (kind == scalar_unknown_k)
+        return fail(error, "Unknown scalar kind!"), 0;
     return search_shared(index, query, kind, 1, bytes_per_vector(kind, index.dimensions), count, keys, count * 8, distances,
                          count * 4, nullptr, nullptr, nullptr, filter, filter_state, error);
 }
@@ -1245,14 +1053,12 @@ size_t usearch_get(usearch_index_t handle, usearch_key_t key, size_t count, void
                    usearch_error_t* error) {
     index_t& index = *as_index(handle);
     const scalar_kind_t kind = scalar_from_c(vector_kind);
-    if (kind == scalar_unknown_k) {
-        fail(error, "Unknown scalar kind!");
-        return 0;
-    }
+    if (kind == scalar_unknown_k)
+        return fail(error, "Unknown scalar kind!"), 0;
     return guarded(error, std::size_t(0), [&] {
         unique_lock_t lock(index.mutex);
         const std::size_t out_bytes = bytes_per_vector(kind, index.dimensions);
-        auto range = index.key_lookup().equal_range(key);
+        auto range = index.members.lookup().equal_range(key);
         std::vector<std::uint32_t> slots;
         for (auto it = range.first; it != range.second; ++it)
             slots.push_back(it->second);
@@ -1260,7 +1066,7 @@ size_t usearch_get(usearch_index_t handle, usearch_key_t key, size_t count, void
         std::size_t exported = 0;
         for (; exported < slots.size() && exported < count; ++exported) {
             std::uint8_t* target = static_cast<std::uint8_t*>(vector) + exported * out_bytes;
-            const std::uint8_t* stored = index.vector_of(slots[exported]);
+            const std::uint8_t* stored = index.members.row(slots[exported]);
             std::memset(target, 0, out_bytes);
             if (!cast_vector(index.scalar, kind, stored, index.dimensions, target))
                 std::memcpy(target, stored, out_bytes);
@@ -1273,54 +1079,36 @@ size_t usearch_remove(usearch_index_t handle, usearch_key_t key, usearch_error_t
     index_t& index = *as_index(handle);
     return guarded(error, std::size_t(0), [&] {
         unique_lock_t lock(index.mutex);
-        if (!index.key_lookup().count(key))
+        if (!index.members.lookup().count(key))
             return std::size_t(0);
         index.materialize();
-        auto range = index.key_lookup().equal_range(key);
-        std::size_t removed = 0;
-        for (auto it = range.first; it != range.second; ++it, ++removed) {
+        return index.members.remove(key, [&](std::uint32_t slot) {
             // a tombstone: the member keeps routing, stops matching (index_dense.hpp:1479-1511)
-            index.keys[it->second] = free_key_k;
-            index.free_slots.push_back(it->second);
             ++index.version;
-            if (index.builder && it->second < index.builder->size()) // in place on the device too: nothing is relinked
-                if (const char* e = index.builder->set_key(it->second, free_key_k))
+            if (index.builder && slot < index.builder->size()) // in place on the device too: nothing is relinked
+                if (const char* e = index.builder->set_key(slot, free_key_k))
                     fail(error, e);
-        }
-        index.lookup.erase(key);
-        return removed;
+        });
     });
 }
 
 size_t usearch_rename(usearch_index_t handle, usearch_key_t from, usearch_key_t to, usearch_error_t* error) {
     index_t& index = *as_index(handle);
-    if (to == free_key_k) {
-        fail(error, "Free key is reserved");
-        return 0;
-    }
+    if (to == free_key_k)
+        return fail(error, "Free key is reserved"), 0;
     return guarded(error, std::size_t(0), [&] {
         unique_lock_t lock(index.mutex);
-        if (!index.key_lookup().count(from))
+        if (!index.members.lookup().count(from))
             return std::size_t(0);
-        if (!index.multi && index.lookup.count(to)) {
-            fail(error, "Renaming impossible, the key is already in use");
-            return std::size_t(0);
-        }
+        if (!index.multi && index.members.lookup().count(to))
+            return fail(error, "Renaming impossible, the key is already in use"), std::size_t(0);
         index.materialize();
-        std::vector<std::uint32_t> slots;
-        auto range = index.key_lookup().equal_range(from);
-        for (auto it = range.first; it != range.second; ++it)
-            slots.push_back(it->second);
-        index.lookup.erase(from);
-        for (std::uint32_t slot : slots) {
-            index.keys[slot] = to;
+        return index.members.rename(from, to, [&](std::uint32_t slot) {
             ++index.version;
-            index.lookup.emplace(to, slot);
             if (index.builder && slot < index.builder->size()) // keys live next to the graph in HBM: renamed in place
                 if (const char* e = index.builder->set_key(slot, to))
                     fail(error, e);
-        }
-        return slots.size();
+        });
     });
 }
 
@@ -1356,11 +1144,7 @@ void usearch_clear(usearch_index_t handle, usearch_error_t* error) {
     guarded(error, [&] {
         unique_lock_t lock(index.mutex);
         index.drop_device();
-        index.drop_image();
-        index.keys.clear(), index.vectors.clear();
-        index.free_slots.clear(), index.free_head = 0, index.recycled.clear();
-        index.staged = false;
-        index.lookup.clear(), index.lookup_valid = false;
+        index.members.clear();
     });
 }
 
@@ -1382,23 +1166,14 @@ static void search_exact_many(usearch_index_t handle, const made_filter_t* made,
             return fail(error, e);
         if (made && (made->index != &index || made->version != version_before || made->version != index.version))
             return fail(error, "The index changed since the filter was made");
-        std::vector<std::uint64_t> dense_keys(queries_count * count), found(queries_count, 0);
-        std::vector<float> dense_distances(queries_count * count);
+        results_t results(queries_count, count, keys, keys_stride, distances, distances_stride, counts);
         if (!device_index) // nothing indexed yet
-            pad_results(reinterpret_cast<usearch_key_t*>(dense_keys.data()), dense_distances.data(), queries_count * count);
-        else if (const char* e = device_index->exact_host(queries, kind, queries_count, queries_stride, count, dense_keys.data(),
-                                                          dense_distances.data(), found.data(), nullptr, false,
+            results.pad();
+        else if (const char* e = device_index->exact_host(queries, kind, queries_count, queries_stride, count, results.keys(),
+                                                          results.distances(), results.found.data(), nullptr, false,
                                                           made && made->bitmap ? made->bitmap->bits() : nullptr))
             return fail(error, e);
-        for (std::size_t q = 0; q < queries_count; ++q) {
-            if (keys)
-                std::memcpy(reinterpret_cast<std::uint8_t*>(keys) + q * keys_stride, dense_keys.data() + q * count, count * 8);
-            if (distances)
-                std::memcpy(reinterpret_cast<std::uint8_t*>(distances) + q * distances_stride, dense_distances.data() + q * count,
-                            count * 4);
-            if (counts)
-                counts[q] = (std::size_t)found[q];
-        }
+        results.scatter();
     });
 }
 
@@ -1479,31 +1254,35 @@ void usearch_gpu_sync(usearch_index_t handle, usearch_error_t* error) {
     });
 }
 
+/// What `usearch_isolate` and `usearch_compact` start with (unique lock): an image with removed members is taken over by a builder
+/// (`adopt_image`: the lists are about to change, the image no longer describes the index), what `usearch_add` deferred is linked, as a
+/// save does. → the builder, or null when there is nothing to drop anything from: nobody removed from the image, or an empty index.
+static const char* builder_with_removals(index_t& index, builder_t** out) {
+    *out = nullptr;
+    if (!index.members.staged) {
+        if (!index.members.has_image() || !index.members.image.count_deleted)
+            return nullptr;
+        if (const char* e = index.adopt_image())
+            return e;
+    }
+    snapshot_t* device_index = nullptr;
+    if (const char* e = index.ready(&device_index))
+        return e;
+    *out = index.builder.get();
+    return nullptr;
+}
+
 size_t usearch_isolate(usearch_index_t handle, usearch_error_t* error) {
     index_t& index = *as_index(handle);
     return guarded(error, std::size_t(0), [&] {
         unique_lock_t lock(index.mutex);
-        if (!index.staged) {
-            if (!index.has_image || !index.image.count_deleted)
-                return std::size_t(0); // nobody was removed: no list names a removed member
-            if (const char* e = index.adopt_image()) { // the lists change: the image no longer describes the index
-                fail(error, e);
-                return std::size_t(0);
-            }
-        }
-        snapshot_t* device_index = nullptr;
-        if (const char* e = index.ready(&device_index)) { // links what `usearch_add` deferred, as a save does
-            fail(error, e);
-            return std::size_t(0);
-        }
-        if (!index.builder)
-            return std::size_t(0);
+        builder_t* builder = nullptr;
         compact_stats_t stats;
-        if (const char* e = index.builder->isolate(&stats)) {
-            fail(error, e);
-            return std::size_t(0);
-        }
-        return (std::size_t)stats.pruned_edges;
+        const char* e = builder_with_removals(index, &builder);
+        if (!e && builder)
+            e = builder->isolate(&stats);
+        fail(error, e);
+        return e || !builder ? std::size_t(0) : (std::size_t)stats.pruned_edges;
     });
 }
 
@@ -1511,46 +1290,22 @@ size_t usearch_compact(usearch_index_t handle, usearch_error_t* error) {
     index_t& index = *as_index(handle);
     return guarded(error, std::size_t(0), [&] {
         unique_lock_t lock(index.mutex);
-        if (!index.staged) {
-            if (!index.has_image || !index.image.count_deleted)
-                return std::size_t(0);
-            if (const char* e = index.adopt_image()) { // from here on the index is served and saved from its device state
-                fail(error, e);
-                return std::size_t(0);
-            }
-        }
-        snapshot_t* device_index = nullptr;
-        if (const char* e = index.ready(&device_index)) {
-            fail(error, e);
-            return std::size_t(0);
-        }
-        if (!index.builder)
-            return std::size_t(0);
-        std::vector<std::uint32_t> slot_map(index.keys.size());
+        builder_t* builder = nullptr;
         compact_stats_t stats;
-        if (const char* e = index.builder->compact(compact_config_t{}, slot_map.data(), &stats)) {
-            fail(error, e);
-            return std::size_t(0);
+        std::vector<std::uint32_t> slot_map;
+        const char* e = builder_with_removals(index, &builder);
+        if (!e && builder) {
+            slot_map.resize(index.members.keys.size());
+            e = builder->compact(compact_config_t{}, slot_map.data(), &stats);
         }
-        if (!stats.removed_members)
+        fail(error, e);
+        if (e || !builder || !stats.removed_members)
             return std::size_t(0);
-        // the staging arrays follow the same map: new slot ≤ old slot, so everything moves down in place
-        const std::size_t bytes = index.bpv();
-        for (std::size_t slot = 0; slot < slot_map.size(); ++slot) {
-            const std::uint32_t to = slot_map[slot];
-            if (to == none_slot_k || to == slot)
-                continue;
-            index.keys[to] = index.keys[slot];
-            std::memmove(index.vectors.data() + (std::size_t)to * bytes, index.vectors.data() + slot * bytes, bytes);
-        }
-        index.keys.resize((std::size_t)stats.survivors);
-        index.vectors.resize((std::size_t)stats.survivors * bytes);
-        index.free_slots.clear(), index.free_head = 0, index.recycled.clear();
-        index.lookup_valid = false;
+        index.members.compact(slot_map.data(), (std::size_t)stats.survivors); // the staging arrays follow the same map
         ++index.version; // a `usearch_filter_t` made before describes the old numbering
         index.memos.clear();
         if (!stats.survivors)
-            delete index.builder, index.builder = nullptr; // staged and empty: the next add builds anew
+            index.builder.reset(); // staged and empty: the next add builds anew
         return (std::size_t)stats.removed_members;
     });
 }
@@ -1571,7 +1326,7 @@ static void clustering_shared(index_t& index, const void* queries, scalar_kind_t
             return fail(error, "Clustering by member keys is not available for a multi-index");
         if (members && member_keys) {
             slots.resize(count);
-            const auto& lookup = index.key_lookup();
+            const auto& lookup = index.members.lookup();
             for (std::size_t q = 0; q < count; ++q) {
                 const auto found = lookup.find(member_keys[q]);
                 if (found == lookup.end())
@@ -1626,10 +1381,8 @@ void usearch_gpu_release(usearch_index_t handle, usearch_error_t*) {
 static size_t dropin_join(usearch_index_t a_handle, usearch_index_t b_handle, size_t max_proposals, size_t expansion, bool exact,
                           size_t threads, usearch_key_t* a_keys, usearch_key_t* b_keys, size_t capacity, size_t* stats,
                           usearch_error_t* error) {
-    if (!a_handle || !b_handle) {
-        fail(error, "Join needs two indexes");
-        return 0;
-    }
+    if (!a_handle || !b_handle)
+        return fail(error, "Join needs two indexes"), 0;
     if (a_handle == b_handle) {
         fail(error, "Can't join with itself, consider copying"); // index.hpp:4388
         return 0;
