@@ -358,6 +358,9 @@ USEARCH_AMD_EXPORT size_t usearch_amd_snapshot_live_keys(usearch_amd_snapshot_t 
  *  float tolerance of `usearch_amd_exact_search_many`, which remains the bit-exact path), cos / ip over f32 (l2sq over f32 is refused; `v_mfma_f32_32x32x2_f32`: f32
  *  products and sums in the matrix unit's order — within a derived bound of the f64 distance, not bit-equal to the bit-exact path
  *  and not promised within 1e-5 of it) and over i8 (bit-identical to it, ties included); `wanted` ≤ 64. Other pairs: an error.
+ *  Bit vectors have a tile of their own behind the same entry (usearch_amd/csrc/exact_bits.hip, no matrix unit: popcount(a ∧ b) on the
+ *  vector ALU, rows read once per 256 queries): hamming, tanimoto, jaccard and sorensen over b1, bit-identical to the bit-exact path,
+ *  ties and NaN (two empty sets) included.
  */
 USEARCH_AMD_EXPORT void usearch_amd_exact_search_many_tiled(usearch_amd_snapshot_t snapshot, void const* queries,
                                                             int query_kind, size_t queries_count, size_t queries_stride,
@@ -368,7 +371,7 @@ USEARCH_AMD_EXPORT void usearch_amd_exact_search_many_tiled(usearch_amd_snapshot
 /**
  *  Either exact search over DEVICE buffers (queries in the storage scalar kind, `queries_stride` bytes apart; keys, distances and
  *  counts dense `[queries_count][wanted]` / `[queries_count]` in HBM), enqueued on `stream` (NULL: a stream of the snapshot);
- *  returns when the results are complete. `tiled != 0` selects the matrix-unit kernel. `kernel_ms` (may be NULL): HIP-event
+ *  returns when the results are complete. `tiled != 0` selects the matrix-unit kernel (b1: the bit tile). `kernel_ms` (may be NULL): HIP-event
  *  time of the kernels. What `bench.py --exact` times.
  */
 USEARCH_AMD_EXPORT void usearch_amd_exact_search_many_device(usearch_amd_snapshot_t snapshot, void const* queries,
@@ -392,7 +395,8 @@ USEARCH_AMD_EXPORT void usearch_amd_exact_search_dataset(void const* dataset, si
 
 /**
  *  The same call, same arguments, as a TILED MATRIX PRODUCT over the uploaded rows (usearch_amd/csrc/exact_tiled.hip) for every
- *  pair that has a tiled kernel — cos / ip / l2sq over f16, bf16 and i8, cos / ip over f32, `wanted` ≤ 64; any other pair is refused ("No tiled
+ *  pair that has a tiled kernel — cos / ip / l2sq over f16, bf16 and i8, cos / ip over f32, and hamming / tanimoto / jaccard / sorensen
+ *  over b1 (the bit tile, exact_bits.hip: the same bits as the untiled call), `wanted` ≤ 64; any other pair is refused ("No tiled
  *  exact-search kernel for this metric / scalar kind / result count"), never sent down the other kernel quietly. Float kinds:
  *  every distance lies within a derived bound of the f64 distance of the row it names (f32: f32 arithmetic in the matrix unit's
  *  summation order — NOT bit-equal to `usearch_amd_exact_search_dataset`, which stays the bit-exact path, and not promised within

@@ -121,6 +121,17 @@ __device__ __forceinline__ float closing_distance(sum_at sum, std::uint32_t a2_b
         } else { // metric_l2sq_i8_t 1613-1630
             return (float)(a2 + b2 - 2 * ab);
         }
+    } else if constexpr (scalar_ak == scalar_b1x8_k) {
+        // `sum` is the `ix` of kernels.hpp's `partial_t` — |a⊕b| for hamming, |a∧b| for the other two — and the two stored values
+        // are |a| and |b|, from which its `iy` follows in integers: |a∨b| = |a| + |b| − |a∧b| (tanimoto), |a| + |b| (sorensen).
+        // One IEEE division of exact integers; 0 / 0 (both vectors empty) is the NaN the reference returns, and stays one.
+        const int ab = sum, a2 = (int)a2_bits, b2 = (int)b2_bits;
+        if constexpr (metric_ak == metric_hamming_k) // metric_hamming_gt<b1x8_t> 1392-1414
+            return (float)ab;
+        else if constexpr (metric_ak == metric_sorensen_k) // 1451-1476
+            return 1 - 2 * (float)ab / (float)(a2 + b2);
+        else // tanimoto, jaccard 1420-1445
+            return 1 - (float)ab / (float)(a2 + b2 - ab);
     } else {
         const float ab = sum, a2 = __builtin_bit_cast(float, a2_bits), b2 = __builtin_bit_cast(float, b2_bits);
         if constexpr (metric_ak == metric_cos_k) { // metric_cos_gt, index_plugins.hpp:1334-1359

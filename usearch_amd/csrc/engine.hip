@@ -1451,12 +1451,13 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
     view.bytes_per_vector = (std::uint32_t)bpv;
     view.dimensions = (std::uint32_t)dimensions;
     // i8: the matrix-unit kernel returns the very same bits (exact integer sums, same closing arithmetic, same tie order);
-    // the float kinds only reach it when asked (`tiled`: a derived bound instead of bit equality)
+    // the float kinds only reach it when asked (`tiled`: a derived bound instead of bit equality), and so does b1, whose bit tile
+    // (exact_bits.hip) returns the wave kernel's bits too: routing it unasked waits for its speed to be measured
     const char* error = nullptr;
     if (tiled || (scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
                   !env_size("USEARCH_AMD_NO_TILED_EXACT", 0)))
-        error = exact_search_tiled_device(metric, scalar, view, d_queries, queries_count, bpv, wanted, false, d_keys, d_distances,
-                                          d_counts, nullptr, nullptr);
+        error = exact_search_tiled_device(kernel_metric(metric), scalar, view, d_queries, queries_count, bpv, wanted, false, d_keys,
+                                          d_distances, d_counts, nullptr, nullptr);
     else
         error = exact_search_device(metric, scalar, lanes, view, d_queries, queries_count, bpv, wanted, false, d_keys, d_distances,
                                     d_counts, nullptr, nullptr);

@@ -543,18 +543,27 @@ const char* exact_search_device(metric_kind_t metric, scalar_kind_t scalar, std:
 
 /// Is there a tiled (matrix-unit) exact-search kernel for this pair and result count? (exact_tiled.hip: cos / ip / l2sq over f16
 /// and bf16 — float tolerance —, cos / ip over f32 — a derived bound, not bit equality; l2sq over f32 stays refused — and over i8 — bit-identical to the wave-per-query
-/// kernel. The table itself: `exact_tiled_pair` of exact_plan.hpp.)
+/// kernel. The table itself: `exact_tiled_pair` of exact_plan.hpp.) Or a bit tile (exact_bits.hip: hamming, tanimoto / jaccard and
+/// sorensen over b1, no matrix unit, bit-identical to the wave-per-query kernel, NaN included; its table: `exact_bits_pair`)? Either
+/// one makes the tiled routes available: `exact_search_tiled_device` runs whichever the pair has.
 bool exact_tiled_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted);
 
-/// Many-to-many exact search as a tiled matrix product (index_plugins.hpp:2071-2164): rows are read once per 64 queries. Same
-/// contract as `exact_search_device`.
+/// Many-to-many exact search as a tiled matrix product (index_plugins.hpp:2071-2164): rows are read once per 64 queries — or, for the
+/// b1 pairs of `exact_bits_pair`, the bit tile below. Same contract as `exact_search_device`.
 const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar, const snapshot_view_t& view,
                                       const void* queries, std::size_t count, std::size_t stride_bytes, std::size_t wanted,
                                       bool map_keys, std::uint64_t* keys, float* distances, std::uint64_t* counts,
                                       hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits = nullptr);
 
+/// The bit tile (exact_bits.hip): rows are read once per 256 queries, popcount(a ∧ b) on the vector ALU. `metric`: hamming, tanimoto,
+/// jaccard or sorensen; the view's rows are b1. Same contract and the same refusals as `exact_search_tiled_device`, which is its
+/// one caller.
+const char* exact_search_bits_device(metric_kind_t metric, const snapshot_view_t& view, const void* queries, std::size_t count,
+                                     std::size_t stride_bytes, std::size_t wanted, bool map_keys, std::uint64_t* keys, float* distances,
+                                     std::uint64_t* counts, hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits = nullptr);
+
 /// Host-buffer exact search of a raw dataset — `usearch_exact_search` (c/usearch.h:467-474): keys are dataset offsets.
-/// `tiled`: the matrix-unit kernel over the uploaded rows for any pair that has one (`exact_tiled_available`; refused otherwise)
+/// `tiled`: the matrix-unit kernel (or the bit tile) over the uploaded rows for any pair that has one (`exact_tiled_available`; refused otherwise)
 /// instead of the bit-exact wave-per-query one, which stays what the float kinds get unasked.
 const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar, std::size_t dimensions,
                                       const void* dataset, std::size_t dataset_count, std::size_t dataset_stride,

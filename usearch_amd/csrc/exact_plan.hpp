@@ -111,4 +111,63 @@ inline const char* plan_exact(std::uint64_t rows, std::uint64_t bytes_per_vector
     return nullptr;
 }
 
+// ---- the bit tile (exact_bits.hip): hamming, tanimoto / jaccard and sorensen over b1, popcount(a ∧ b) on the vector ALU
+
+constexpr int bits_wave_queries_k = 64; ///< queries a wave owns: their lists are its own, no wave ever inserts into another's
+constexpr int bits_waves_k = 4;         ///< waves per workgroup: 256 queries meet a partition's rows together (one pass through L1 / L2)
+constexpr int bits_rows_k = 64;         ///< rows per step of a wave: lane ↔ row
+constexpr int bits_block_k = 16;        ///< queries per block of accumulators: what a lane holds while a long row passes piece by piece
+
+/// Which (metric, scalar kind) pairs the bit tile takes, and for how many results per query: hamming, tanimoto, jaccard (which
+/// `kernel_metric` maps to tanimoto) and sorensen over b1, 1 … `max_wanted_k` results. NOT part of `exact_tiled_pair`, which stays
+/// the table of the matrix-unit pairs. tests/test_exact_bits_plan.py pins it through `usearch_amd_test_exact_bits_pair`.
+inline bool exact_bits_pair(metric_kind_t metric, scalar_kind_t scalar, std::uint64_t wanted) {
+    if (!wanted || wanted > (std::uint64_t)max_wanted_k || scalar != scalar_b1x8_k)
+        return false;
+    return metric == metric_hamming_k || metric == metric_tanimoto_k || metric == metric_jaccard_k || metric == metric_sorensen_k;
+}
+
+/// What `plan_exact_bits` settles: a grid of (query_tiles, partitions) workgroups of `bits_waves_k` waves, workgroup (x, y) takes
+/// queries [256x, 256x + 256) and rows [y · rows_per_partition, (y + 1) · rows_per_partition).
+struct exact_bits_plan_t {
+    std::uint64_t query_tiles = 0;
+    std::uint64_t partitions = 0;
+    std::uint64_t rows_per_partition = 0;
+    std::uint64_t padded_queries = 0;     ///< rows of the padded copy of the batch: whole waves of 64 queries
+    std::uint64_t padded_query_bytes = 0; ///< … and its pitch: whole 16-byte pieces, as the stored rows have them
+    std::uint64_t lds_bytes = 0;          ///< the workgroup's lists: [4 waves][64 queries][wanted] cells of 8 bytes
+};
+
+/// One variant, so nothing to force and no environment to read. → nullptr, or why the call is refused.
+inline const char* plan_exact_bits(std::uint64_t rows, std::uint64_t bytes_per_vector, std::uint64_t row_stride, std::uint64_t count,
+                                   std::uint64_t wanted, exact_bits_plan_t& plan) {
+    plan = exact_bits_plan_t{};
+    if (!wanted || wanted > (std::uint64_t)max_wanted_k)
+        return "No tiled exact-search kernel for this metric / scalar kind / result count";
+    if (!count)
+        return nullptr;
+    if (!rows)
+        return "Nothing to scan";
+    const std::uint64_t pieces = (bytes_per_vector + 15) / 16;
+    if (!bytes_per_vector || row_stride < pieces * 16 || pieces >= (1ull << 27))
+        return "Row pitch is smaller than the row's 16-byte pieces";
+    constexpr std::uint64_t tile = (std::uint64_t)bits_wave_queries_k * bits_waves_k;
+    plan.query_tiles = (count + tile - 1) / tile;
+    if (plan.query_tiles >= (1ull << 31))
+        return "Batch is too large";
+    plan.padded_queries = (count + bits_wave_queries_k - 1) / bits_wave_queries_k * bits_wave_queries_k;
+    plan.padded_query_bytes = pieces * 16;
+    plan.lds_bytes = tile * wanted * 8;
+    // enough workgroups to fill the chip several times over (the tail of a round is a smaller share of the run, and a compute unit
+    // holds several of them); few enough lists per query for one merge wave; a partition is at least four steps of 64 rows
+    std::uint64_t partitions = std::max<std::uint64_t>(1, (2048 + plan.query_tiles - 1) / plan.query_tiles);
+    partitions = std::min<std::uint64_t>(partitions, std::max<std::uint64_t>(1, 8192 / wanted));
+    partitions = std::min<std::uint64_t>(partitions, std::max<std::uint64_t>(1, rows / (4 * bits_rows_k)));
+    partitions = std::min<std::uint64_t>(partitions, 65535);
+    plan.rows_per_partition = (rows + partitions - 1) / partitions;
+    plan.rows_per_partition = (plan.rows_per_partition + bits_rows_k - 1) / bits_rows_k * bits_rows_k;
+    plan.partitions = (rows + plan.rows_per_partition - 1) / plan.rows_per_partition;
+    return nullptr;
+}
+
 } // namespace usearch_amd

@@ -1103,7 +1103,7 @@ constexpr std::uint32_t norms_blocks_k = 1u << 20; ///< the grid of the Σx² la
 } // namespace
 
 bool exact_tiled_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted) {
-    return exact_tiled_pair(metric, scalar, wanted); // the table: exact_plan.hpp
+    return exact_tiled_pair(metric, scalar, wanted) || exact_bits_pair(metric, scalar, wanted); // the tables: exact_plan.hpp
 }
 
 const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar, const snapshot_view_t& view,
@@ -1112,7 +1112,10 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
                                       hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits) {
     if (kernel_ms)
         *kernel_ms = 0.f;
-    if (!exact_tiled_available(metric, scalar, wanted))
+    if (exact_bits_pair(metric, scalar, wanted)) // b1: the bit tile (exact_bits.hip), same contract
+        return exact_search_bits_device(metric, view, queries, count, stride_bytes, wanted, map_keys, keys, distances, counts, stream,
+                                        kernel_ms, allow_bits);
+    if (!exact_tiled_pair(metric, scalar, wanted))
         return "No tiled exact-search kernel for this metric / scalar kind / result count";
     if (!count)
         return nullptr;

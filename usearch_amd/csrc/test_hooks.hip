@@ -616,6 +616,22 @@ extern "C" __attribute__((visibility("default"))) int usearch_amd_test_exact_til
     return usearch_amd::exact_tiled_pair((usearch_amd::metric_kind_t)metric, (usearch_amd::scalar_kind_t)scalar, wanted) ? 1 : 0;
 }
 
+// ---- the same two for the bit tile (exact_bits.hip): its table (`exact_bits_pair`) and its planner (`plan_exact_bits`, one variant:
+//      nothing to force, no environment), for tests/test_exact_bits_plan.py and the route checks of tests/test_gpu_exact_bits.py.
+extern "C" __attribute__((visibility("default"))) int usearch_amd_test_exact_bits_pair(int metric, int scalar, uint64_t wanted) {
+    return usearch_amd::exact_bits_pair((usearch_amd::metric_kind_t)metric, (usearch_amd::scalar_kind_t)scalar, wanted) ? 1 : 0;
+}
+extern "C" __attribute__((visibility("default"))) int usearch_amd_test_plan_exact_bits(uint64_t rows, uint64_t bytes_per_vector,
+                                                                                       uint64_t row_stride, uint64_t count, uint64_t wanted,
+                                                                                       usearch_amd::exact_bits_plan_t* plan,
+                                                                                       usearch_amd_error_t* error) {
+    if (const char* e = usearch_amd::plan_exact_bits(rows, bytes_per_vector, row_stride, count, wanted, *plan)) {
+        fail(error, e);
+        return 0;
+    }
+    return 1;
+}
+
 // ---- the sketch on the device and its twins piece by piece, for tests/test_gpu_sketch_records.py, tests/test_gpu_sketch_counts.py and
 //      tests/test_sketch_truth.py. `scalar_kind`: scalar_kind_t of common.hpp (f32, f16, bf16); `directions`: [dimensions][64] f32.
 namespace usearch_amd {

@@ -741,6 +741,7 @@ class Index:
         if exact:  # brute force over every stored vector (Index.search(..., exact=True), index.py:700-748)
             kernel_ms = C.c_float()
             # exact="tiled": the matrix-unit kernel (f16 / bf16 within float tolerance; f32 within a derived bound; i8 bit-identical)
+            # or, for b1, the bit tile (hamming / tanimoto / jaccard / sorensen: bit-identical, NaN included)
             entry = (library().usearch_amd_exact_search_many_tiled if exact == "tiled"
                      else library().usearch_amd_exact_search_many)
             entry(self._handle, _pointer(vectors), SCALAR_KINDS[dtype], q,
@@ -800,7 +801,7 @@ class Index:
     def exact_search_device(self, queries_ptr: int, queries_count: int, queries_stride: int, count: int, keys_ptr: int,
                             distances_ptr: int, counts_ptr: int, stream: int = 0, tiled: bool = True) -> float:
         """Exact search of an HBM-resident batch into HBM-resident results (`search(…, exact = true)` of the class for a batch);
-        returns the kernels' HIP-event time in ms. `tiled`: the matrix-unit kernel (exact_tiled.hip)."""
+        returns the kernels' HIP-event time in ms. `tiled`: the matrix-unit kernel (exact_tiled.hip), for b1 the bit tile (exact_bits.hip)."""
         kernel_ms = C.c_float(0)
         err = C.c_char_p()
         library().usearch_amd_exact_search_many_device(self._handle, C.c_void_p(queries_ptr), queries_count, queries_stride,
@@ -1094,7 +1095,8 @@ def exact_search(dataset: np.ndarray, queries: np.ndarray, count: int, metric: s
                  dtype: Optional[str] = None, tiled: bool = False):
     """`usearch.index.search(dataset, queries, count, exact=True)` (index.py:1608-1700) → (keys = row offsets [Q, k],
     distances [Q, k]); both matrices in the same scalar kind, rows may be strided. `tiled`: the matrix-unit kernel
-    (csrc/exact_tiled.hip) over the uploaded rows — cos / ip / l2sq over f16, bf16 and i8, cos / ip over f32, count ≤ 64, any
+    (csrc/exact_tiled.hip) over the uploaded rows — cos / ip / l2sq over f16, bf16 and i8, cos / ip over f32 — or the bit tile
+    (csrc/exact_bits.hip: hamming / tanimoto / jaccard / sorensen over b1, the wave kernel's bits), count ≤ 64, any
     other pair is refused; float distances then lie within a derived bound of the f64 distance instead of being the wave kernel's bits (f32:
     not promised within 1e-5 of them). The default stays the bit-exact wave-per-query kernel."""
     dataset, queries = np.asarray(dataset), np.asarray(queries)
@@ -1278,6 +1280,10 @@ def test_hooks() -> C.CDLL:
                                                             C.POINTER(ExactPlan), C.POINTER(C.c_char_p)]
         _test_hooks.usearch_amd_test_exact_tiled_pair.restype = C.c_int
         _test_hooks.usearch_amd_test_exact_tiled_pair.argtypes = [C.c_int, C.c_int, C.c_uint64]
+        _test_hooks.usearch_amd_test_exact_bits_pair.restype = C.c_int
+        _test_hooks.usearch_amd_test_exact_bits_pair.argtypes = [C.c_int, C.c_int, C.c_uint64]
+        _test_hooks.usearch_amd_test_plan_exact_bits.restype = C.c_int
+        _test_hooks.usearch_amd_test_plan_exact_bits.argtypes = [C.c_uint64] * 5 + [C.c_void_p, C.POINTER(C.c_char_p)]
         _test_hooks.usearch_amd_test_kmeans_quantize.restype = None
         _test_hooks.usearch_amd_test_kmeans_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
@@ -1356,6 +1362,29 @@ def test_exact_tiled_pair(metric: str, dtype: str, wanted: int) -> bool:
                        "jaccard": "j", "tanimoto": "t", "sorensen": "s"}[metric])  # metric_kind_t and scalar_kind_t of csrc/common.hpp
     scalar_kind = {"b1": 1, "bf16": 4, "f64": 10, "f32": 11, "f16": 12, "i8": 23}[dtype]
     return bool(test_hooks().usearch_amd_test_exact_tiled_pair(metric_kind, scalar_kind, wanted))
+
+
+# the bit tile's plan (csrc/exact_plan.hpp: exact_bits_plan_t)
+ExactBitsPlan = _struct("ExactBitsPlan", (C.c_uint64, "query_tiles partitions rows_per_partition padded_queries padded_query_bytes lds_bytes"))
+
+
+def test_exact_bits_pair(metric: str, dtype: str, wanted: int) -> bool:
+    """Does the bit tile (csrc/exact_bits.hip) take `metric` over `dtype` rows for `wanted` results per query? The table of
+    csrc/exact_plan.hpp (`exact_bits_pair`): hamming, tanimoto, jaccard and sorensen over b1, 1 … 64 results; no GPU involved."""
+    metric_kind = ord({"ip": "i", "cos": "c", "l2sq": "e", "hamming": "b", "pearson": "p", "haversine": "h", "divergence": "d",
+                       "jaccard": "j", "tanimoto": "t", "sorensen": "s"}[metric])  # metric_kind_t and scalar_kind_t of csrc/common.hpp
+    scalar_kind = {"b1": 1, "bf16": 4, "f64": 10, "f32": 11, "f16": 12, "i8": 23}[dtype]
+    return bool(test_hooks().usearch_amd_test_exact_bits_pair(metric_kind, scalar_kind, wanted))
+
+
+def test_plan_exact_bits(rows: int, bytes_per_vector: int, row_stride: int, count: int, wanted: int) -> dict:
+    """The bit tile's planner (csrc/exact_plan.hpp, `plan_exact_bits`) on plain values, no GPU involved: the grid of (query tiles of 256,
+    row partitions) a batch of `count` queries for `wanted` results over `rows` rows takes. One variant: nothing to force, and the
+    environment is not read. → the fields of `ExactBitsPlan` as a dict; a refusal raises."""
+    plan, err = ExactBitsPlan(), C.c_char_p()
+    test_hooks().usearch_amd_test_plan_exact_bits(rows, bytes_per_vector, row_stride, count, wanted, C.byref(plan), C.byref(err))
+    _raise(err, "usearch_amd_test_plan_exact_bits")
+    return plan.as_dict()
 
 
 def test_kmeans_quantize(X: np.ndarray, from_dtype: str, to_dtype: str, device: int = 0) -> np.ndarray:
