@@ -1031,11 +1031,16 @@ const char* snapshot_t::search_finish(search_call_t& call, search_stats_t* stats
                      call.plan.ef, first_grid, 100 * ticks[0] / total, 100 * ticks[1] / total, 100 * ticks[2] / total,
                      100 * ticks[3] / total, 100 * ticks[4] / total, 100 * ticks[8] / total, 100 * ticks[9] / total, ticks[10],
                      100 * ticks[5] / total, total, ticks[6], ticks[7]);
-        if (!ticks[15] && ticks[12]) // one wave per query with the sketch on: phase 3 split, per hop that took the sketch path
+        const bool team = call.params.team != 0; // (slots 11 … 15 are the helpers' in a team, the one wave's own otherwise)
+        if (!team)
+            std::fprintf(stderr, "[usearch_amd] lists not ready ahead: %.2f%% of all ticks in pop+list on those hops (%llu ticks); hops with a "
+                                 "second probe round %llu\n",
+                         100 * ticks[14] / total, ticks[14], ticks[15]);
+        if (!team && ticks[12]) // one wave per query with the sketch on: phase 3 split, per hop that took the sketch path
             std::fprintf(stderr, "[usearch_amd] sketch hops %llu: records+bounds %.1f%%, rest of phase 3 (rows; hops before `top` is full included) %.1f%% (of all ticks), hops with more than 8 "
                                  "survivors %llu\n",
                          ticks[12], 100 * ticks[11] / total, 100 * ((double)ticks[3] - (double)ticks[11]) / total, ticks[13]);
-        if (ticks[15])
+        if (team && ticks[15])
             std::fprintf(stderr, "[usearch_amd] a team's helpers: %llu hops, ticks measuring per hop %.0f %.0f %.0f %.0f\n", ticks[15],
                          (double)ticks[11] / (double)ticks[15], (double)ticks[12] / (double)ticks[15],
                          (double)ticks[13] / (double)ticks[15], (double)ticks[14] / (double)ticks[15]);

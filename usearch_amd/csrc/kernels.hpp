@@ -1268,8 +1268,9 @@ struct phase_clock_t {
     unsigned long long* out;   // `args.phases`; null = the clock stands still
     std::uint32_t row_groups;  // rows one round of one row per lane group holds (a sketch hop with more survivors is "wide")
     std::uint64_t mark = 0, ticks[6] = {0, 0, 0, 0, 0, 0};
-    std::uint32_t pushes = 0, ready = 0, rechecks = 0, sketch_hops = 0, wide_hops = 0;
-    std::uint64_t push_ticks = 0, insert_ticks = 0, bound_ticks = 0;
+    std::uint32_t pushes = 0, ready = 0, rechecks = 0, sketch_hops = 0, wide_hops = 0, second_rounds = 0;
+    std::uint64_t push_ticks = 0, insert_ticks = 0, bound_ticks = 0, miss_ticks = 0;
+    bool missed = false; // this hop's list had not been requested ahead, and its phase 1 has not been booked yet
     std::uint64_t push_t0 = 0, push_t1 = 0;
     std::uint64_t helper_busy = 0, helper_idle = 0, helper_hops = 0;
     UA_DEVICE phase_clock_t(const search_args_t& args, std::uint32_t row_groups) : out(args.phases), row_groups(row_groups) {
@@ -1279,6 +1280,8 @@ struct phase_clock_t {
         if (out) {
             const std::uint64_t now = __builtin_amdgcn_s_memtime();
             ticks[phase] += now - mark;
+            if (phase == 1 && missed)
+                miss_ticks += now - mark, missed = false;
             mark = now;
         }
     }
@@ -1291,12 +1294,15 @@ struct phase_clock_t {
             wide_hops += kept > row_groups ? 1u : 0u;
         }
     }
-    UA_DEVICE void list_ready(bool was_ready) { ready += was_ready ? 1u : 0u; } ///< a hop whose list had been requested ahead
+    /// A hop whose list had been requested ahead — or not: then its phase 1 (pop + list) is also booked as the price of the miss.
+    UA_DEVICE void list_ready(bool was_ready) { ready += was_ready ? 1u : 0u, missed = !was_ready; }
+    UA_DEVICE void second_round(bool any_lane) { second_rounds += any_lane ? 1u : 0u; } ///< a hop whose probe went past the home cells
     UA_DEVICE void recheck() { ++rechecks; }                                    ///< a candidate looked at again inside the commit
     UA_DEVICE void push_begin() { ++pushes, push_t0 = __builtin_amdgcn_s_memtime(); }
     UA_DEVICE void push_middle() { push_t1 = __builtin_amdgcn_s_memtime(); }
     UA_DEVICE void push_end() { push_ticks += push_t1 - push_t0, insert_ticks += __builtin_amdgcn_s_memtime() - push_t1; }
-    /// `one_wave`: [11 … 15] belong to a team's helpers otherwise.
+    /// `one_wave`: [11 … 15] belong to a team's helpers otherwise. [14] phase 1 of the hops whose list was not ready, [15] hops with a
+    /// second probe round.
     UA_DEVICE void flush(const search_args_t& args, std::uint32_t lane, bool one_wave) {
         if (!args.phases || lane != 0)
             return;
@@ -1312,6 +1318,8 @@ struct phase_clock_t {
             atomicAdd(args.phases + 11, (unsigned long long)bound_ticks);
             atomicAdd(args.phases + 12, (unsigned long long)sketch_hops);
             atomicAdd(args.phases + 13, (unsigned long long)wide_hops);
+            atomicAdd(args.phases + 14, (unsigned long long)miss_ticks);
+            atomicAdd(args.phases + 15, (unsigned long long)second_rounds);
         }
     }
     /// A team's helper: what it spent waiting for the leader to publish a hop, and measuring its share between the hop's two barriers.
@@ -1342,6 +1350,7 @@ struct phase_clock_t {
     UA_DEVICE void tick(int) {}
     UA_DEVICE void tick_bounds(std::uint32_t) {}
     UA_DEVICE void list_ready(bool) {}
+    UA_DEVICE void second_round(bool) {}
     UA_DEVICE void recheck() {}
     UA_DEVICE void push_begin() {}
     UA_DEVICE void push_middle() {}
@@ -1675,6 +1684,9 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                           : ix.nbr0 + (std::uint64_t)slot * ix.m0;
     };
     std::uint32_t ahead_slot = none_slot_k, ahead_cell = none_slot_k; // list tile requested ahead of its hop
+    // The in-`top` builds that carry the sketch compute its bounds while the probe's second round is in flight (see the probe); the
+    // heap-frontier builds keep the order they had.
+    constexpr bool overlap_ak = in_top_ak;
     // rows stored next to the lists (`nbr0_rows`): one-chunk rows only, lists of one tile, level 0
     constexpr bool inline_ak = lanes_ak == 1 && !global_ak;
     const bool inline_rows = plain_ak ? inline_ak : inline_ak && ix.nbr0_rows != nullptr && !beam_level && cells <= 64 && ix.chunks == 1;
@@ -1952,6 +1964,10 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 }
                 // The slab is probed by compare-and-swap, one per probe round, executed at the memory side (`probe_first`, `probe_rest`).
                 // A load first with the swap only to claim, and no atomic at all, both lost to it: DESIGN.md §3.2.
+                std::uint32_t h_rest = h; // where `probe_rest` takes over: the home cell, or one further on (the sketch's peeled round)
+#ifdef USEARCH_AMD_PHASES
+                bool round_counted = false;
+#endif
                 bool shadow_done = false;
                 auto shadow_work = [&]() {
                     if (shadow_done)
@@ -2012,6 +2028,37 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                             const std::uint32_t slot = (std::uint32_t)__builtin_amdgcn_ds_bpermute(from + r * 32, (int)present_slot);
                             early_record[r] = *reinterpret_cast<const uint4*>(ix.sketch + ((std::uint64_t)slot * sketch_record_bytes_k + (lane_now & 7u) * 16));
                         }
+                        // ---- the bounds in the shadow of the probe's SECOND round. A lane that met a taken home cell goes on to the next
+                        //      cell, one more trip to the memory side with the whole wave waiting. The bounds need the records and the query
+                        //      and nothing of the probe, so the first round of `probe_rest` is peeled off: the lanes that must go on issue
+                        //      their second compare-and-swap, every lane group then turns its four records into bounds — for every list
+                        //      position, fresh or not: an absent cell read slot 0's record and is never fresh — and only then is the second
+                        //      answer waited for, in `probe_rest`. Right here, in the block that requested the records, and not behind it
+                        //      where `probe_rest` stands: returning atomics and loads come back in issue order, and only on this path does
+                        //      the compiler know that four loads are younger than the first swap — it waits for the swap with `vmcnt(4)`
+                        //      here, with `vmcnt(0)`, for the records as well, behind the join with the other path. The four records are
+                        //      then waited for with `vmcnt(3)` … `vmcnt(0)`, not 4 … 1: the second swap sits behind a branch the whole wave
+                        //      may skip, so the compiler cannot count on it, and the fourth round of bounds waits for that swap too. Three
+                        //      rounds of four run in its shadow. (Nothing else stands between the two places in these builds: the member
+                        //      was popped at the hop's start.)
+                        if constexpr (overlap_ak) {
+#ifdef USEARCH_AMD_PHASES
+                            clock.second_round(ballot(asks && old != none_slot_k && old != neighbor) != 0), round_counted = true;
+#endif
+                            if (old != none_slot_k && old != neighbor) {
+                                h_rest = (h_rest + 1) & visits_mask;
+                                old = atomicCAS(visits + h_rest, none_slot_k, neighbor);
+                            }
+                            const std::uint32_t sub = lane_now & 7u, group = lane_now >> 3;
+                            const float* coefficients = reinterpret_cast<const float*>(query_lds + args.sketch_offset) + sub * 8;
+                            const float4 q0 = *reinterpret_cast<const float4*>(coefficients), q1 = *reinterpret_cast<const float4*>(coefficients + 4);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float lower = sketch_record_bound(early_record[r], q0, q1, sub, sketch_margin);
+                                if (sub == 0u)
+                                    cand_distances[(std::uint32_t)r * 8 + group] = lower;
+                            }
+                        }
                     }
                 }
                 if (!popped)
@@ -2038,8 +2085,12 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                         aside_count += popcount64(ballot(lane_bit(taken_mask) && old == none_slot_k));
                     }
                 }
+#ifdef USEARCH_AMD_PHASES
+                if (!round_counted)
+                    clock.second_round(ballot(asks && old != none_slot_k && old != neighbor) != 0);
+#endif
                 if constexpr (!aside_ak)
-                    old = probe_rest(visits, visits_mask, h, neighbor, old);
+                    old = probe_rest(visits, visits_mask, h_rest, neighbor, old);
                 fresh = present && old == none_slot_k;
                 if constexpr (seen_ak) {
                     if (seen && asks)
@@ -2091,7 +2142,13 @@ UA_DEVICE bool search_one(const snapshot_view_t& ix, const search_args_t& args, 
                 const std::uint32_t sub = lane & 7u, group = lane >> 3;
                 bool member;
                 float bound;
-                if (records_early) {
+                if (records_early && overlap_ak) {
+                    // the bounds were computed while the probe's second round was in flight, for every list position
+                    wave_sync<false>();
+                    member = fresh;
+                    mine_slot = neighbor;
+                    bound = fresh ? cand_distances[lane] : 0.f; // (fresh lanes sit below 32: the list has no more cells)
+                } else if (records_early) {
                     const float* coefficients = reinterpret_cast<const float*>(query_lds + args.sketch_offset) + sub * 8;
                     const float4 q0 = *reinterpret_cast<const float4*>(coefficients), q1 = *reinterpret_cast<const float4*>(coefficients + 4);
 #pragma unroll
