@@ -9,7 +9,10 @@ with two extra objects:
   "roofline":     achieved algorithmic GB/s of the search kernel (bytes from the reference's own per-query counters,
                   SURVEY §8d, ÷ HIP-event kernel time measured on the launch stream) against the 8 TB/s HBM peak;
   "cpu_baseline": the REAL reference (`oracle/_ref`, compiled from /root/reference's own headers) searching the same
-                  index with the loop of cpp/bench.cpp:352-377 on all host cores, on a bounded sample (rank 0, N = 1).
+                  index with the loop of cpp/bench.cpp:352-377 on all host cores, on a bounded sample (rank 0, N = 1; `--full`).
+`--full` is the whole measurement: the image saved and loaded back through the device loader, the matrix placed by
+trial, the host-buffer legs, the reference's legs ("cpu_baseline"), the second load, the stress rows and BASELINE.json's other
+configurations. A plain run is the quick line: what the metric needs — the index as the builder left it, recall sweep, timed steps.
 
 Default workload = the configuration BASELINE.json's metric is quoted on: 10M x 768 f16 cosine, batch 10 000, k = 10.
 The seeded synthetic vectors are generated in HBM and the index is built ON THE GPU (`usearch_amd.build`, ≈20 s for 10M;
@@ -167,7 +170,15 @@ def flush_native_stdio() -> None:
 
 
 def recall_per_query(found: np.ndarray, truth: np.ndarray, k: int) -> np.ndarray:
-    return np.array([len(np.intersect1d(found[i], truth[i])) / k for i in range(len(found))], dtype=np.float64)
+    """Per row, the distinct keys that `found` and `truth` share, over k (`len(np.intersect1d(found[i], truth[i])) / k`, all rows at once)."""
+    out = np.zeros(len(found), dtype=np.float64)
+    for begin in range(0, len(found), 4096):  # rows x k x k comparisons a block
+        ordered = np.sort(truth[begin:begin + 4096], axis=1)
+        distinct = np.ones(ordered.shape, dtype=bool)
+        distinct[:, 1:] = ordered[:, 1:] != ordered[:, :-1]
+        shared = (ordered[:, :, None] == found[begin:begin + 4096, None, :]).any(axis=2)
+        out[begin:begin + 4096] = (shared & distinct).sum(axis=1) / k
+    return out
 
 
 def interval(values: np.ndarray):
@@ -274,12 +285,12 @@ PRESETS = {
 
 def secondary_lines(presets, timeout_seconds: float) -> list:
     """BASELINE.json's other configurations (`PRESETS`), each run by this script in a process of its own — `python bench.py --config cN
-    --no-secondary …`: its own index at the configuration's full size, its own recall sweep, roofline and reference baseline — and
+    --full --no-secondary …`: its own index at the configuration's full size, its own recall sweep, roofline and reference baseline — and
     summarised for `config.secondary` of the default line. A configuration that fails or overruns is reported as such, never hidden."""
     import subprocess
     out = []
     for name in presets:
-        command = [sys.executable, os.path.abspath(__file__), "--config", name, "--no-secondary", "--no-stress-rows", "--steps", "10",
+        command = [sys.executable, os.path.abspath(__file__), "--config", name, "--full", "--no-secondary", "--no-stress-rows", "--steps", "10",
                    "--warmup", "2", "--cpu-seconds", "4", "--recall-queries", "2000", "--no-load-timing"]
         t0 = time.time()
         entry = {"preset": name, "what": PRESETS[name]["what"], "command": " ".join(["python", "bench.py"] + command[2:])}
@@ -629,6 +640,12 @@ def main() -> None:
     parser.add_argument("--gpus", type=int, default=1)
     parser.add_argument("--steps", type=int, default=5)
     parser.add_argument("--warmup", type=int, default=1)
+    parser.add_argument("--full", action="store_true",
+                        help="everything around the metric as well: the host-buffer legs, the reference on the host cores (cpu_baseline, "
+                             "ground-truth and frontier checks, load timing), the second load of the image, the stress rows and BASELINE.json's "
+                             "other configurations, on the saved image loaded back through the device loader and placed by trial before the "
+                             "timed steps: the whole measurement of DESIGN.md §8. Without it the run is what the metric needs: the index as "
+                             "the builder left it, recall sweep, timed steps")
     parser.add_argument("--dump-outputs", default=None, metavar="DIR",
                         help="after the timed steps, write what the last one returned (rank 0: keys, distances, counts, traversal "
                              "counters) as DIR/<name>.npy in float32 / float64; a seeded sample of rows above 64 MB in all")
@@ -669,10 +686,10 @@ def main() -> None:
                         help="skip loading the image a SECOND time after the timed steps and timing the batch on that copy "
                              "(roofline.kernel_ms_second_load: how reproducible the settled placement is)")
     parser.add_argument("--no-reload", action="store_true",
-                        help="search the builder's own arrays instead of the saved image loaded back through the device loader "
-                             "(the default walks what `usearch_load` would give a user: matrix placed after the settle window)")
+                        help="with --full: search the builder's own arrays instead of the saved image loaded back through the device loader "
+                             "(--full walks what `usearch_load` would give a user: matrix placed after the settle window)")
     parser.add_argument("--no-tune", action="store_true",
-                        help="do not place the matrix by trial on the batch before the timed steps (usearch_amd_snapshot_tune)")
+                        help="with --full: do not place the matrix by trial on the batch before the timed steps (usearch_amd_snapshot_tune)")
     parser.add_argument("--no-secondary", action="store_true",
                         help="skip BASELINE.json's other configurations (c1, c2, c4, c5 — each in a process of its own, summarised "
                              "under config.secondary of the default line)")
@@ -694,6 +711,12 @@ def main() -> None:
         for name, value in PRESETS[args.config]["set"].items():
             if getattr(args, name) == parser.get_default(name):
                 setattr(args, name, value)
+    if not args.full:  # the legs that only --full runs; each keeps its own --no-… switch under --full
+        args.no_host_api = args.no_cpu_baseline = args.no_placement_check = args.no_stress_rows = args.no_secondary = True
+        # ... and what places the matrix before the timed steps: the image's round trip through the host and the device loader (save,
+        # settle window, load: 3.7 s on the headline) and the placement trials (3 s, two settle windows among them). The steps walk the
+        # arrays the builder left; on the headline a step costs the same on them (23.49 ms against 23.52 ms loaded and tuned)
+        args.no_reload = args.no_tune = True
     if args.dry:
         plan = memory_plan(args.n, args.dim, args.dtype, args.connectivity, args.queries, args.k)
         hbm = 288 * 10**9
@@ -909,10 +932,14 @@ def main() -> None:
     #      now the host does what a service does before it serves: hands the engine a sample of the batches to come — this batch, at the
     #      expansion just chosen — and lets it place the matrix by trial (`usearch_amd_snapshot_tune`: explicit, synchronous, never inside
     #      a search call). Nothing moves after this line; the timed steps assert it.
-    placement_policy = ("the loader places the matrix once, after USEARCH_AMD_SETTLE_MS (1000) since the last big release; then "
-                        "usearch_amd_snapshot_tune on the batch at the chosen expansion BEFORE the timed steps: up to 8 fresh device-to-device "
-                        "copies timed against the incumbent on the batch's first queries, the faster stays, three wins of the incumbent in "
-                        "a row end it; no trial inside any search call; the scratch block is drawn by run_ladder when a chip-filling launch "
+    placement_policy = (("the builder's own matrix is walked (a run without --full, or --no-reload); " if args.builder == "gpu" and args.no_reload else
+                         "the loader places the matrix once, after USEARCH_AMD_SETTLE_MS (1000) since the last big release; ") +
+                        ("no placement by trial before the timed steps (a run without --full, or --no-tune); "
+                         if args.no_tune or sharded_searcher is not None else
+                         "then usearch_amd_snapshot_tune on the batch at the chosen expansion BEFORE the timed steps: up to 8 fresh "
+                         "device-to-device copies timed against the incumbent on the batch's first queries, the faster stays, three wins of "
+                         "the incumbent in a row end it; ") +
+                        "no trial inside any search call; the scratch block is drawn by run_ladder when a chip-filling launch "
                         "needs a new one (<= 8 candidates timed by the launch's first queries)")
     tuned = None
 

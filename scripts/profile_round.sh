@@ -46,6 +46,6 @@ done
 rm -rf "$OUT/stats"
 python "$REPO/scripts/pmc_traffic.py" "$OUT/pmc_FETCH_SIZE.csv" "$OUT/pmc_WRITE_SIZE.csv" search_kernel "$OUT/stats_bench.json" \
     "$OUT/pmc_TCC_EA0_RDREQ_sum_TCC_EA0_RDREQ_32B_sum_.csv" "$OUT/pmc_TCC_EA0_WRREQ_sum_TCC_EA0_WRREQ_64B_sum_.csv" > "$OUT/traffic.json" && cat "$OUT/traffic.json"
-python "$REPO/bench.py" "$@" --expansion $EF --traffic-json "$OUT/traffic.json" --wave-clock --no-secondary --warmup $WARMUP > "$OUT/bench.json" 2> "$OUT/bench.log"
+python "$REPO/bench.py" "$@" --expansion $EF --traffic-json "$OUT/traffic.json" --wave-clock --full --no-secondary --warmup $WARMUP > "$OUT/bench.json" 2> "$OUT/bench.log"
 cat "$OUT/bench.json"
 du -sh "$OUT"; head -8 "$OUT/kernel_stats.csv"

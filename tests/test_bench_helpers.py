@@ -16,6 +16,21 @@ def test_synthetic_vectors_in_every_storage_kind():
     assert np.array_equal(bits, np.packbits(bench.synthetic_vectors(8, 16, "f32", seed=5) > 0, axis=1))
 
 
+def test_recall_per_query_is_the_intersection_of_distinct_keys():
+    """`recall_per_query` scores blocks of rows at once: row by row it is `len(np.intersect1d(found[i], truth[i])) / k`, with keys
+    repeated on either side (filler zeros of short results, duplicate keys) counted once, over more rows than one block holds."""
+    rng, rows, k = np.random.default_rng(17), 4096 + 37, 10
+    truth = rng.integers(0, 40, size=(rows, k)).astype(np.uint64)  # 10 draws of 40 values: most rows repeat a key
+    found = rng.integers(0, 40, size=(rows, k)).astype(np.uint64)
+    found[: rows // 2, :6] = truth[: rows // 2, :6]
+    found[0], truth[1], found[2] = 0, 0, truth[2]
+    expected = np.array([len(np.intersect1d(found[i], truth[i])) / k for i in range(rows)], dtype=np.float64)
+    got = bench.recall_per_query(found, truth, k)
+    assert got.dtype == np.float64 and np.array_equal(got, expected)
+    assert expected[2] == len(np.unique(truth[2])) / k and expected.min() < expected.max()
+    assert bench.recall_per_query(found[:0], truth[:0], k).shape == (0,)
+
+
 def test_host_core_count_respects_the_cgroup_quota():
     assert 1 <= bench.host_cores() <= (__import__("os").cpu_count() or 1)
 

@@ -161,6 +161,18 @@ def test_build_is_reproducible_and_takes_device_vectors():
     assert np.array_equal(first, third)
 
 
+def test_saved_matrix_of_padded_rows_is_the_input_across_copy_blocks():
+    """`save_buffer` brings rows that sit at a pitch in HBM over in blocks of 256 MiB and packs them on the host: 3120-byte rows at a
+    pitch of 3200 fill a block with 83 886 of them, so 90 000 rows take a full block and a short one."""
+    n, ndim = 90_000, 780
+    vectors = np.random.default_rng(31).standard_normal((n, ndim), dtype=np.float32)
+    built = usearch_amd.build(vectors, "l2sq", "f32", connectivity=4, expansion_add=16)
+    assert built.index.row_stride == 3200 and (256 << 20) // 3200 < n
+    image = built.save_buffer()
+    assert image[:8].view(np.uint32).tolist() == [n, 4 * ndim]
+    assert np.array_equal(image[8:8 + vectors.nbytes].view(np.float32).reshape(n, ndim), vectors)
+
+
 def test_hubs_lose_no_reverse_link(reference):
     """A few rows that every other row picks as a neighbour (long vectors under the inner product): far more reverse-link
     requests per pass than a hub's inbox holds. The reference takes any number (index.hpp:3848-3893, one at a time under the
