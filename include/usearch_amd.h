@@ -42,6 +42,8 @@ enum {
     usearch_amd_scalar_i8_k = 4,
     usearch_amd_scalar_b1_k = 5,
     usearch_amd_scalar_bf16_k = 6,
+    usearch_amd_scalar_f8_k = 7, /**< OCP e4m3fn codes, a byte each (the reference's serialized code for `f8_k`, index_dense.hpp:223):
+                                      casts and the tiled exact search so far, every other entry point refuses the kind by name */
 };
 
 /** Optional knobs of one batched search; zero-initialise for the defaults. */
@@ -395,7 +397,8 @@ USEARCH_AMD_EXPORT void usearch_amd_exact_search_dataset(void const* dataset, si
 
 /**
  *  The same call, same arguments, as a TILED MATRIX PRODUCT over the uploaded rows (usearch_amd/csrc/exact_tiled.hip) for every
- *  pair that has a tiled kernel — cos / ip / l2sq over f16, bf16 and i8, cos / ip over f32, and hamming / tanimoto / jaccard / sorensen
+ *  pair that has a tiled kernel — cos / ip / l2sq over f16, bf16, i8 and f8 (e4m3 codes, decoded to f16 in registers: this call is
+ *  all f8 has so far, the untiled one refuses it), cos / ip over f32, and hamming / tanimoto / jaccard / sorensen
  *  over b1 (the bit tile, exact_bits.hip: the same bits as the untiled call), `wanted` ≤ 64; any other pair is refused ("No tiled
  *  exact-search kernel for this metric / scalar kind / result count"), never sent down the other kernel quietly. Float kinds:
  *  every distance lies within a derived bound of the f64 distance of the row it names (f32: f32 arithmetic in the matrix unit's
@@ -669,6 +672,16 @@ USEARCH_AMD_EXPORT float usearch_amd_last_distances_ms(usearch_amd_snapshot_t sn
  *  equal (nothing written), 1 after writing the cast vector.
  */
 USEARCH_AMD_EXPORT int usearch_amd_cast(int from_kind, int to_kind, void const* input, size_t dimensions, void* output);
+
+/**
+ *  A whole matrix cast by ONE kernel on the current device (usearch_amd/csrc/cast_rows.hip): `count` rows of f32, f16, bf16 or f64
+ *  → f8 codes (`dimensions` bytes a row) under the very rules of `usearch_amd_cast`, byte for byte; any other pair of kinds is
+ *  refused. Strides in bytes. `on_device` as `vectors_on_device` of `usearch_amd_build`: 0 = host buffers (uploaded, fetched
+ *  back), 1 = both matrices are device pointers, and the call returns when the kernel has finished.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_cast_rows(void const* input, size_t count, size_t input_stride, int from_kind, size_t dimensions,
+                                              int to_kind, void* output, size_t output_stride, int on_device,
+                                              usearch_amd_error_t* error);
 
 /* ---- k-means clustering on the device ---------------------------------------------------------------------------------------
  *  `kmeans_clustering_gt` (index_plugins.hpp:2199-2500; `usearch.index.kmeans`, python/usearch/index.py:1618-1712) with its

@@ -41,6 +41,7 @@ scalar_kind_t scalar_from_c(int kind) { // c/lib.cpp:61-79
     case usearch_amd_scalar_i8_k: return scalar_i8_k;
     case usearch_amd_scalar_b1_k: return scalar_b1x8_k;
     case usearch_amd_scalar_bf16_k: return scalar_bf16_k;
+    case usearch_amd_scalar_f8_k: return scalar_f8_k;
     default: return scalar_unknown_k;
     }
 }
@@ -53,6 +54,7 @@ int scalar_to_c(scalar_kind_t kind) {
     case scalar_i8_k: return usearch_amd_scalar_i8_k;
     case scalar_b1x8_k: return usearch_amd_scalar_b1_k;
     case scalar_bf16_k: return usearch_amd_scalar_bf16_k;
+    case scalar_f8_k: return usearch_amd_scalar_f8_k;
     default: return 0;
     }
 }
@@ -909,6 +911,24 @@ int usearch_amd_cast(int from_kind, int to_kind, void const* input, size_t dimen
                        dimensions, static_cast<std::uint8_t*>(output))
                ? 1
                : 0;
+}
+
+void usearch_amd_cast_rows(void const* input, size_t count, size_t input_stride, int from_kind, size_t dimensions, int to_kind,
+                           void* output, size_t output_stride, int on_device, usearch_amd_error_t* error) try {
+    const scalar_kind_t from = scalar_from_c(from_kind), to = scalar_from_c(to_kind);
+    const char* e = nullptr;
+    if (on_device) {
+        e = cast_rows_device(from, to, input, count, input_stride, dimensions, output, output_stride, nullptr);
+        if (!e)
+            if (const hipError_t h = hipStreamSynchronize(nullptr); h != hipSuccess)
+                e = hipGetErrorString(h);
+    } else {
+        e = cast_rows_host(from, to, input, count, input_stride, dimensions, output, output_stride);
+    }
+    if (e)
+        fail(error, e);
+} catch (...) {
+    fail_from_exception(error);
 }
 
 // ---- semantic join (join.hpp)

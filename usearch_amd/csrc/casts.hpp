@@ -10,6 +10,10 @@
  *    float kinds → i8     → L2-normalise in double, × 127, clamp to ±127, truncate toward zero (1172-1191)
  *    i8 → float kinds     → x / 127.f in the target type (1193-1201)
  *    float ↔ float kinds  → element-wise conversion through float/double, IEEE round-to-nearest-even (1105-1113)
+ *  f8 (OCP e4m3fn; the reference names the kind and has no arithmetic for it, so these rules are this project's own):
+ *    float kinds → f8     → the nearest finite code, ties to the even code, ±448 beyond it (±∞ too, as the i8 cast clips), a NaN →
+ *                           0x7F with its sign, −0 stays −0, subnormal codes are produced; one rounding from the source's own value
+ *    f8 → float kinds     → the exact value (every e4m3 value is an f16 value); i8 and b1 meet f8 by the rules above
  *  It runs once per query over `dimensions` scalars — O(Q·d) host work against O(Q·2000·d) device work.
  */
 #pragma once
@@ -30,6 +34,61 @@ __host__ __device__ inline float bf16_bits_to_f32(std::uint16_t h) { return __bu
 /// bf16_bits_t(float) of index_plugins.hpp:430-470 truncates (keeps the upper 16 bits) — no rounding.
 __host__ __device__ inline std::uint16_t f32_to_bf16_bits(float f) { return (std::uint16_t)(__builtin_bit_cast(std::uint32_t, f) >> 16); }
 
+// ---- f8 = OCP e4m3fn: sign, 4 exponent bits (bias 7), 3 mantissa bits; exponent 0 = subnormals m/8·2⁻⁶; no infinities; 0x7F and
+//      0xFF are the NaNs; ±448 (0x7E / 0xFE) the largest. Plain integer arithmetic on host and device alike — no conversion
+//      instruction, whose answer past 448 depends on a mode bit (cast_rows.hip runs these very functions).
+__host__ __device__ inline float f8_bits_to_f32(std::uint8_t code) {
+    const std::uint32_t sign = (std::uint32_t)(code & 0x80u) << 24, exponent = (code >> 3) & 15u, mantissa = code & 7u;
+    if (exponent == 15u && mantissa == 7u)
+        return __builtin_bit_cast(float, sign | 0x7FC00000u);
+    if (exponent == 0u) // m·2⁻⁹, exact
+        return __builtin_bit_cast(float, sign | __builtin_bit_cast(std::uint32_t, (float)mantissa * 0x1p-9f));
+    return __builtin_bit_cast(float, sign | ((exponent + 120u) << 23) | (mantissa << 20));
+}
+
+/// The code of a magnitude below 2⁻⁶ given as `significand`·2^−`shift`·2⁻⁹: the nearest multiple of 2⁻⁹, ties to the even one
+/// (8 is the code of 2⁻⁶ itself, the smallest normal: the carry lands where it belongs).
+template <typename bits_at> __host__ __device__ inline std::uint8_t f8_subnormal_code(bits_at significand, std::uint32_t shift) {
+    const bits_at one = 1, whole = significand >> shift, rest = significand & ((one << shift) - 1), half = one << (shift - 1);
+    return (std::uint8_t)(whole + ((rest > half || (rest == half && (whole & 1))) ? 1 : 0));
+}
+
+__host__ __device__ inline std::uint8_t f32_to_f8_bits(float f) {
+    const std::uint32_t bits = __builtin_bit_cast(std::uint32_t, f), magnitude = bits & 0x7FFFFFFFu;
+    const std::uint8_t sign = (std::uint8_t)((bits >> 24) & 0x80u);
+    if (magnitude > 0x7F800000u)
+        return sign | 0x7Fu;
+    if (magnitude >= 0x43E00000u) // 448 and beyond (what lies between 448 and the next step rounds down to it anyway)
+        return sign | 0x7Eu;
+    if (magnitude >= 0x3C800000u) { // 2⁻⁶ and beyond: 20 mantissa bits go, exponent field − 120
+        const std::uint32_t rounded = magnitude + 0x7FFFFu + ((magnitude >> 20) & 1u);
+        return sign | (std::uint8_t)((rounded >> 20) - (120u << 3));
+    }
+    const std::uint32_t exponent = magnitude >> 23, field = exponent ? exponent : 1u; // value = significand·2^(field − 150)
+    const std::uint32_t shift = 141u - field;                                         // … = significand·2^−shift·2⁻⁹, shift ≥ 21
+    if (shift >= 25u) // significand < 2²⁴: below half a step
+        return sign;
+    return sign | f8_subnormal_code<std::uint32_t>((magnitude & 0x7FFFFFu) | (exponent ? 0x800000u : 0u), shift);
+}
+
+__host__ __device__ inline std::uint8_t f64_to_f8_bits(double f) {
+    const std::uint64_t bits = __builtin_bit_cast(std::uint64_t, f), magnitude = bits & 0x7FFFFFFFFFFFFFFFull;
+    const std::uint8_t sign = (std::uint8_t)((bits >> 56) & 0x80u);
+    if (magnitude > 0x7FF0000000000000ull)
+        return sign | 0x7Fu;
+    if (magnitude >= 0x407C000000000000ull) // 448
+        return sign | 0x7Eu;
+    if (magnitude >= 0x3F90000000000000ull) { // 2⁻⁶: 49 mantissa bits go, exponent field − 1016
+        const std::uint64_t rounded = magnitude + 0xFFFFFFFFFFFFull + ((magnitude >> 49) & 1u);
+        return sign | (std::uint8_t)((rounded >> 49) - (1016u << 3));
+    }
+    const std::uint64_t exponent = magnitude >> 52, field = exponent ? exponent : 1u; // value = significand·2^(field − 1075)
+    const std::uint64_t shift = 1066u - field;                                        // shift ≥ 50
+    if (shift >= 54u) // significand < 2⁵³: below half a step
+        return sign;
+    return sign | f8_subnormal_code<std::uint64_t>((magnitude & 0xFFFFFFFFFFFFFull) | (exponent ? 1ull << 52 : 0ull), (std::uint32_t)shift);
+}
+
 inline double load_scalar(scalar_kind_t kind, const std::uint8_t* p, std::size_t i) {
     switch (kind) {
     case scalar_f64_k: { double v; std::memcpy(&v, p + 8 * i, 8); return v; }
@@ -37,6 +96,7 @@ inline double load_scalar(scalar_kind_t kind, const std::uint8_t* p, std::size_t
     case scalar_f16_k: { std::uint16_t v; std::memcpy(&v, p + 2 * i, 2); return f16_bits_to_f32(v); }
     case scalar_bf16_k: { std::uint16_t v; std::memcpy(&v, p + 2 * i, 2); return bf16_bits_to_f32(v); }
     case scalar_i8_k: return (double)(std::int8_t)p[i];
+    case scalar_f8_k: return f8_bits_to_f32(p[i]);
     default: return 0;
     }
 }
@@ -47,6 +107,7 @@ inline void store_scalar(scalar_kind_t kind, std::uint8_t* p, std::size_t i, flo
     case scalar_f32_k: std::memcpy(p + 4 * i, &as_float, 4); break;
     case scalar_f16_k: { std::uint16_t v = f32_to_f16_bits(as_float); std::memcpy(p + 2 * i, &v, 2); break; }
     case scalar_bf16_k: { std::uint16_t v = f32_to_bf16_bits(as_float); std::memcpy(p + 2 * i, &v, 2); break; }
+    case scalar_f8_k: p[i] = f64_to_f8_bits(as_double); break;
     default: break;
     }
 }
@@ -95,12 +156,19 @@ inline bool cast_vector(scalar_kind_t from, scalar_kind_t to, const std::uint8_t
                 store_scalar(to, output, i, 0.f, (double)x / 127.f);
             } else if (to == scalar_f32_k) {
                 store_scalar(to, output, i, (float)x / 127.f, 0.0);
+            } else if (to == scalar_f8_k) {
+                output[i] = f32_to_f8_bits((float)x / 127.f);
             } else if (to == scalar_f16_k) { // f16_t(int) then a float division, rounded back to f16
                 store_scalar(to, output, i, f16_bits_to_f32(f32_to_f16_bits((float)x)) / 127.f, 0.0);
             } else { // bf16
                 store_scalar(to, output, i, bf16_bits_to_f32(f32_to_bf16_bits((float)x)) / 127.f, 0.0);
             }
         }
+        return true;
+    }
+    if (to == scalar_f8_k && from != scalar_f64_k) { // f32, f16 and bf16 are f32 values: the function the device runs for them
+        for (std::size_t i = 0; i != dimensions; ++i)
+            output[i] = f32_to_f8_bits((float)load_scalar(from, input, i));
         return true;
     }
     for (std::size_t i = 0; i != dimensions; ++i) {

@@ -31,6 +31,7 @@ enum scalar_kind_t : std::uint8_t {
     scalar_f64_k = 10,
     scalar_f32_k = 11,
     scalar_f16_k = 12,
+    scalar_f8_k = 13, // OCP e4m3fn codes (bias 7, no infinities, 0x7F / 0xFF = NaN, ±448 the largest): batched exact search only so far
     scalar_i8_k = 23,
     scalar_u64_k = 14, // key kind of index_dense_t (index_dense.hpp:2229)
     scalar_u32_k = 15, // compressed slot kind of index_dense_t
@@ -40,6 +41,7 @@ enum scalar_kind_t : std::uint8_t {
 inline std::size_t bytes_per_vector(scalar_kind_t kind, std::size_t dimensions) {
     switch (kind) {
     case scalar_b1x8_k: return (dimensions + 7) / 8;
+    case scalar_f8_k:
     case scalar_i8_k: return dimensions;
     case scalar_f16_k:
     case scalar_bf16_k: return dimensions * 2;

@@ -11,6 +11,16 @@
  *  four scalars and each feeds one 32x32x2 step — lanes 0 … 31 carry k = e, lanes 32 … 63 k = 4 + e, for A and B alike — so the sum
  *  is right as it is; only the order of its terms is the kernel's own. C/D: column (B row) = lane & 31 (`accumulator_column`),
  *  row (A row) = (reg & 3) + 8·(reg >> 2) + 4·(lane >> 5) (`accumulator_row`).
+ *
+ *  f8 (OCP e4m3 codes, a byte each): the lane's 16 bytes are decoded in registers to sixteen f16 values — exact, every e4m3 value is
+ *  an f16 value — and go through the f16 instruction as two operands, chained (`multiply`, `decode_f8x16`); any split of the 16
+ *  scalars into two operands gives the right sum, because the query's scalar and the row's scalar land on the same k. What f8 buys
+ *  here is bytes — half of an f16 row's from HBM to LDS to registers, which is what bounds the tiles — not matrix-unit rate.
+ *  gfx950's fp8 instructions were tried first, with the same geometry, and are NOT used: on an MI355X both `v_mfma_f32_32x32x16_fp8_fp8`
+ *  (twice per 16 bytes) and `v_mfma_scale_f32_32x32x64_f8f6f4` (k = 64, two steps to an instruction, unit scales) decode every code
+ *  exactly but return sums about 2·10⁻⁵ of their own size from the f64 value — 1.5 … 1.9 of the bounds of tests/exact_truth.py for
+ *  64-d cos, 96-d l2sq and 200-d ip, whatever the length of the row — where this route's f32 sums of the (exact) products are exact for ip and l2sq
+ *  and within 0.011 of the bound for cos: inside those instructions the products are not summed in f32. The bound is the contract, so the products go the f16 way.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -44,6 +54,21 @@ template <> struct accumulator_gt<scalar_i8_k> {
     using type = i32x16_t;
 };
 
+/// Sixteen e4m3 codes → their sixteen f16 values, in order, as two operands of the f16 instruction: `v_cvt_pk_f32_fp8` (OCP e4m3 on
+/// gfx950) decodes two codes exactly, `v_cvt_pkrtz_f16_f32` packs them — nothing to round, the values are f16 values.
+__device__ __forceinline__ void decode_f8x16(uint4 codes, f16x8_t& low, f16x8_t& high) {
+    const std::uint32_t words[4] = {codes.x, codes.y, codes.z, codes.w};
+    std::uint32_t packed[8];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const auto first = __builtin_amdgcn_cvt_pk_f32_fp8((int)words[w], false), second = __builtin_amdgcn_cvt_pk_f32_fp8((int)words[w], true);
+        packed[2 * w] = __builtin_bit_cast(std::uint32_t, __builtin_amdgcn_cvt_pkrtz(first[0], first[1]));
+        packed[2 * w + 1] = __builtin_bit_cast(std::uint32_t, __builtin_amdgcn_cvt_pkrtz(second[0], second[1]));
+    }
+    low = __builtin_bit_cast(f16x8_t, uint4{packed[0], packed[1], packed[2], packed[3]});
+    high = __builtin_bit_cast(f16x8_t, uint4{packed[4], packed[5], packed[6], packed[7]});
+}
+
 /// One 32 × 32 block: c += A·Bᵀ over the 16 bytes each lane holds of its A row and of its B row.
 template <int scalar_ak>
 __device__ __forceinline__ typename accumulator_gt<scalar_ak>::type multiply(uint4 a, uint4 b,
@@ -61,6 +86,12 @@ __device__ __forceinline__ typename accumulator_gt<scalar_ak>::type multiply(uin
         c = __builtin_amdgcn_mfma_f32_32x32x2f32(x[1], y[1], c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_32x32x2f32(x[2], y[2], c, 0, 0, 0);
         return __builtin_amdgcn_mfma_f32_32x32x2f32(x[3], y[3], c, 0, 0, 0);
+    } else if constexpr (scalar_ak == scalar_f8_k) {
+        f16x8_t a_low, a_high, b_low, b_high;
+        decode_f8x16(a, a_low, a_high);
+        decode_f8x16(b, b_low, b_high);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_low, b_low, c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a_high, b_high, c, 0, 0, 0);
     } else
         return __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4_t, a), __builtin_bit_cast(i32x4_t, b), c, 0, 0, 0);
 }
@@ -175,11 +206,16 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const std::uint8_t* rows
         const std::uint8_t* p = rows + row * stride;
         float sum = 0.f;
         int exact = 0;
-        // bytes a lane takes per round: one f32, one 16-bit scalar, or two i8. `bytes` is what the row holds, whatever its pitch
+        // bytes a lane takes per round: one f32, one 16-bit scalar, two i8, or one f8. `bytes` is what the row holds, whatever its pitch
         // (a query row is not padded to 16 bytes, and a caller's batch need not be aligned to more than its scalars)
-        constexpr std::uint32_t width = scalar_ak == scalar_f32_k ? 4 : 2;
+        constexpr std::uint32_t width = scalar_ak == scalar_f32_k ? 4 : scalar_ak == scalar_f8_k ? 1 : 2;
         for (std::uint32_t b = lane * width; b < bytes; b += 64 * width) {
-            if constexpr (scalar_ak == scalar_i8_k) {
+            if constexpr (scalar_ak == scalar_f8_k) {
+                // `v_cvt_pk_f32_fp8` (OCP e4m3 on gfx950; decoding is exact): element 0 of the pair is the code. A lane takes every
+                // 64th element by fmaf, as for f16: the bound derived for that scheme (tests/exact_truth.py) carries over
+                const float x = __builtin_amdgcn_cvt_pk_f32_fp8((int)p[b], false)[0];
+                sum = __builtin_fmaf(x, x, sum);
+            } else if constexpr (scalar_ak == scalar_i8_k) {
                 const int x = (std::int8_t)p[b], y = b + 1 < bytes ? (std::int8_t)p[b + 1] : 0;
                 exact += x * x + y * y;
             } else if constexpr (scalar_ak == scalar_f32_k) {

@@ -1421,7 +1421,9 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
                                       const void* queries, std::size_t queries_count, std::size_t queries_stride,
                                       std::size_t wanted, std::uint64_t* keys, std::size_t keys_stride,
                                       float* distances, std::size_t distances_stride, bool tiled) {
-    if (!kernel_available(metric, scalar))
+    // (f8 has the matrix-unit tiles and nothing else so far: asked for by name it is the tiles' table that answers, any other way
+    // it is refused like every pair without a kernel)
+    if (!kernel_available(metric, scalar) && !(tiled && scalar == scalar_f8_k))
         return "No MI355X kernel for this metric / scalar kind combination";
     if (!queries_count || !wanted)
         return nullptr;

@@ -590,6 +590,14 @@ const char* merge_shards_enqueue(const float* distances, const std::uint64_t* ke
                                  std::uint64_t* out_keys, std::uint64_t* out_counts, hipStream_t stream,
                                  bool later_position_first = true);
 
+/// A whole matrix cast by one kernel (cast_rows.hip): rows of f32, f16, bf16 or f64 → f8 codes under the rules of casts.hpp; any
+/// other pair of kinds is refused. `_device`: both matrices in HBM, enqueued on `stream`; `_host`: host buffers, uploaded and
+/// fetched back. Strides in bytes.
+const char* cast_rows_device(scalar_kind_t from, scalar_kind_t to, const void* input, std::size_t count, std::size_t input_stride,
+                             std::size_t dimensions, void* output, std::size_t output_stride, hipStream_t stream);
+const char* cast_rows_host(scalar_kind_t from, scalar_kind_t to, const void* input, std::size_t count, std::size_t input_stride,
+                           std::size_t dimensions, void* output, std::size_t output_stride);
+
 /// Is there a HIP kernel for this (metric, scalar) pair?
 bool kernel_available(metric_kind_t metric, scalar_kind_t scalar);
 

@@ -32,7 +32,7 @@ inline std::uint64_t wide_padded_stride(std::uint64_t bytes_per_vector) {
 }
 
 /// Which (metric, scalar kind) pairs have a tiled kernel, and for how many results per query: cos, ip and l2sq over f16, bf16 and
-/// i8, cos and ip over f32, 1 … `max_wanted_k` results. Both kernels are instantiated for every pair here — which of them runs is
+/// i8 and f8 (e4m3 codes), cos and ip over f32, 1 … `max_wanted_k` results. Both kernels are instantiated for every pair here — which of them runs is
 /// a matter of the batch's shape (`plan_exact`), never of the kind. tests/test_exact_tiled_pairs.py pins it through
 /// `usearch_amd_test_exact_tiled_pair`.
 /// l2sq over f32 is NOT here, on purpose: that `exact="tiled"` over an l2sq f32 index is refused is behaviour the suite pins
@@ -44,7 +44,7 @@ inline bool exact_tiled_pair(metric_kind_t metric, scalar_kind_t scalar, std::ui
         return false;
     if (scalar == scalar_f32_k)
         return metric == metric_cos_k || metric == metric_ip_k;
-    if (scalar != scalar_f16_k && scalar != scalar_bf16_k && scalar != scalar_i8_k)
+    if (scalar != scalar_f16_k && scalar != scalar_bf16_k && scalar != scalar_i8_k && scalar != scalar_f8_k)
         return false;
     return metric == metric_cos_k || metric == metric_ip_k || metric == metric_l2sq_k;
 }

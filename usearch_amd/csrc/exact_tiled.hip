@@ -16,7 +16,9 @@
  *  kernel, ties included — selection is the total order (distance ↑, slot ↓) that `search_exact_`'s lower_bound inserts
  *  produce), and cos and ip over f32 — l2sq over f32 stays refused, see `exact_tiled_pair` — (f32 products AND sums: an fmaf chain in the matrix unit's order, one rounding per product — every
  *  distance within a derived bound of its row's f64 distance, tests/exact_truth_f32.py; NOT bit-equal to the wave kernel and
- *  not promised within 1e-5 of it — opt-in, the wave kernel stays what `exact=True` runs). Row shapes: any number of bytes; a
+ *  not promised within 1e-5 of it — opt-in, the wave kernel stays what `exact=True` runs), and cos, ip and l2sq over f8 (OCP e4m3
+ *  codes, half the staged bytes of f16; a lane's 16 codes are decoded to f16 in registers and take the f16 instruction twice — the
+ *  f16 pairs' bound holds unchanged, tests/test_gpu_exact_f8.py — the raw-matrix route only: nothing else stores f8). Row shapes: any number of bytes; a
  *  stored row is zero padded to whole 16-byte pieces, a query row need not be (32-d f32 = 128 B is one staged chunk, 33-d =
  *  132 B leaves one scalar alone in the second, 50-d = 200 B half fills a 16-byte piece).
  *
@@ -1183,6 +1185,9 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
     UA_TILED(metric_l2sq_k, scalar_i8_k)
     UA_TILED(metric_cos_k, scalar_f32_k)
     UA_TILED(metric_ip_k, scalar_f32_k)
+    UA_TILED(metric_cos_k, scalar_f8_k)
+    UA_TILED(metric_ip_k, scalar_f8_k)
+    UA_TILED(metric_l2sq_k, scalar_f8_k)
 #undef UA_TILED
     if (e != hipSuccess)
         return hip_message(e);

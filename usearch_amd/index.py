@@ -23,12 +23,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIBRARY_PATH = os.environ.get("USEARCH_AMD_LIBRARY") or os.path.join(HERE, "lib", "libusearch_amd.so")
 
 # `usearch_scalar_kind_t` / `usearch_metric_kind_t` of c/usearch.h:40-62
-SCALAR_KINDS = {"f32": 1, "f64": 2, "f16": 3, "i8": 4, "b1": 5, "bf16": 6}
+SCALAR_KINDS = {"f32": 1, "f64": 2, "f16": 3, "i8": 4, "b1": 5, "bf16": 6, "f8": 7}
 SCALAR_NAMES = {v: k for k, v in SCALAR_KINDS.items()}
 METRIC_NAMES = {1: "cos", 2: "ip", 3: "l2sq", 4: "haversine", 5: "divergence", 6: "pearson", 7: "jaccard",
                 8: "hamming", 9: "tanimoto", 10: "sorensen"}
 NUMPY_DTYPES = {"f32": np.float32, "f64": np.float64, "f16": np.float16, "i8": np.int8, "b1": np.uint8,
-                "bf16": np.uint16}  # numpy has no bfloat16: bf16 rows are handed over as their uint16 bit patterns
+                "bf16": np.uint16,  # numpy has no bfloat16: bf16 rows are handed over as their uint16 bit patterns
+                "f8": np.uint8}  # … and no 8-bit float: f8 rows travel as their e4m3 codes, and are always named (`uint8` alone reads as b1)
 
 
 def _infer_dtype(array: np.ndarray) -> str:
@@ -168,7 +169,7 @@ EXPORTED_SYMBOLS = [
     "usearch_amd_filter_from_key_range", "usearch_amd_filter_from_keys", "usearch_amd_filter_from_bits",
     "usearch_amd_filter_allowed", "usearch_amd_filter_device_bits", "usearch_amd_filter_free",
     "usearch_amd_filtered_search_many", "usearch_amd_filtered_search_many_device", "usearch_amd_filtered_exact_search_many",
-    "usearch_amd_cast",
+    "usearch_amd_cast", "usearch_amd_cast_rows",
     "usearch_amd_build", "usearch_amd_build_free", "usearch_amd_build_snapshot", "usearch_amd_build_extend", "usearch_amd_build_update",
     "usearch_amd_build_serialized_length", "usearch_amd_build_save_buffer", "usearch_amd_build_stats",
     "usearch_amd_snapshot_isolate", "usearch_amd_snapshot_compact", "usearch_amd_compact_scan_chunk",
@@ -299,6 +300,8 @@ def library() -> C.CDLL:
     L.usearch_amd_last_distances_ms.argtypes = [C.c_void_p]
     L.usearch_amd_cast.restype = C.c_int
     L.usearch_amd_cast.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.usearch_amd_cast_rows.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.c_int, err_p]
     L.usearch_amd_build.restype = C.c_void_p
     L.usearch_amd_build.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_void_p,
                                     C.POINTER(BuildConfig), C.c_int, C.c_int, err_p]
@@ -1095,10 +1098,12 @@ def exact_search(dataset: np.ndarray, queries: np.ndarray, count: int, metric: s
                  dtype: Optional[str] = None, tiled: bool = False):
     """`usearch.index.search(dataset, queries, count, exact=True)` (index.py:1608-1700) → (keys = row offsets [Q, k],
     distances [Q, k]); both matrices in the same scalar kind, rows may be strided. `tiled`: the matrix-unit kernel
-    (csrc/exact_tiled.hip) over the uploaded rows — cos / ip / l2sq over f16, bf16 and i8, cos / ip over f32 — or the bit tile
+    (csrc/exact_tiled.hip) over the uploaded rows — cos / ip / l2sq over f16, bf16, i8 and f8, cos / ip over f32 — or the bit tile
     (csrc/exact_bits.hip: hamming / tanimoto / jaccard / sorensen over b1, the wave kernel's bits), count ≤ 64, any
     other pair is refused; float distances then lie within a derived bound of the f64 distance instead of being the wave kernel's bits (f32:
-    not promised within 1e-5 of them). The default stays the bit-exact wave-per-query kernel."""
+    not promised within 1e-5 of them). The default stays the bit-exact wave-per-query kernel.
+    f8: `uint8` matrices of OCP e4m3 codes (`cast_rows` makes them), `dtype="f8"` named — a `uint8` matrix alone reads as b1. Tiled
+    exact search is ALL f8 has so far: `tiled=False` refuses it, and so do `build`, `Index.restore`, the walk and `kmeans`."""
     dataset, queries = np.asarray(dataset), np.asarray(queries)
     if dtype is None:
         dtype = _infer_dtype(dataset)
@@ -1161,12 +1166,31 @@ def device_count() -> int:
 def cast(vector: np.ndarray, from_dtype: str, to_dtype: str, ndim: int) -> Optional[np.ndarray]:
     """Host-side query cast (`usearch_amd_cast`); None when the kinds are equal."""
     vector = np.ascontiguousarray(vector)
-    nbytes = {"b1": (ndim + 7) // 8, "i8": ndim, "f16": 2 * ndim, "bf16": 2 * ndim, "f32": 4 * ndim,
+    nbytes = {"b1": (ndim + 7) // 8, "i8": ndim, "f8": ndim, "f16": 2 * ndim, "bf16": 2 * ndim, "f32": 4 * ndim,
               "f64": 8 * ndim}[to_dtype]
     out = np.zeros(nbytes, dtype=np.uint8)
     done = library().usearch_amd_cast(SCALAR_KINDS[from_dtype], SCALAR_KINDS[to_dtype], _pointer(vector), ndim,
                                       _pointer(out))
     return out if done else None
+
+
+def cast_rows(X: np.ndarray, to_dtype: str, from_dtype: Optional[str] = None) -> np.ndarray:
+    """A whole matrix cast by one kernel on the device (`usearch_amd_cast_rows`, csrc/cast_rows.hip): [N, d] rows of f32, f16, f64 or
+    bf16 (`uint16` bit patterns, `from_dtype="bf16"` named) → [N, d] `uint8` f8 codes, byte for byte what `cast` gives one vector
+    at a time. f8 is the only target so far; any other is refused."""
+    X = np.asarray(X)
+    if from_dtype is None:
+        from_dtype = _infer_dtype(X)
+    if X.ndim != 2 or X.strides[1] != X.itemsize:
+        X = np.ascontiguousarray(X).reshape(len(X), -1)
+    if to_dtype not in SCALAR_KINDS or from_dtype not in SCALAR_KINDS:
+        raise ValueError(f"Unknown scalar kind {to_dtype if to_dtype not in SCALAR_KINDS else from_dtype}")
+    out = np.zeros(X.shape, dtype=np.uint8)
+    err = C.c_char_p()
+    library().usearch_amd_cast_rows(_pointer(X), X.shape[0], X.strides[0], SCALAR_KINDS[from_dtype], X.shape[1], SCALAR_KINDS[to_dtype],
+                                    _pointer(out), out.strides[0], 0, C.byref(err))
+    _raise(err, "usearch_amd_cast_rows")
+    return out
 
 
 METRIC_KINDS = {name: kind for kind, name in METRIC_NAMES.items()}
@@ -1360,7 +1384,7 @@ def test_exact_tiled_pair(metric: str, dtype: str, wanted: int) -> bool:
     csrc/exact_plan.hpp (`exact_tiled_pair`) that `exact="tiled"` and `exact_search(…, tiled=True)` are refused by; no GPU involved."""
     metric_kind = ord({"ip": "i", "cos": "c", "l2sq": "e", "hamming": "b", "pearson": "p", "haversine": "h", "divergence": "d",
                        "jaccard": "j", "tanimoto": "t", "sorensen": "s"}[metric])  # metric_kind_t and scalar_kind_t of csrc/common.hpp
-    scalar_kind = {"b1": 1, "bf16": 4, "f64": 10, "f32": 11, "f16": 12, "i8": 23}[dtype]
+    scalar_kind = {"b1": 1, "bf16": 4, "f64": 10, "f32": 11, "f16": 12, "f8": 13, "i8": 23}[dtype]
     return bool(test_hooks().usearch_amd_test_exact_tiled_pair(metric_kind, scalar_kind, wanted))
 
 
