@@ -37,6 +37,7 @@
 #include "engine.hpp"
 #include "exact_plan.hpp"
 #include "host_util.hpp"
+#include "wide_stage.hpp"
 
 namespace usearch_amd {
 
@@ -237,23 +238,13 @@ __global__ __launch_bounds__(256) void exact_tiled_kernel(const snapshot_view_t 
 //  (`global_load_lds_dwordx4`, no staging registers, no `ds_write`) into two XOR-swizzled buffers; register epilogue
 // ---------------------------------------------------------------------------------------------------------------------
 
-constexpr int wide_blocks_k = wide_rows_k / 32; ///< 32-row blocks of a tile = accumulators of a wave
-constexpr int wide_threads_k = 512; ///< 8 waves; wave w multiplies queries [32w, 32w + 32) with the tile's 256 rows
-constexpr int wide_buffers_k = 2;   ///< staging buffers: one being multiplied, one being filled
-constexpr int wide_stage_rows_k = wide_queries_k + wide_rows_k;
-constexpr std::uint32_t wide_stage_bytes_k = wide_stage_rows_k * chunk_bytes_k;         ///< a buffer: [512][128] bytes, no padding
-constexpr int wide_fills_k = wide_stage_rows_k / 8 / (wide_threads_k / 64);              ///< fill instructions per wave per chunk: 8
+// (the staging itself — buffer shape, swizzle, a fill step — is wide_stage.hpp's, shared with the k-means assignment)
+static_assert(wide_queries_k == wide_tile_k && wide_rows_k == wide_tile_k, "the planner's tile is the one wide_stage.hpp stages");
 
 constexpr std::uint32_t wide_lds_bytes(bool lds_lists, std::uint32_t wanted) {
     return wide_buffers_k * wide_stage_bytes_k + wide_queries_k * 4 * 5 + 2 * wide_rows_k * 4 + 2 * 512 * 4 +
            (lds_lists ? wide_queries_k * wanted * 8 : 0);
 }
-
-/// Where the 16-byte piece `piece` of staged row `row` sits inside the row's 128 bytes. A `ds_read_b128` is served in groups of 16
-/// lanes — 16 different rows at one piece index — and rows 128 bytes apart fall on the same banks every second row; XOR-ing the
-/// piece index with bits 1…3 of the row spreads each group over all sixteen 16-byte bank slots (no conflict). The DMA writes lanes
-/// linearly, so the swizzle is applied to the SOURCE: lane i of a fill instruction fetches the piece that belongs in slot i.
-__device__ __forceinline__ std::uint32_t wide_swizzle(std::uint32_t row, std::uint32_t piece) { return piece ^ ((row >> 1) & 7u); }
 
 #ifdef USEARCH_AMD_EXACT_PHASES
 /// Diagnostic build (`make EXTRA=-DUSEARCH_AMD_EXACT_PHASES`): shader-clock ticks of wave 0 of every workgroup, summed — [0] multiply
@@ -268,9 +259,6 @@ __device__ unsigned long long exact_phase_ticks[8];
 #else
 #define UA_PHASE_TICK(phase)
 #endif
-
-using global_bytes_t = const __attribute__((address_space(1))) void*;
-using lds_bytes_t = __attribute__((address_space(3))) void*;
 
 /**
  *  grid = 1-D, ONE round of the chip where the batch allows (`wide_plan`): 10 000 queries = 40 query tiles = 5 per XCD × 6
@@ -401,7 +389,7 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
     //      texture unit). No branch on the data path: a row past the partition's end lies outside its tile's resource (whatever
     //      the staging cell then holds, the epilogue drops that column: `live`), bytes past a row's last 16-byte chunk re-read that
     //      chunk (ragged rows only: one subtraction on the last chunk) and meet the zeros the padded queries hold there.
-    constexpr int resource_flags = 0x00020000; // raw buffer, 32-bit data format: what the range check needs on gfx94x / gfx950
+    constexpr int resource_flags = wide_resource_flags_k;
     const std::uint32_t fill_row = wave * 8 + lane / 8; // + 64·pass
     const std::uint32_t fill_piece = wide_swizzle(fill_row, lane & 7u);
     const std::uint32_t row_stride = (std::uint32_t)ix.row_stride, query_stride = (std::uint32_t)padded_stride; // × 256 fits 31 bits (launch_wide)
@@ -432,9 +420,8 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
         std::uint8_t* stage = lds + buffer * wide_stage_bytes_k;
 #pragma unroll
         for (int pass = first_pass; pass < first_pass + 2; ++pass)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(query_resource, (lds_bytes_t)(stage + (pass * 64 + wave * 8) * chunk_bytes_k), 16,
-                                                     (int)query_offset,
-                                                     (int)__builtin_amdgcn_readfirstlane(pass * query_pass_bytes + fetch_chunk * chunk_bytes_k), 0, 0);
+            wide_fill(query_resource, stage + (pass * 64 + wave * 8) * chunk_bytes_k, query_offset,
+                      __builtin_amdgcn_readfirstlane(pass * query_pass_bytes + fetch_chunk * chunk_bytes_k));
     };
     auto fill_rows = [&](std::uint32_t buffer, int first_pass) { // two of the four row passes
         std::uint8_t* stage = lds + buffer * wide_stage_bytes_k;
@@ -447,9 +434,8 @@ __global__ __launch_bounds__(wide_threads_k) void exact_wide_kernel(const snapsh
         }
 #pragma unroll
         for (int pass = first_pass; pass < first_pass + 2; ++pass)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(row_resource, (lds_bytes_t)(stage + (wide_queries_k + pass * 64 + wave * 8) * chunk_bytes_k),
-                                                     16, (int)offset,
-                                                     (int)__builtin_amdgcn_readfirstlane(pass * row_pass_bytes + fetch_chunk * chunk_bytes_k), 0, 0);
+            wide_fill(row_resource, stage + (wide_queries_k + pass * 64 + wave * 8) * chunk_bytes_k, offset,
+                      __builtin_amdgcn_readfirstlane(pass * row_pass_bytes + fetch_chunk * chunk_bytes_k));
     };
     auto fill_tile_head_and_advance = [&]() {
         if (fetch_chunk == 0) { // this wave's 32 queries' shared bounds as they stand now (lanes 32 … 63 repeat them), same DMA

@@ -29,6 +29,13 @@
  *                 a pair to the same bits (tests/test_gpu_kmeans.py) and i8 distances are bit-identical to the wave kernel's. The
  *                 epilogue keeps ONE (distance, index) per point under (distance ↑, centroid index ↑). The centroids (k · row
  *                 bytes, a few MB) stay in L2; the points are read from HBM once per iteration.
+ *                 From 65 536 points and 1 024 centroids on (`plan_kmeans_assign`, kmeans_plan.hpp; USEARCH_AMD_KMEANS_TILE = 64 / 256
+ *                 forces either) the same pairs run on a tile of 256 points × 256 centroids per workgroup of 8 waves
+ *                 (`assign_wide_kernel`): both operands go global → LDS by LDS-DMA into the two swizzled buffers of wide_stage.hpp,
+ *                 shared with exact search's wide tile; a wave multiplies its 32 points with all 256 centroids of every tile and
+ *                 keeps one running (distance, index) per accumulator register — the sums never visit LDS — and the lanes that
+ *                 share a point fold their pairs once at the end. Same `multiply` calls in the same chunk order: the same float
+ *                 bits as the 64 tile (tests/test_gpu_kmeans_wide.py). 1M × 768 bf16, k = 1 024: 2.73 ms against 3.55 ms.
  *                 f32: a plain wave per point (f32 FMAs over 64 lanes, shuffle reduction), within the f32 tolerance.
  *                 The same kernel counts the points whose index changed (integer atomics) and writes the per-point distances;
  *    aggregate    one workgroup sums the f32 distances in f64 in a fixed tree: the same bits run after run;
@@ -55,13 +62,15 @@
 #include "device_scratch.hpp"
 #include "host_util.hpp"
 #include "kmeans.hpp"
+#include "kmeans_plan.hpp"
+#include "wide_stage.hpp"
 
 namespace usearch_amd {
 
 namespace {
 
-constexpr int tile_points_k = 64;     ///< points per workgroup
-constexpr int tile_centroids_k = 128; ///< centroids per inner tile
+constexpr int tile_points_k = kmeans_tile_points_k;       ///< points per workgroup of the 64 tile
+constexpr int tile_centroids_k = kmeans_tile_centroids_k; ///< centroids per inner tile of the 64 tile
 constexpr float float_max_k = 3.402823466e+38f;
 constexpr std::uint32_t norms_blocks_k = 65536; ///< the grid of the Σx² launches at most
 
@@ -307,6 +316,217 @@ __global__ __launch_bounds__(256) void assign_tiled_kernel(const std::uint8_t* p
     }
     if (thread < tile_points_k) // wave 0
         publish_assignment(first_point + thread, first_point + thread < count, best_i, best_d, assignments, distances, shifted, lane);
+}
+
+/**
+ *  The wide tile. grid = tiles of 256 points, 512 threads = 8 waves, one workgroup per compute unit (two staging buffers of 64 KB).
+ *  Every centroid tile of 256 rows streams past the workgroup's points; wave w multiplies points [32w, 32w + 32) with all 256
+ *  centroids of the tile: eight 32 × 32 accumulators, `multiply` in the chunk order of the 64 tile — the same float bits. A
+ *  workgroup sees every centroid: no partitions, nothing to merge between workgroups.
+ *
+ *  Staging is wide_stage.hpp's: both operands go global → LDS by LDS-DMA into two XOR-swizzled buffers of [512][128] bytes, chunk
+ *  c + 1 is requested before chunk c is multiplied, a wave waits for ITS fills and meets the others at a bare barrier. Both
+ *  matrices are k-means' own and hold whole tiles of whole chunks, zeros beyond the data (`kmeans_wide_stride`, `kmeans_wide_rows`):
+ *  every fill reads inside its allocation, no clamp, no branch. Fragment reads are inline assembly that waits for its own reads —
+ *  a read the compiler can see would wait for every fill in flight first (for all it knows the fill writes the very cell), and the
+ *  next chunk would no longer land behind this one's products; the wave's partner on the SIMD multiplies while it waits.
+ *
+ *  The epilogue never leaves the registers. Accumulator register r of a lane is point 32w + accumulator_row(r, lane), its column
+ *  the centroid residue lane & 31: a lane keeps one running (distance, index) per register and meets "its" centroids in ascending
+ *  index — blocks ascend inside a tile, tiles ascend — so the strict `<` from FLT_MAX is the reference's scan (index_plugins.hpp:
+ *  2366-2375) restricted to the lane. After the last tile the 32 lanes that share a point fold their pairs once under
+ *  (distance ↑, index ↑); a NaN never entered a pair, and a point nobody took stays (FLT_MAX, 0). Rows ≥ `count` are not published,
+ *  columns ≥ `clusters` never compared: padding cannot win.
+ */
+template <int metric_ak, int scalar_ak>
+__global__ __launch_bounds__(wide_threads_k) void assign_wide_kernel(const std::uint8_t* points, std::uint32_t count, const std::uint8_t* centroids,
+                                                                     std::uint32_t clusters, std::uint32_t stride,
+                                                                     const std::uint32_t* point_norms, const std::uint32_t* centroid_norms,
+                                                                     std::uint32_t* assignments, float* distances, std::uint32_t* shifted) {
+    using accumulator_t = typename accumulator_gt<scalar_ak>::type;
+    using u32x4_t = std::uint32_t __attribute__((ext_vector_type(4))); // a native 128-bit register operand for the assembler
+    extern __shared__ __attribute__((aligned(1024))) std::uint8_t wide_lds[]; // [2][512][128]
+
+    // (the wave's number as a scalar: the LDS targets of the fills travel in M0)
+    const std::uint32_t thread = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(thread / 64), lane = thread % 64;
+    const std::uint32_t first_point = blockIdx.x * wide_tile_k;
+    const std::uint32_t chunks = stride / chunk_bytes_k; // whole chunks: kmeans_wide_stride
+    const std::uint32_t tiles = (clusters + wide_tile_k - 1) / wide_tile_k;
+    const std::uint32_t column = accumulator_column(lane);
+
+    // ---- the points' Σa² behind the staging buffers (written here, before any fill is in flight; read by `ds_read` in assembly)
+    std::uint32_t* norms_p = reinterpret_cast<std::uint32_t*>(wide_lds + wide_buffers_k * wide_stage_bytes_k); // [256]
+    if (thread < wide_tile_k)
+        norms_p[thread] = first_point + thread < count ? point_norms[first_point + thread] : 0u;
+    __syncthreads();
+
+    // ---- per lane: the best so far of the 16 points its accumulator registers belong to
+    std::uint32_t best_i[16];
+    float best_d[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        best_d[r] = float_max_k, best_i[r] = 0;
+
+    // ---- fills: wave w brings rows 64·pass + 8w … + 8 of either operand, four passes each; lane i the piece that belongs in slot i
+    const std::uint32_t fill_row = wave * 8 + lane / 8;
+    const std::uint32_t lane_offset = fill_row * stride + wide_swizzle(fill_row, lane & 7u) * 16;
+    const std::uint32_t tile_bytes = wide_tile_k * stride, pass_bytes = 64u * stride; // < 2^31: plan_kmeans_assign
+    const __amdgpu_buffer_rsrc_t point_resource = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<std::uint8_t*>(points + (std::uint64_t)first_point * stride), 0, (int)tile_bytes, wide_resource_flags_k);
+    auto fill = [&](std::uint32_t buffer, std::uint32_t tile, std::uint32_t chunk) {
+        std::uint8_t* stage = wide_lds + buffer * wide_stage_bytes_k;
+        const __amdgpu_buffer_rsrc_t centroid_resource = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<std::uint8_t*>(centroids + (std::uint64_t)tile * tile_bytes), 0, (int)tile_bytes, wide_resource_flags_k);
+#pragma unroll
+        for (int pass = 0; pass < 4; ++pass) // the centroids first: the points of a workgroup come back from L2 after the first tile
+            wide_fill(centroid_resource, stage + (wide_tile_k + pass * 64 + wave * 8) * chunk_bytes_k, lane_offset,
+                      __builtin_amdgcn_readfirstlane(pass * pass_bytes + chunk * chunk_bytes_k));
+#pragma unroll
+        for (int pass = 0; pass < 4; ++pass)
+            wide_fill(point_resource, stage + (pass * 64 + wave * 8) * chunk_bytes_k, lane_offset,
+                      __builtin_amdgcn_readfirstlane(pass * pass_bytes + chunk * chunk_bytes_k));
+    };
+
+    // ---- fragment reads. Lane L reads row (base + (L & 31)), piece 2·step + (L >> 5), through the swizzle of that row; row bases
+    //      are multiples of 32, so the swizzled piece only depends on the lane and the step. A statement requests a point fragment
+    //      and four centroid fragments (or the other four) and waits for them: what leaves it has landed.
+    const std::uint32_t lane_swizzle = ((lane & 31u) >> 1) & 7u, lane_half = lane >> 5;
+    const std::uint32_t lds_base = (std::uint32_t)(std::uintptr_t)(lds_bytes_t)wide_lds;
+    const std::uint32_t point_fragments = lds_base + (wave * 32 + (lane & 31)) * chunk_bytes_k;
+    const std::uint32_t centroid_fragments = lds_base + (wide_tile_k + (lane & 31)) * chunk_bytes_k;
+    accumulator_t acc[wide_blocks_k];
+    static_assert(wide_blocks_k == 8 && chunk_bytes_k / 32 == 4, "multiply_chunk is written out for four steps of eight centroid blocks");
+    auto multiply_chunk = [&](std::uint32_t buffer) {
+#pragma unroll
+        for (std::uint32_t step = 0; step < 4; ++step) {
+            const std::uint32_t piece = buffer * wide_stage_bytes_k + ((2u * step + lane_half) ^ lane_swizzle) * 16u;
+            u32x4_t a, b0, b1, b2, b3;
+            asm volatile("ds_read_b128 %0, %5\n\t"
+                         "ds_read_b128 %1, %6\n\t"
+                         "ds_read_b128 %2, %6 offset:4096\n\t"
+                         "ds_read_b128 %3, %6 offset:8192\n\t"
+                         "ds_read_b128 %4, %6 offset:12288\n\t"
+                         "s_waitcnt lgkmcnt(0)"
+                         : "=&v"(a), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3)
+                         : "v"(point_fragments + piece), "v"(centroid_fragments + piece)
+                         : "memory");
+            acc[0] = multiply<scalar_ak>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b0), acc[0]);
+            acc[1] = multiply<scalar_ak>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b1), acc[1]);
+            acc[2] = multiply<scalar_ak>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b2), acc[2]);
+            acc[3] = multiply<scalar_ak>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b3), acc[3]);
+            asm volatile("ds_read_b128 %0, %4 offset:16384\n\t"
+                         "ds_read_b128 %1, %4 offset:20480\n\t"
+                         "ds_read_b128 %2, %4 offset:24576\n\t"
+                         "ds_read_b128 %3, %4 offset:28672\n\t"
+                         "s_waitcnt lgkmcnt(0)"
+                         : "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3)
+                         : "v"(centroid_fragments + piece)
+                         : "memory");
+            acc[4] = multiply<scalar_ak>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b0), acc[4]);
+            acc[5] = multiply<scalar_ak>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b1), acc[5]);
+            acc[6] = multiply<scalar_ak>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b2), acc[6]);
+            acc[7] = multiply<scalar_ak>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b3), acc[7]);
+        }
+    };
+
+    // ---- the pipeline: chunk c is multiplied out of buffer c & 1 while the DMA fills the other buffer with chunk c + 1. What a
+    //      buffer holds is read one iteration after the wait + barrier that completed it, and refilled one barrier after its last read.
+    fill(0, 0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    std::uint32_t c = 0;
+    for (std::uint32_t tile = 0; tile < tiles; ++tile) {
+#pragma unroll
+        for (int u = 0; u < wide_blocks_k; ++u)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                acc[u][r] = 0;
+        for (std::uint32_t chunk = 0; chunk < chunks; ++chunk, ++c) {
+            const bool last_of_tile = chunk + 1 == chunks;
+            // the tile's Σb² ahead of the fills: they are there when the products are, whatever is still in flight behind them
+            std::uint32_t b2[wide_blocks_k] = {};
+            if (last_of_tile) {
+#pragma unroll
+                for (int u = 0; u < wide_blocks_k; ++u) {
+                    const std::uint32_t j = tile * wide_tile_k + u * 32 + column;
+                    b2[u] = j < clusters ? centroid_norms[j] : 0u;
+                }
+            }
+            if (!last_of_tile)
+                fill((c + 1) & 1u, tile, chunk + 1);
+            else if (tile + 1 < tiles)
+                fill((c + 1) & 1u, tile + 1, 0);
+            multiply_chunk(c & 1u);
+            if (last_of_tile) {
+                // the points' Σa² by a hand-waited read, like the fragments (registers 4q … 4q + 3 ↔ points 8q + 4·(lane >> 5) + 0 … 3)
+                u32x4_t n0, n1, n2, n3;
+                asm volatile("ds_read_b128 %0, %4\n\t"
+                             "ds_read_b128 %1, %4 offset:32\n\t"
+                             "ds_read_b128 %2, %4 offset:64\n\t"
+                             "ds_read_b128 %3, %4 offset:96\n\t"
+                             "s_waitcnt lgkmcnt(0)"
+                             : "=&v"(n0), "=&v"(n1), "=&v"(n2), "=&v"(n3)
+                             : "v"(lds_base + wide_buffers_k * wide_stage_bytes_k + (wave * 32 + 4 * lane_half) * 4)
+                             : "memory");
+                const std::uint32_t a2[16] = {n0[0], n0[1], n0[2], n0[3], n1[0], n1[1], n1[2], n1[3],
+                                              n2[0], n2[1], n2[2], n2[3], n3[0], n3[1], n3[2], n3[3]};
+#pragma unroll
+                for (int u = 0; u < wide_blocks_k; ++u) {
+                    const std::uint32_t j = tile * wide_tile_k + u * 32 + column;
+                    const bool live = j < clusters;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        // (l2sq over floats: a NaN stays a NaN and fails the `<`; device_math.hpp)
+                        float distance;
+                        if constexpr (metric_ak == metric_cos_k && scalar_ak != scalar_i8_k) {
+                            // closing_distance's answers for a zero norm taken as selects around its general expression, which is
+                            // told that it sees none: its early returns are divergent branches otherwise, 128 of them in a row
+                            const float a2f = __builtin_bit_cast(float, a2[r]), b2f = __builtin_bit_cast(float, b2[u]);
+                            const bool zero_a = a2f == 0.f, zero_b = b2f == 0.f;
+                            const float a2_safe = zero_a ? 1.f : a2f, b2_safe = zero_b ? 1.f : b2f;
+                            __builtin_assume(a2_safe != 0.f && b2_safe != 0.f);
+                            const float general = closing_distance<metric_ak, scalar_ak, l2sq_nan_stays_k>(
+                                acc[u][r], __builtin_bit_cast(std::uint32_t, a2_safe), __builtin_bit_cast(std::uint32_t, b2_safe));
+                            distance = zero_a && zero_b ? 0.f : (zero_a || zero_b ? 1.f : general);
+                        } else if constexpr (metric_ak == metric_cos_k) { // i8: the same for its `ab == 0 → 0`
+                            const int ab = acc[u][r], ab_safe = ab != 0 ? ab : 1;
+                            __builtin_assume(ab_safe != 0);
+                            const float general = closing_distance<metric_ak, scalar_ak, l2sq_nan_stays_k>(ab_safe, a2[r], b2[u]);
+                            distance = ab != 0 ? general : 0.f;
+                        } else
+                            distance = closing_distance<metric_ak, scalar_ak, l2sq_nan_stays_k>(acc[u][r], a2[r], b2[u]);
+                        if (live && distance < best_d[r])
+                            best_d[r] = distance, best_i[r] = j;
+                        if constexpr (metric_ak == metric_cos_k) // one division at a time: sixteen interleaved do not fit the registers
+                            __builtin_amdgcn_sched_barrier(0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0); // block by block
+                }
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's share of the next chunk is in LDS
+            __builtin_amdgcn_s_barrier();
+        }
+    }
+
+    // ---- the 32 lanes of a half hold a point's 32 residues: fold them, then lane r of the half (r < 16) publishes register r's point
+    float mine_d = float_max_k;
+    std::uint32_t mine_i = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float d = best_d[r];
+        std::uint32_t i = best_i[r];
+#pragma unroll
+        for (int offset = 1; offset <= 16; offset <<= 1) {
+            const float other_d = __shfl_xor(d, offset, 64);
+            const std::uint32_t other_i = (std::uint32_t)__shfl_xor((int)i, offset, 64);
+            if (other_d < d || (other_d == d && other_i < i))
+                d = other_d, i = other_i;
+        }
+        if ((lane & 31u) == (std::uint32_t)r)
+            mine_d = d, mine_i = i;
+    }
+    const std::uint32_t point = first_point + wave * 32 + accumulator_row(lane & 15u, lane);
+    publish_assignment(point, (lane & 31u) < 16u && point < count, mine_i, mine_d, assignments, distances, shifted, lane);
 }
 
 /// f32 rows: a wave per point, the reference's expressions (metric_l2sq_gt / metric_cos_gt / metric_ip_gt over f32) with the
@@ -584,10 +804,12 @@ const char* refuse_kinds(scalar_kind_t kind, scalar_kind_t quantization) {
     return nullptr;
 }
 
-/// Host rows of `kind` → device rows of `quantization`, `quantized_stride` bytes apart and zero padded, slab by slab.
+/// Host rows of `kind` → device rows of `quantization`, `quantized_stride` bytes apart and zero padded, slab by slab; the matrix
+/// holds `allocated_rows` ≥ `count` rows, zeros after the data (whole tiles for the wide assignment).
 const char* quantize_rows(const std::uint8_t* rows, std::size_t count, std::size_t stride, scalar_kind_t kind,
-                          std::size_t dimensions, scalar_kind_t quantization, std::uint8_t* quantized, std::size_t quantized_stride) {
-    UA_HIP(hipMemset(quantized, 0, count * quantized_stride));
+                          std::size_t dimensions, scalar_kind_t quantization, std::uint8_t* quantized, std::size_t quantized_stride,
+                          std::size_t allocated_rows) {
+    UA_HIP(hipMemset(quantized, 0, allocated_rows * quantized_stride));
     const std::size_t row_bytes = bytes_per_vector(kind, dimensions);
     if (kind == quantization) {
         UA_HIP(hipMemcpy2D(quantized, quantized_stride, rows, stride, row_bytes, count, hipMemcpyHostToDevice));
@@ -633,10 +855,34 @@ struct assign_args_t {
     std::uint32_t* assignments;
     float* distances;
     std::uint32_t* shifted;
+    kmeans_assign_plan_t plan; ///< f16 / bf16 / i8: which tile (kmeans_plan.hpp); the matrices are laid out for it
 };
+
+/// Which tile a run over `quantization` rows takes, and with it how its two matrices are laid out: USEARCH_AMD_KMEANS_TILE = 64 /
+/// 256 forces either, anything else leaves the choice to the planner. f32 has its wave-per-point kernel and no tile.
+kmeans_assign_plan_t plan_assign(scalar_kind_t quantization, std::size_t count, std::size_t clusters, std::size_t dimensions) {
+    if (quantization == scalar_f32_k)
+        return kmeans_assign_plan_t{};
+    return plan_kmeans_assign(count, clusters, (bytes_per_vector(quantization, dimensions) + 15) / 16 * 16, env_size("USEARCH_AMD_KMEANS_TILE", 0));
+}
+
+template <int metric_ak, int scalar_ak> const char* launch_assign_wide(const assign_args_t& a) {
+    auto kernel = assign_wide_kernel<metric_ak, scalar_ak>;
+    UA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.plan.lds_bytes));
+    hipLaunchKernelGGL(kernel, dim3((std::uint32_t)a.plan.point_tiles), dim3(wide_threads_k), a.plan.lds_bytes, nullptr, a.points, a.count,
+                       a.centroids, a.clusters, a.stride, a.point_norms, a.centroid_norms, a.assignments, a.distances, a.shifted);
+    UA_HIP(hipGetLastError());
+    return nullptr;
+}
 
 template <int metric_ak> const char* launch_assign_metric(scalar_kind_t quantization, const assign_args_t& a) {
     const std::uint32_t tiles = (a.count + tile_points_k - 1) / tile_points_k;
+    if (a.plan.wide && quantization == scalar_f16_k)
+        return launch_assign_wide<metric_ak, scalar_f16_k>(a);
+    if (a.plan.wide && quantization == scalar_bf16_k)
+        return launch_assign_wide<metric_ak, scalar_bf16_k>(a);
+    if (a.plan.wide && quantization == scalar_i8_k)
+        return launch_assign_wide<metric_ak, scalar_i8_k>(a);
     if (quantization == scalar_f32_k)
         assign_f32_kernel<metric_ak><<<(a.count + 3) / 4, 256>>>(a.points, a.count, a.centroids, a.clusters, a.stride, a.dimensions,
                                                                  a.assignments, a.distances, a.shifted);
@@ -686,6 +932,13 @@ const char* launch_update_kind(metric_kind_t metric, const std::uint8_t* points,
 inline std::size_t quantized_stride_of(scalar_kind_t quantization, std::size_t dimensions) {
     return (bytes_per_vector(quantization, dimensions) + 15) / 16 * 16;
 }
+/// The two matrices as the planned tile reads them: the wide tile fills LDS with whole 128-byte chunks of whole tiles of 256 rows,
+/// so both hold them (zeros beyond the data); every other kernel of the run only ever sees the pitch.
+inline std::size_t planned_stride(const kmeans_assign_plan_t& plan, scalar_kind_t quantization, std::size_t dimensions) {
+    const std::size_t stride = quantized_stride_of(quantization, dimensions);
+    return plan.wide ? kmeans_wide_stride(stride) : stride;
+}
+inline std::size_t planned_rows(const kmeans_assign_plan_t& plan, std::size_t rows) { return plan.wide ? kmeans_wide_rows(rows) : rows; }
 
 const char* check_shape(std::size_t count, std::size_t dimensions, std::size_t clusters) {
     if (count >= (std::size_t(1) << 32))
@@ -718,7 +971,7 @@ const char* kmeans_quantize(const std::uint8_t* points, std::size_t count, std::
     device_scratch_t scratch(device);
     std::uint8_t* quantized = nullptr;
     UA_HIP(scratch.allocate(&quantized, count * quantized_stride));
-    if (const char* e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride))
+    if (const char* e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride, count))
         return e;
     UA_HIP(hipMemcpy2D(out, out_stride, quantized, quantized_stride, bytes_per_vector(quantization, dimensions), count,
                        hipMemcpyDeviceToHost));
@@ -739,22 +992,25 @@ const char* kmeans_assign(const std::uint8_t* points, std::size_t count, std::si
     if (!count)
         return nullptr;
     UA_HIP(hipSetDevice(device));
-    const std::size_t quantized_stride = quantized_stride_of(quantization, dimensions);
+    const kmeans_assign_plan_t plan = plan_assign(quantization, count, clusters, dimensions);
+    const std::size_t quantized_stride = planned_stride(plan, quantization, dimensions);
+    const std::size_t point_rows = planned_rows(plan, count), centroid_rows = planned_rows(plan, clusters);
     const std::uint32_t bytes = (std::uint32_t)bytes_per_vector(quantization, dimensions);
     device_scratch_t scratch(device);
     std::uint8_t *quantized = nullptr, *quantized_centroids = nullptr;
     std::uint32_t *point_norms = nullptr, *centroid_norms = nullptr, *indexes = nullptr, *shifted = nullptr;
     float* nearest = nullptr;
-    UA_HIP(scratch.allocate(&quantized, count * quantized_stride));
-    UA_HIP(scratch.allocate(&quantized_centroids, clusters * quantized_stride));
+    UA_HIP(scratch.allocate(&quantized, point_rows * quantized_stride));
+    UA_HIP(scratch.allocate(&quantized_centroids, centroid_rows * quantized_stride));
     UA_HIP(scratch.allocate(&point_norms, count * 4));
     UA_HIP(scratch.allocate(&centroid_norms, clusters * 4));
     UA_HIP(scratch.allocate(&indexes, count * 4));
     UA_HIP(scratch.allocate(&nearest, count * 4));
     UA_HIP(scratch.allocate(&shifted, 4));
     const char* e = nullptr;
-    if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride)) ||
-        (e = quantize_rows(centroids, clusters, centroids_stride, kind, dimensions, quantization, quantized_centroids, quantized_stride)))
+    if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride, point_rows)) ||
+        (e = quantize_rows(centroids, clusters, centroids_stride, kind, dimensions, quantization, quantized_centroids, quantized_stride,
+                           centroid_rows)))
         return e;
     if (quantization != scalar_f32_k)
         if ((e = launch_norms(quantization, quantized, count, quantized_stride, bytes, point_norms)) ||
@@ -763,7 +1019,7 @@ const char* kmeans_assign(const std::uint8_t* points, std::size_t count, std::si
     UA_HIP(hipMemset(indexes, 0xFF, count * 4));
     UA_HIP(hipMemset(shifted, 0, 4));
     const assign_args_t args{quantized, (std::uint32_t)count, quantized_centroids, (std::uint32_t)clusters, (std::uint32_t)quantized_stride,
-                             (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, shifted};
+                             (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, shifted, plan};
     if ((e = launch_assign(metric, quantization, args)))
         return e;
     std::vector<std::uint32_t> narrow(count);
@@ -794,7 +1050,9 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
         return e;
     UA_HIP(hipSetDevice(config.device)); // before any allocation
 
-    const std::size_t quantized_stride = quantized_stride_of(quantization, dimensions);
+    const kmeans_assign_plan_t plan = plan_assign(quantization, count, clusters, dimensions);
+    const std::size_t quantized_stride = planned_stride(plan, quantization, dimensions);
+    const std::size_t point_rows = planned_rows(plan, count), centroid_rows = planned_rows(plan, clusters);
     const std::uint32_t bytes = (std::uint32_t)bytes_per_vector(quantization, dimensions);
     // chunks of the stable scatter: 64 points each while a cell per (chunk, centroid) fits 256 MB, longer ones beyond
     constexpr std::uint64_t max_cells = std::uint64_t(1) << 26;
@@ -806,7 +1064,7 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
         return "The number of clusters is too large for the device";
 
     // what the f64 sums and the rest need in HBM, against what is free
-    const std::size_t needed = count * quantized_stride + clusters * quantized_stride + count * 16 + clusters * 16 +
+    const std::size_t needed = point_rows * quantized_stride + centroid_rows * quantized_stride + count * 16 + clusters * 16 +
                                chunks * clusters * 4 + clusters * dimensions * 8 +
                                (kind == quantization ? 0 : std::min<std::size_t>(count * bytes_per_vector(kind, dimensions), std::size_t(1) << 30));
     std::size_t free_bytes = 0, total_bytes = 0;
@@ -820,8 +1078,8 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
                   *cells = nullptr, *counts = nullptr, *offsets = nullptr, *members = nullptr;
     float* nearest = nullptr;
     double* sums = nullptr;
-    UA_HIP(scratch.allocate(&quantized, count * quantized_stride));
-    UA_HIP(scratch.allocate(&quantized_centroids, clusters * quantized_stride));
+    UA_HIP(scratch.allocate(&quantized, point_rows * quantized_stride));
+    UA_HIP(scratch.allocate(&quantized_centroids, centroid_rows * quantized_stride));
     UA_HIP(scratch.allocate(&point_norms, count * 4));
     UA_HIP(scratch.allocate(&centroid_norms, clusters * 4));
     UA_HIP(scratch.allocate(&indexes, count * 4));
@@ -837,9 +1095,9 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
     UA_HIP(events.create());
 
     const char* e = nullptr;
-    if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride)))
+    if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride, point_rows)))
         return e;
-    UA_HIP(hipMemset(quantized_centroids, 0, clusters * quantized_stride));
+    UA_HIP(hipMemset(quantized_centroids, 0, centroid_rows * quantized_stride));
 
     // ---- seeding, index_plugins.hpp:2308-2350, the uniqueness test as the reference has it
     std::vector<std::uint32_t> index(count, (std::uint32_t)clusters), seed_points(clusters);
@@ -874,7 +1132,7 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
     UA_HIP(hipDeviceSynchronize());
 
     const assign_args_t args{quantized, (std::uint32_t)count, quantized_centroids, (std::uint32_t)clusters, (std::uint32_t)quantized_stride,
-                             (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, scalars + 2};
+                             (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, scalars + 2, plan};
     struct {
         double aggregate;
         std::uint32_t shifted, unused;

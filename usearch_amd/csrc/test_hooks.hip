@@ -16,6 +16,7 @@
 #include "host_util.hpp"
 #include "kernels.hpp"
 #include "kmeans.hpp"
+#include "kmeans_plan.hpp"
 #include "merge_core.hpp"
 #include "placement.hpp"
 #include "search_plan.hpp"
@@ -630,6 +631,16 @@ extern "C" __attribute__((visibility("default"))) int usearch_amd_test_plan_exac
         return 0;
     }
     return 1;
+}
+
+// ---- the k-means assignment's planner (kmeans_plan.hpp) on plain values, for the route assertions of tests/test_gpu_kmeans_wide.py:
+//      which tile `count` points against `clusters` centroids take, quantised rows `stride` bytes apart. `forced_tile` < 0 = the
+//      environment (USEARCH_AMD_KMEANS_TILE), read as kmeans.hip reads it.
+extern "C" __attribute__((visibility("default"))) void usearch_amd_test_plan_kmeans_assign(uint64_t count, uint64_t clusters, uint64_t stride,
+                                                                                           int64_t forced_tile,
+                                                                                           usearch_amd::kmeans_assign_plan_t* plan) {
+    const std::uint64_t tile = forced_tile < 0 ? usearch_amd::env_size("USEARCH_AMD_KMEANS_TILE", 0) : (std::uint64_t)forced_tile;
+    *plan = usearch_amd::plan_kmeans_assign(count, clusters, stride, tile);
 }
 
 // ---- the sketch on the device and its twins piece by piece, for tests/test_gpu_sketch_records.py, tests/test_gpu_sketch_counts.py and

@@ -1308,6 +1308,8 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_exact_bits_pair.argtypes = [C.c_int, C.c_int, C.c_uint64]
         _test_hooks.usearch_amd_test_plan_exact_bits.restype = C.c_int
         _test_hooks.usearch_amd_test_plan_exact_bits.argtypes = [C.c_uint64] * 5 + [C.c_void_p, C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_plan_kmeans_assign.restype = None
+        _test_hooks.usearch_amd_test_plan_kmeans_assign.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p]
         _test_hooks.usearch_amd_test_kmeans_quantize.restype = None
         _test_hooks.usearch_amd_test_kmeans_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
@@ -1408,6 +1410,20 @@ def test_plan_exact_bits(rows: int, bytes_per_vector: int, row_stride: int, coun
     plan, err = ExactBitsPlan(), C.c_char_p()
     test_hooks().usearch_amd_test_plan_exact_bits(rows, bytes_per_vector, row_stride, count, wanted, C.byref(plan), C.byref(err))
     _raise(err, "usearch_amd_test_plan_exact_bits")
+    return plan.as_dict()
+
+
+# the k-means assignment's plan (csrc/kmeans_plan.hpp: kmeans_assign_plan_t)
+KmeansAssignPlan = _struct("KmeansAssignPlan", (C.c_uint32, "wide lds_bytes"), (C.c_uint64, "point_tiles centroid_tiles"))
+
+
+def test_plan_kmeans_assign(count: int, clusters: int, stride: int, forced_tile: Optional[int] = None) -> dict:
+    """The k-means assignment's planner (csrc/kmeans_plan.hpp) on plain values, no GPU involved: which tile `count` points against
+    `clusters` centroids take — the 64 × 128 register-staged one or the 256 × 256 LDS-DMA one — for f16 / bf16 / i8 rows `stride`
+    bytes apart (whole 16-byte pieces). `forced_tile` replaces USEARCH_AMD_KMEANS_TILE; None reads it as `kmeans` does.
+    → the fields of `KmeansAssignPlan` as a dict."""
+    plan = KmeansAssignPlan()
+    test_hooks().usearch_amd_test_plan_kmeans_assign(count, clusters, stride, -1 if forced_tile is None else int(forced_tile), C.byref(plan))
     return plan.as_dict()
 
 
