@@ -6,6 +6,12 @@ input (scripts/kmeans_reference_driver.cpp, compiled outside the repository; `--
 fewer points / iterations, its work being proportional to both, and the line says so).
 
     python scripts/kmeans_bench.py --n 1000000 --dim 768 --k 1024 --iterations 10
+
+The f32 leg (profiles/r17_kmeans_f32/): `--dtype f32`, once with USEARCH_AMD_KMEANS_TILE=1 (the wave-per-point kernel alone, what
+every f32 run took before the screened tile) and once with =64 (the screened tile), three runs each, `assign_ms` set side by side:
+
+    USEARCH_AMD_KMEANS_TILE=1  python scripts/kmeans_bench.py --n 65536 --k 1024 --iterations 3 --dtype f32
+    USEARCH_AMD_KMEANS_TILE=64 python scripts/kmeans_bench.py --n 65536 --k 1024 --iterations 3 --dtype f32
 """
 import argparse
 import json

@@ -36,7 +36,13 @@
  *                 keeps one running (distance, index) per accumulator register — the sums never visit LDS — and the lanes that
  *                 share a point fold their pairs once at the end. Same `multiply` calls in the same chunk order: the same float
  *                 bits as the 64 tile (tests/test_gpu_kmeans_wide.py). 1M × 768 bf16, k = 1 024: 2.73 ms against 3.55 ms.
- *                 f32: a plain wave per point (f32 FMAs over 64 lanes, shuffle reduction), within the f32 tolerance.
+ *                 f32: the bits of a plain wave per point (`assign_f32_kernel`: f32 FMAs over 64 lanes, shuffle reduction, within the
+ *                 f32 tolerance) — below 128 centroids by that kernel alone, from there on (`plan_kmeans_assign_f32`;
+ *                 USEARCH_AMD_KMEANS_TILE = 64 / 1 forces either) by `assign_screened_kernel`: the 64 tile over
+ *                 `v_mfma_f32_32x32x2_f32` only SCREENS — a score and a derived error per pair, up to four contenders per point in
+ *                 registers — and the contenders are re-measured by the wave kernel's own device function (`wave_distance_f32`);
+ *                 points with more contenders, or with a Σx² the derivation does not cover, go to the wave kernel through a list.
+ *                 1M × 768, k = 1 024: 17.2 ms against 517 ms (profiles/r17_kmeans_f32/).
  *                 The same kernel counts the points whose index changed (integer atomics) and writes the per-point distances;
  *    aggregate    one workgroup sums the f32 distances in f64 in a fixed tree: the same bits run after run;
  *    update       assignments → per-(chunk of points, centroid) counts → exclusive scans → a STABLE scatter of point ids, so every
@@ -529,70 +535,352 @@ __global__ __launch_bounds__(wide_threads_k) void assign_wide_kernel(const std::
     publish_assignment(point, (lane & 31u) < 16u && point < count, mine_i, mine_d, assignments, distances, shifted, lane);
 }
 
-/// f32 rows: a wave per point, the reference's expressions (metric_l2sq_gt / metric_cos_gt / metric_ip_gt over f32) with the
-/// dimensions dealt over the lanes.
+/// The f32 distance of one (point, centroid) pair as a whole wave measures it — the reference's expressions (metric_l2sq_gt /
+/// metric_cos_gt / metric_ip_gt over f32) with the dimensions dealt over the lanes, a lane's fmaf chain in ascending dimension, six
+/// shuffle-adds. `wave_square_f32` is the point's Σa² for cos, summed the same way. Every lane returns the result. Both f32
+/// assignment kernels call these two and nothing else for a distance that is published: one set of bits.
+__device__ __forceinline__ float wave_square_f32(const float* a, std::uint32_t dimensions, std::uint32_t lane) {
+    float a2 = 0.f;
+    for (std::uint32_t i = lane; i < dimensions; i += 64)
+        a2 = __builtin_fmaf(a[i], a[i], a2);
+#pragma unroll
+    for (int offset = 32; offset >= 1; offset >>= 1)
+        a2 += __shfl_xor(a2, offset, 64);
+    return a2;
+}
+template <int metric_ak>
+__device__ __forceinline__ float wave_distance_f32(const float* a, float a2, const float* b, std::uint32_t dimensions, std::uint32_t lane) {
+    float x = 0.f, b2 = 0.f;
+    for (std::uint32_t i = lane; i < dimensions; i += 64) {
+        const float ai = a[i], bi = b[i];
+        if constexpr (metric_ak == metric_l2sq_k) {
+            const float difference = ai - bi;
+            x = __builtin_fmaf(difference, difference, x);
+        } else {
+            x = __builtin_fmaf(ai, bi, x);
+            if constexpr (metric_ak == metric_cos_k)
+                b2 = __builtin_fmaf(bi, bi, b2);
+        }
+    }
+#pragma unroll
+    for (int offset = 32; offset >= 1; offset >>= 1) {
+        x += __shfl_xor(x, offset, 64);
+        b2 += __shfl_xor(b2, offset, 64);
+    }
+    if constexpr (metric_ak == metric_cos_k) {
+        if (a2 == 0.f && b2 == 0.f)
+            return 0.f;
+        if (a2 == 0.f || b2 == 0.f)
+            return 1.f;
+        return 1.f - x / (__builtin_sqrtf(a2) * __builtin_sqrtf(b2));
+    } else if constexpr (metric_ak == metric_ip_k) {
+        return 1.f - x;
+    } else {
+        return x;
+    }
+}
+
+/// f32 rows: a wave per point, every centroid in ascending order. `list` null: wave s takes point s, and the grid holds a wave per
+/// point. `list` set (the points the screened tile handed over): wave s takes point list[s] for s < *list_count, grid-stride.
 template <int metric_ak>
 __global__ __launch_bounds__(256) void assign_f32_kernel(const std::uint8_t* points, std::uint32_t count, const std::uint8_t* centroids,
                                                          std::uint32_t clusters, std::uint32_t stride, std::uint32_t dimensions,
-                                                         std::uint32_t* assignments, float* distances, std::uint32_t* shifted) {
+                                                         std::uint32_t* assignments, float* distances, std::uint32_t* shifted,
+                                                         const std::uint32_t* list, const std::uint32_t* list_count) {
     const std::uint32_t lane = threadIdx.x % 64;
-    const std::uint32_t point = blockIdx.x * 4u + threadIdx.x / 64;
-    const bool inside = point < count;
-    const float* a = reinterpret_cast<const float*>(points + (std::uint64_t)(inside ? point : 0u) * stride);
-    float a2 = 0.f;
-    if constexpr (metric_ak == metric_cos_k) {
-        for (std::uint32_t i = lane; i < dimensions; i += 64)
-            a2 = __builtin_fmaf(a[i], a[i], a2);
-#pragma unroll
-        for (int offset = 32; offset >= 1; offset >>= 1)
-            a2 += __shfl_xor(a2, offset, 64);
+    const std::uint32_t total = list ? *list_count : count;
+    for (std::uint32_t slot = blockIdx.x * 4u + threadIdx.x / 64; slot < total; slot += gridDim.x * 4u) {
+        const std::uint32_t point = list ? list[slot] : slot;
+        const float* a = reinterpret_cast<const float*>(points + (std::uint64_t)point * stride);
+        const float a2 = metric_ak == metric_cos_k ? wave_square_f32(a, dimensions, lane) : 0.f;
+        float best_d = float_max_k;
+        std::uint32_t best_i = 0;
+        for (std::uint32_t c = 0; c < clusters; ++c) {
+            const float distance =
+                wave_distance_f32<metric_ak>(a, a2, reinterpret_cast<const float*>(centroids + (std::uint64_t)c * stride), dimensions, lane);
+            if (distance < best_d)
+                best_d = distance, best_i = c;
+        }
+        // one lane per wave publishes and counts its mover
+        if (lane == 0) {
+            const bool moved = assignments[point] != best_i;
+            assignments[point] = best_i;
+            distances[point] = best_d;
+            if (moved)
+                atomicAdd(shifted, 1u);
+        }
     }
-    float best_d = float_max_k;
-    std::uint32_t best_i = 0;
-    for (std::uint32_t c = 0; c < clusters; ++c) {
-        const float* b = reinterpret_cast<const float*>(centroids + (std::uint64_t)c * stride);
-        float x = 0.f, b2 = 0.f;
-        for (std::uint32_t i = lane; i < dimensions; i += 64) {
-            const float ai = a[i], bi = b[i];
-            if constexpr (metric_ak == metric_l2sq_k) {
-                const float difference = ai - bi;
-                x = __builtin_fmaf(difference, difference, x);
-            } else {
-                x = __builtin_fmaf(ai, bi, x);
-                if constexpr (metric_ak == metric_cos_k)
-                    b2 = __builtin_fmaf(bi, bi, b2);
+}
+
+/**
+ *  f32 rows on the matrix units, with the wave kernel's bits. The 64 tile's geometry and staging (64 points per workgroup, centroid
+ *  tiles of 128 streamed past them, `multiply_staged_chunk<scalar_f32_k>`); what differs is what a sum is used for. The matrix unit
+ *  adds in another order than `wave_distance_f32`, so its sums only SCREEN: per (point i, centroid j) a score s and an error e with
+ *      | s − (d − cᵢ)·fᵢ | ≤ e       d = the wave kernel's distance, cᵢ and fᵢ > 0 the same for every centroid of the point
+ *  (DESIGN.md §9 derives e; g = 2·(dimensions + 16)·2⁻²⁴, A = √Σa², B = √Σb² from `launch_row_norms<scalar_f32_k>`):
+ *      l2sq  s = Σb² − 2Σab        e = g·(A + B)²
+ *      ip    s = −Σab              e = g·A·B + 2⁻²³
+ *      cos   s = −Σab / √Σb²       e = g·A            (Σb² = 0: s = 0, which is (1 − 1)·A to the bit)
+ *  A centroid can be the wave kernel's answer only if s − e ≤ min over all centroids of (s + e): whoever fails that is farther than
+ *  the holder of the minimum in the wave kernel's own arithmetic. Thread (point i, quarter q) scans centroids [32q, 32q + 32) of every
+ *  tile, as the 64 tile's epilogue does, and keeps in registers the running bound min (s + e) and up to four contenders (s − e, j)
+ *  at or below it; a lower bound prunes the set when it is full. After the last tile the four quarters of a point fold their sets under the
+ *  lowest bound, and wave w re-measures the contenders of points [16w, 16w + 16) with `wave_distance_f32` — the lowest
+ *  (distance ↑, index ↑) from FLT_MAX with strict `<`, the scan of index_plugins.hpp:2366-2375 restricted to the only centroids that
+ *  can win it.
+ *
+ *  Handed to `assign_f32_kernel` through `overflow_list` (an append by an integer atomic) instead: a point with more than four
+ *  contenders (in a quarter at any time, or after the fold), and a point that met a Σx² outside [2⁻⁶⁰, 2⁶⁰] other than 0 — its own or
+ *  any centroid's; a NaN or an infinity anywhere in a row makes its Σx² one — because the derivation of e assumes sums that neither
+ *  overflow nor lose bits to underflow; under cos also a point with Σa² = 0 (fᵢ = A). `contenders` (tests only, or null): per point
+ *  the number re-measured, 0 for a point handed over.
+ */
+constexpr int screen_slots_k = 4;
+constexpr float screen_least_square_k = 0x1p-60f, screen_most_square_k = 0x1p+60f;
+
+__device__ __forceinline__ bool screen_square_out_of_band(float x2) {
+    return !(x2 >= screen_least_square_k && x2 <= screen_most_square_k) && x2 != 0.f; // a NaN is out of band
+}
+
+template <int metric_ak>
+__global__ __launch_bounds__(256) void assign_screened_kernel(const std::uint8_t* points, std::uint32_t count, const std::uint8_t* centroids,
+                                                              std::uint32_t clusters, std::uint32_t stride, std::uint32_t dimensions,
+                                                              const std::uint32_t* point_norms, const std::uint32_t* centroid_norms,
+                                                              std::uint32_t* assignments, float* distances, std::uint32_t* shifted,
+                                                              std::uint32_t* overflow_list, std::uint32_t* overflow_count,
+                                                              std::uint32_t* contenders) {
+    constexpr int scalar_ak = scalar_f32_k;
+    __shared__ __attribute__((aligned(16))) std::uint8_t lds[staged_tile_bytes(tile_points_k, tile_centroids_k)];
+    __shared__ float squares_c[tile_centroids_k]; // Σb² of the tile's centroids, and their roots
+    __shared__ float roots_c[tile_centroids_k];
+    __shared__ std::uint32_t out_of_band;         // some centroid's Σb² was: nothing of this workgroup is decided here
+    __shared__ std::uint32_t final_count[tile_points_k];
+    __shared__ std::uint32_t final_index[tile_points_k][screen_slots_k];
+    std::uint8_t* stage_p = lds;                               // [64][pitch]
+    std::uint8_t* stage_c = stage_p + tile_points_k * pitch_k; // [128][pitch]
+    float* tile_s = reinterpret_cast<float*>(lds);             // [64][129], aliases the staging area after the products
+    static_assert(sizeof(lds) >= 256 * (2 * screen_slots_k + 2) * 4, "the quarters' sets are folded through the staging area");
+
+    const std::uint32_t thread = threadIdx.x, wave = thread / 64, lane = thread % 64;
+    const std::uint32_t first_point = blockIdx.x * tile_points_k;
+    const std::uint32_t chunks = (stride + chunk_bytes_k - 1) / chunk_bytes_k;
+    const float g = 2.f * (float)(dimensions + 16) * 0x1p-24f;
+
+    // ---- thread (point i = thread % 64, quarter = thread / 64): the point's part of e, its running bound and its contenders
+    const std::uint32_t scan_point = first_point + thread % tile_points_k;
+    const float a2 = scan_point < count ? __builtin_bit_cast(float, point_norms[scan_point]) : 0.f;
+    const float root_a = __builtin_sqrtf(a2);
+    bool handed_over = screen_square_out_of_band(a2) || (metric_ak == metric_cos_k && a2 == 0.f);
+    float bound = __builtin_inff();
+    float low[screen_slots_k];
+    std::uint32_t index[screen_slots_k];
+    std::uint32_t held = 0;
+#pragma unroll
+    for (int s = 0; s < screen_slots_k; ++s)
+        low[s] = 0.f, index[s] = 0;
+    if (thread == 0)
+        out_of_band = 0;
+    __syncthreads();
+    // drops what the bound has left behind, keeping the order
+    auto prune = [&]() {
+        std::uint32_t kept = 0;
+#pragma unroll
+        for (int s = 0; s < screen_slots_k; ++s) {
+            const bool stays = (std::uint32_t)s < held && low[s] <= bound;
+            const float l = low[s];
+            const std::uint32_t j = index[s];
+#pragma unroll
+            for (int target = 0; target <= s; ++target)
+                if (stays && kept == (std::uint32_t)target)
+                    low[target] = l, index[target] = j;
+            kept += stays ? 1u : 0u;
+        }
+        held = kept;
+    };
+    auto offer = [&](float s, float e, std::uint32_t j) {
+        const float upper = s + e, lower = s - e;
+        if (upper < bound)
+            bound = upper;
+        if (lower <= bound) {
+            if (held == screen_slots_k)
+                prune();
+            if (held == screen_slots_k)
+                handed_over = true;
+            else {
+#pragma unroll
+                for (int slot = 0; slot < screen_slots_k; ++slot)
+                    if (held == (std::uint32_t)slot)
+                        low[slot] = lower, index[slot] = j;
+                ++held;
             }
         }
+    };
+
+    // ---- staging: the 64 tile's (assign_tiled_kernel), next step's rows requested before this step's products
+    const std::uint32_t segment = thread % 8;
+    uint4 fetched[(tile_points_k + tile_centroids_k) / 32];
+    auto fetch = [&](std::uint32_t tile, std::uint32_t chunk) {
+        const std::uint32_t byte = chunk * chunk_bytes_k + segment * 16;
 #pragma unroll
-        for (int offset = 32; offset >= 1; offset >>= 1) {
-            x += __shfl_xor(x, offset, 64);
-            b2 += __shfl_xor(b2, offset, 64);
+        for (std::uint32_t pass = 0; pass < tile_points_k / 32; ++pass) {
+            const std::uint32_t i = pass * 32 + thread / 8;
+            uint4 value = {0u, 0u, 0u, 0u};
+            if (first_point + i < count && byte < stride)
+                value = *reinterpret_cast<const uint4*>(points + (std::uint64_t)(first_point + i) * stride + byte);
+            fetched[pass] = value;
         }
-        float distance;
-        if constexpr (metric_ak == metric_cos_k) {
-            if (a2 == 0.f && b2 == 0.f)
-                distance = 0.f;
-            else if (a2 == 0.f || b2 == 0.f)
-                distance = 1.f;
-            else
-                distance = 1.f - x / (__builtin_sqrtf(a2) * __builtin_sqrtf(b2));
-        } else if constexpr (metric_ak == metric_ip_k) {
-            distance = 1.f - x;
-        } else {
-            distance = x;
+#pragma unroll
+        for (std::uint32_t pass = 0; pass < tile_centroids_k / 32; ++pass) {
+            const std::uint32_t j = pass * 32 + thread / 8;
+            uint4 value = {0u, 0u, 0u, 0u};
+            if (tile + j < clusters && byte < stride)
+                value = *reinterpret_cast<const uint4*>(centroids + (std::uint64_t)(tile + j) * stride + byte);
+            fetched[tile_points_k / 32 + pass] = value;
         }
-        if (distance < best_d)
-            best_d = distance, best_i = c;
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (std::uint32_t pass = 0; pass < tile_points_k / 32; ++pass)
+            *reinterpret_cast<uint4*>(stage_p + (pass * 32 + thread / 8) * pitch_k + segment * 16) = fetched[pass];
+#pragma unroll
+        for (std::uint32_t pass = 0; pass < tile_centroids_k / 32; ++pass)
+            *reinterpret_cast<uint4*>(stage_c + (pass * 32 + thread / 8) * pitch_k + segment * 16) = fetched[tile_points_k / 32 + pass];
+    };
+    fetch(0, 0);
+
+    for (std::uint32_t tile = 0; tile < clusters; tile += tile_centroids_k) {
+        f32x16_t acc[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                acc[t][r] = 0;
+        if (thread < tile_centroids_k) { // read after the chunks' barriers; written again after the scan's
+            const float b2 = tile + thread < clusters ? __builtin_bit_cast(float, centroid_norms[tile + thread]) : 0.f;
+            squares_c[thread] = b2, roots_c[thread] = __builtin_sqrtf(b2);
+            if (screen_square_out_of_band(b2))
+                out_of_band = 1;
+        }
+        for (std::uint32_t chunk = 0; chunk < chunks; ++chunk) {
+            stash();
+            __syncthreads();
+            if (chunk + 1 < chunks)
+                fetch(tile, chunk + 1);
+            else if (tile + tile_centroids_k < clusters)
+                fetch(tile + tile_centroids_k, 0);
+            multiply_staged_chunk<scalar_ak>(stage_p, stage_c, wave, lane, acc);
+            __syncthreads();
+        }
+
+        // ---- scores of the tile into LDS (the staging area is free now): S[point][centroid of the tile]
+        {
+            const std::uint32_t j = wave * 32 + accumulator_column(lane);
+            const float b2 = squares_c[j], root_b = roots_c[j];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const std::uint32_t i = t * 32 + accumulator_row(r, lane);
+                    float score;
+                    if constexpr (metric_ak == metric_l2sq_k)
+                        score = b2 - 2.f * acc[t][r];
+                    else if constexpr (metric_ak == metric_ip_k)
+                        score = -acc[t][r];
+                    else
+                        score = b2 == 0.f ? 0.f : -acc[t][r] / root_b;
+                    tile_s[i * (tile_centroids_k + 1) + j] = score;
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- thread (point i, quarter q) offers centroids [32q, 32q + 32) of the tile to its set, in ascending order
+        {
+            const std::uint32_t i = thread % tile_points_k, first = (thread / tile_points_k) * (tile_centroids_k / 4);
+            const std::uint32_t live = tile + first < clusters ? min((std::uint32_t)(tile_centroids_k / 4), clusters - tile - first) : 0u;
+            for (std::uint32_t s = 0; s < live; ++s) {
+                const float score = tile_s[i * (tile_centroids_k + 1) + first + s];
+                float e;
+                if constexpr (metric_ak == metric_l2sq_k) {
+                    const float both = root_a + roots_c[first + s];
+                    e = g * both * both;
+                } else if constexpr (metric_ak == metric_ip_k)
+                    e = __builtin_fmaf(g * root_a, roots_c[first + s], 0x1p-23f);
+                else
+                    e = g * root_a;
+                offer(score, e, tile + first + s);
+            }
+        }
+        __syncthreads(); // the tile's scores are consumed: the area becomes staging again, the norms the next tile's
     }
-    // one lane per wave publishes; the four leaders of a workgroup count their movers one by one
-    bool moved = false;
-    if (inside && lane == 0) {
-        moved = assignments[point] != best_i;
-        assignments[point] = best_i;
-        distances[point] = best_d;
+
+    // ---- the four quarters of a point fold their sets through LDS: [256] bounds, counts (all ones: handed over), then the slots
+    float* fold_bound = reinterpret_cast<float*>(lds);
+    std::uint32_t* fold_held = reinterpret_cast<std::uint32_t*>(lds) + 256;
+    float* fold_low = reinterpret_cast<float*>(lds) + 512;                          // [256][slots]
+    std::uint32_t* fold_index = reinterpret_cast<std::uint32_t*>(lds) + 512 + 256 * screen_slots_k;
+    fold_bound[thread] = bound;
+    fold_held[thread] = handed_over ? 0xFFFFFFFFu : held;
+#pragma unroll
+    for (int s = 0; s < screen_slots_k; ++s)
+        fold_low[thread * screen_slots_k + s] = low[s], fold_index[thread * screen_slots_k + s] = index[s];
+    __syncthreads();
+    if (thread < tile_points_k) {
+        float lowest = __builtin_inff();
+        bool over = out_of_band != 0;
+#pragma unroll
+        for (int quarter = 0; quarter < 4; ++quarter) {
+            lowest = fminf(lowest, fold_bound[quarter * tile_points_k + thread]);
+            over = over || fold_held[quarter * tile_points_k + thread] == 0xFFFFFFFFu;
+        }
+        std::uint32_t kept = 0;
+        if (!over)
+            for (int quarter = 0; quarter < 4; ++quarter) {
+                const std::uint32_t from = quarter * tile_points_k + thread;
+                for (std::uint32_t s = 0; s < fold_held[from]; ++s)
+                    if (fold_low[from * screen_slots_k + s] <= lowest) {
+                        if (kept < screen_slots_k)
+                            final_index[thread][kept] = fold_index[from * screen_slots_k + s];
+                        ++kept;
+                    }
+            }
+        over = over || kept == 0 || kept > screen_slots_k;
+        const bool inside = first_point + thread < count;
+        final_count[thread] = inside && !over ? kept : 0u;
+        if (inside && over)
+            overflow_list[atomicAdd(overflow_count, 1u)] = first_point + thread;
+        if (inside && contenders)
+            contenders[first_point + thread] = over ? 0u : kept;
     }
-    if (moved)
-        atomicAdd(shifted, 1u);
+    __syncthreads();
+
+    // ---- closing: wave w re-measures the contenders of points [16w, 16w + 16), one after the other, in the wave kernel's arithmetic
+    std::uint32_t movers = 0;
+    for (std::uint32_t i = wave * (tile_points_k / 4); i < (wave + 1) * (tile_points_k / 4); ++i) {
+        const std::uint32_t wanted = final_count[i]; // the same for the whole wave
+        if (!wanted)
+            continue;
+        const std::uint32_t point = first_point + i;
+        const float* a = reinterpret_cast<const float*>(points + (std::uint64_t)point * stride);
+        const float wave_a2 = metric_ak == metric_cos_k ? wave_square_f32(a, dimensions, lane) : 0.f;
+        float best_d = float_max_k;
+        std::uint32_t best_i = 0;
+        for (std::uint32_t s = 0; s < wanted; ++s) {
+            const std::uint32_t c = final_index[i][s];
+            const float distance =
+                wave_distance_f32<metric_ak>(a, wave_a2, reinterpret_cast<const float*>(centroids + (std::uint64_t)c * stride), dimensions, lane);
+            // the ascending scan's winner whatever the order the set is held in: the lowest index among equals, nothing at FLT_MAX
+            if (distance < best_d || (distance == best_d && distance < float_max_k && c < best_i))
+                best_d = distance, best_i = c;
+        }
+        if (lane == 0) {
+            movers += assignments[point] != best_i ? 1u : 0u;
+            assignments[point] = best_i;
+            distances[point] = best_d;
+        }
+    }
+    if (movers)
+        atomicAdd(shifted, movers);
 }
 
 /// Σ of the f32 distances in f64, a fixed tree: thread t adds distances t, t + 1024, … in that order, then the 1 024 partial sums
@@ -843,6 +1131,8 @@ const char* launch_norms(scalar_kind_t quantization, const std::uint8_t* rows, s
         UA_HIP(launch_row_norms<scalar_bf16_k>(rows, count, stride, bytes, norms, norms_blocks_k, nullptr));
     else if (quantization == scalar_i8_k)
         UA_HIP(launch_row_norms<scalar_i8_k>(rows, count, stride, bytes, norms, norms_blocks_k, nullptr));
+    else if (quantization == scalar_f32_k) // what the screened tile measures its scores and their error by
+        UA_HIP(launch_row_norms<scalar_f32_k>(rows, count, stride, bytes, norms, norms_blocks_k, nullptr));
     return nullptr;
 }
 
@@ -856,15 +1146,30 @@ struct assign_args_t {
     float* distances;
     std::uint32_t* shifted;
     kmeans_assign_plan_t plan; ///< f16 / bf16 / i8: which tile (kmeans_plan.hpp); the matrices are laid out for it
+    // f32 on the screened tile (`plan_kmeans_assign_f32`): the points it hands to the wave kernel (`count` cells) and how many they
+    // are — zero before every launch —, and for the test hook the contenders re-measured per point. Null: the wave kernel alone.
+    std::uint32_t* overflow_list = nullptr;
+    std::uint32_t* overflow_count = nullptr;
+    std::uint32_t* contenders = nullptr;
 };
 
 /// Which tile a run over `quantization` rows takes, and with it how its two matrices are laid out: USEARCH_AMD_KMEANS_TILE = 64 /
-/// 256 forces either, anything else leaves the choice to the planner. f32 has its wave-per-point kernel and no tile.
+/// 256 forces either, anything else leaves the choice to the planner. f32 rows keep the plain layout whichever kernel takes them
+/// (`screened_assign`).
 kmeans_assign_plan_t plan_assign(scalar_kind_t quantization, std::size_t count, std::size_t clusters, std::size_t dimensions) {
     if (quantization == scalar_f32_k)
         return kmeans_assign_plan_t{};
     return plan_kmeans_assign(count, clusters, (bytes_per_vector(quantization, dimensions) + 15) / 16 * 16, env_size("USEARCH_AMD_KMEANS_TILE", 0));
 }
+
+/// f32 rows: the screened tile or the wave kernel alone (kmeans_plan.hpp; USEARCH_AMD_KMEANS_TILE = 64 / 1 forces either).
+bool screened_assign(scalar_kind_t quantization, std::size_t count, std::size_t clusters) {
+    return quantization == scalar_f32_k && plan_kmeans_assign_f32(count, clusters, env_size("USEARCH_AMD_KMEANS_TILE", 0));
+}
+
+/// The grid of the wave kernel's second launch, over the points the screen handed over: enough waves to fill the chip, each taking
+/// its share of the list; with an empty list every wave leaves at once.
+constexpr std::uint32_t overflow_blocks_k = 2048;
 
 template <int metric_ak, int scalar_ak> const char* launch_assign_wide(const assign_args_t& a) {
     auto kernel = assign_wide_kernel<metric_ak, scalar_ak>;
@@ -883,9 +1188,17 @@ template <int metric_ak> const char* launch_assign_metric(scalar_kind_t quantiza
         return launch_assign_wide<metric_ak, scalar_bf16_k>(a);
     if (a.plan.wide && quantization == scalar_i8_k)
         return launch_assign_wide<metric_ak, scalar_i8_k>(a);
-    if (quantization == scalar_f32_k)
+    if (quantization == scalar_f32_k && a.overflow_list) {
+        assign_screened_kernel<metric_ak><<<tiles, 256>>>(a.points, a.count, a.centroids, a.clusters, a.stride, a.dimensions, a.point_norms,
+                                                          a.centroid_norms, a.assignments, a.distances, a.shifted, a.overflow_list,
+                                                          a.overflow_count, a.contenders);
+        UA_HIP(hipGetLastError());
+        assign_f32_kernel<metric_ak><<<std::min(overflow_blocks_k, (a.count + 3) / 4), 256>>>(
+            a.points, a.count, a.centroids, a.clusters, a.stride, a.dimensions, a.assignments, a.distances, a.shifted, a.overflow_list,
+            a.overflow_count);
+    } else if (quantization == scalar_f32_k)
         assign_f32_kernel<metric_ak><<<(a.count + 3) / 4, 256>>>(a.points, a.count, a.centroids, a.clusters, a.stride, a.dimensions,
-                                                                 a.assignments, a.distances, a.shifted);
+                                                                 a.assignments, a.distances, a.shifted, nullptr, nullptr);
     else if (quantization == scalar_f16_k)
         assign_tiled_kernel<metric_ak, scalar_f16_k><<<tiles, 256>>>(a.points, a.count, a.centroids, a.clusters, a.stride, a.point_norms,
                                                                      a.centroid_norms, a.assignments, a.distances, a.shifted);
@@ -978,9 +1291,13 @@ const char* kmeans_quantize(const std::uint8_t* points, std::size_t count, std::
     return nullptr;
 }
 
-const char* kmeans_assign(const std::uint8_t* points, std::size_t count, std::size_t stride, const std::uint8_t* centroids,
-                          std::size_t clusters, std::size_t centroids_stride, scalar_kind_t kind, std::size_t dimensions,
-                          metric_kind_t metric, scalar_kind_t quantization, int device, std::uint64_t* assignments, float* distances) {
+namespace {
+
+/// `kmeans_assign`, and `kmeans_screen` with `contenders` set: f32 rows on the screened tile whatever the planner would choose.
+const char* assign_once(const std::uint8_t* points, std::size_t count, std::size_t stride, const std::uint8_t* centroids,
+                        std::size_t clusters, std::size_t centroids_stride, scalar_kind_t kind, std::size_t dimensions,
+                        metric_kind_t metric, scalar_kind_t quantization, int device, std::uint64_t* assignments, float* distances,
+                        std::uint32_t* contenders) {
     if (const char* e = refuse_kinds(kind, quantization))
         return e;
     if (const char* e = metric_supported(metric))
@@ -993,12 +1310,14 @@ const char* kmeans_assign(const std::uint8_t* points, std::size_t count, std::si
         return nullptr;
     UA_HIP(hipSetDevice(device));
     const kmeans_assign_plan_t plan = plan_assign(quantization, count, clusters, dimensions);
+    const bool screened = contenders || screened_assign(quantization, count, clusters);
     const std::size_t quantized_stride = planned_stride(plan, quantization, dimensions);
     const std::size_t point_rows = planned_rows(plan, count), centroid_rows = planned_rows(plan, clusters);
     const std::uint32_t bytes = (std::uint32_t)bytes_per_vector(quantization, dimensions);
     device_scratch_t scratch(device);
     std::uint8_t *quantized = nullptr, *quantized_centroids = nullptr;
-    std::uint32_t *point_norms = nullptr, *centroid_norms = nullptr, *indexes = nullptr, *shifted = nullptr;
+    std::uint32_t *point_norms = nullptr, *centroid_norms = nullptr, *indexes = nullptr, *shifted = nullptr, *overflow_list = nullptr,
+                  *contenders_device = nullptr;
     float* nearest = nullptr;
     UA_HIP(scratch.allocate(&quantized, point_rows * quantized_stride));
     UA_HIP(scratch.allocate(&quantized_centroids, centroid_rows * quantized_stride));
@@ -1006,28 +1325,54 @@ const char* kmeans_assign(const std::uint8_t* points, std::size_t count, std::si
     UA_HIP(scratch.allocate(&centroid_norms, clusters * 4));
     UA_HIP(scratch.allocate(&indexes, count * 4));
     UA_HIP(scratch.allocate(&nearest, count * 4));
-    UA_HIP(scratch.allocate(&shifted, 4));
+    UA_HIP(scratch.allocate(&shifted, 8)); // and the count of points the screen hands over
+    if (screened)
+        UA_HIP(scratch.allocate(&overflow_list, count * 4));
+    if (contenders)
+        UA_HIP(scratch.allocate(&contenders_device, count * 4));
     const char* e = nullptr;
     if ((e = quantize_rows(points, count, stride, kind, dimensions, quantization, quantized, quantized_stride, point_rows)) ||
         (e = quantize_rows(centroids, clusters, centroids_stride, kind, dimensions, quantization, quantized_centroids, quantized_stride,
                            centroid_rows)))
         return e;
-    if (quantization != scalar_f32_k)
+    if (quantization != scalar_f32_k || screened)
         if ((e = launch_norms(quantization, quantized, count, quantized_stride, bytes, point_norms)) ||
             (e = launch_norms(quantization, quantized_centroids, clusters, quantized_stride, bytes, centroid_norms)))
             return e;
     UA_HIP(hipMemset(indexes, 0xFF, count * 4));
-    UA_HIP(hipMemset(shifted, 0, 4));
-    const assign_args_t args{quantized, (std::uint32_t)count, quantized_centroids, (std::uint32_t)clusters, (std::uint32_t)quantized_stride,
-                             (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, shifted, plan};
+    UA_HIP(hipMemset(shifted, 0, 8));
+    assign_args_t args{quantized, (std::uint32_t)count, quantized_centroids, (std::uint32_t)clusters, (std::uint32_t)quantized_stride,
+                       (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, shifted, plan};
+    if (screened)
+        args.overflow_list = overflow_list, args.overflow_count = shifted + 1, args.contenders = contenders_device;
     if ((e = launch_assign(metric, quantization, args)))
         return e;
     std::vector<std::uint32_t> narrow(count);
     UA_HIP(hipMemcpy(narrow.data(), indexes, count * 4, hipMemcpyDeviceToHost));
     UA_HIP(hipMemcpy(distances, nearest, count * 4, hipMemcpyDeviceToHost));
+    if (contenders)
+        UA_HIP(hipMemcpy(contenders, contenders_device, count * 4, hipMemcpyDeviceToHost));
     for (std::size_t i = 0; i != count; ++i)
         assignments[i] = narrow[i];
     return nullptr;
+}
+
+} // namespace
+
+const char* kmeans_assign(const std::uint8_t* points, std::size_t count, std::size_t stride, const std::uint8_t* centroids,
+                          std::size_t clusters, std::size_t centroids_stride, scalar_kind_t kind, std::size_t dimensions,
+                          metric_kind_t metric, scalar_kind_t quantization, int device, std::uint64_t* assignments, float* distances) {
+    return assign_once(points, count, stride, centroids, clusters, centroids_stride, kind, dimensions, metric, quantization, device,
+                       assignments, distances, nullptr);
+}
+
+const char* kmeans_screen(const std::uint8_t* points, std::size_t count, std::size_t stride, const std::uint8_t* centroids,
+                          std::size_t clusters, std::size_t centroids_stride, std::size_t dimensions, metric_kind_t metric, int device,
+                          std::uint64_t* assignments, float* distances, std::uint32_t* contenders) {
+    if (!contenders)
+        return "kmeans_screen reports the contenders of every point";
+    return assign_once(points, count, stride, centroids, clusters, centroids_stride, scalar_f32_k, dimensions, metric, scalar_f32_k, device,
+                       assignments, distances, contenders);
 }
 
 const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_t stride, scalar_kind_t kind, std::size_t dimensions,
@@ -1064,7 +1409,8 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
         return "The number of clusters is too large for the device";
 
     // what the f64 sums and the rest need in HBM, against what is free
-    const std::size_t needed = point_rows * quantized_stride + centroid_rows * quantized_stride + count * 16 + clusters * 16 +
+    const bool screened = screened_assign(quantization, count, clusters);
+    const std::size_t needed = point_rows * quantized_stride + centroid_rows * quantized_stride + count * (screened ? 20 : 16) + clusters * 16 +
                                chunks * clusters * 4 + clusters * dimensions * 8 +
                                (kind == quantization ? 0 : std::min<std::size_t>(count * bytes_per_vector(kind, dimensions), std::size_t(1) << 30));
     std::size_t free_bytes = 0, total_bytes = 0;
@@ -1075,7 +1421,7 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
     device_scratch_t scratch(config.device);
     std::uint8_t *quantized = nullptr, *quantized_centroids = nullptr;
     std::uint32_t *point_norms = nullptr, *centroid_norms = nullptr, *indexes = nullptr, *scalars = nullptr, *seeds = nullptr,
-                  *cells = nullptr, *counts = nullptr, *offsets = nullptr, *members = nullptr;
+                  *cells = nullptr, *counts = nullptr, *offsets = nullptr, *members = nullptr, *overflow_list = nullptr;
     float* nearest = nullptr;
     double* sums = nullptr;
     UA_HIP(scratch.allocate(&quantized, point_rows * quantized_stride));
@@ -1084,7 +1430,9 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
     UA_HIP(scratch.allocate(&centroid_norms, clusters * 4));
     UA_HIP(scratch.allocate(&indexes, count * 4));
     UA_HIP(scratch.allocate(&nearest, count * 4));
-    UA_HIP(scratch.allocate(&scalars, 16)); // the f64 aggregate, then the count of points that changed centroid
+    UA_HIP(scratch.allocate(&scalars, 16)); // the f64 aggregate, the count of points that changed centroid, of points the screen handed over
+    if (screened)
+        UA_HIP(scratch.allocate(&overflow_list, count * 4));
     UA_HIP(scratch.allocate(&seeds, clusters * 4));
     UA_HIP(scratch.allocate(&cells, chunks * clusters * 4));
     UA_HIP(scratch.allocate(&counts, clusters * 4));
@@ -1126,13 +1474,15 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
     gather_rows_kernel<<<grid_for(clusters * (quantized_stride / 16), 256), 256>>>(quantized, seeds, quantized_centroids, (std::uint32_t)clusters,
                                                                                    (std::uint32_t)quantized_stride);
     UA_HIP(hipGetLastError());
-    if (quantization != scalar_f32_k)
+    if (quantization != scalar_f32_k || screened)
         if ((e = launch_norms(quantization, quantized, count, quantized_stride, bytes, point_norms)))
             return e;
     UA_HIP(hipDeviceSynchronize());
 
-    const assign_args_t args{quantized, (std::uint32_t)count, quantized_centroids, (std::uint32_t)clusters, (std::uint32_t)quantized_stride,
-                             (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, scalars + 2, plan};
+    assign_args_t args{quantized, (std::uint32_t)count, quantized_centroids, (std::uint32_t)clusters, (std::uint32_t)quantized_stride,
+                       (std::uint32_t)dimensions, point_norms, centroid_norms, indexes, nearest, scalars + 2, plan};
+    if (screened)
+        args.overflow_list = overflow_list, args.overflow_count = scalars + 3; // zeroed with the other scalars, every iteration
     struct {
         double aggregate;
         std::uint32_t shifted, unused;
@@ -1148,7 +1498,7 @@ const char* kmeans_run(const std::uint8_t* points, std::size_t count, std::size_
         // ---- assignment: the centroids' norms, every point against every centroid, the aggregate
         UA_HIP(hipMemsetAsync(scalars, 0, 16));
         UA_HIP(hipEventRecord(events.begin));
-        if (quantization != scalar_f32_k)
+        if (quantization != scalar_f32_k || screened)
             if ((e = launch_norms(quantization, quantized_centroids, clusters, quantized_stride, bytes, centroid_norms)))
                 return e;
         if ((e = launch_assign(metric, quantization, args)))

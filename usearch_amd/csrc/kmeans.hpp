@@ -40,6 +40,13 @@ const char* kmeans_assign(const std::uint8_t* points, std::size_t count, std::si
                           metric_kind_t metric, scalar_kind_t quantization, int device, std::uint64_t* assignments,
                           float* distances);
 
+/// The assignment of f32 rows on the screened tile (kmeans.hip, `assign_screened_kernel`) whatever the planner would choose, for
+/// the test hook: `kmeans_assign`'s results, and per point the number of contenders the closing re-measured — 0 for a point the
+/// screen handed to the wave kernel.
+const char* kmeans_screen(const std::uint8_t* points, std::size_t count, std::size_t stride, const std::uint8_t* centroids,
+                          std::size_t clusters, std::size_t centroids_stride, std::size_t dimensions, metric_kind_t metric, int device,
+                          std::uint64_t* assignments, float* distances, std::uint32_t* contenders);
+
 /// The device cast alone (what the loop clusters): `count` rows of `kind` → rows of `quantization`, `out_stride` bytes apart.
 const char* kmeans_quantize(const std::uint8_t* points, std::size_t count, std::size_t stride, scalar_kind_t kind,
                             std::size_t dimensions, scalar_kind_t quantization, int device, std::uint8_t* out,

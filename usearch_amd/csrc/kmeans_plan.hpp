@@ -4,6 +4,10 @@
  *  integer arithmetic over plain values, like exact_plan.hpp's planner: no HIP runtime call, no look at the environment (the caller
  *  reads USEARCH_AMD_KMEANS_TILE and passes it in). tests/test_gpu_kmeans_wide.py asserts its routes through
  *  `usearch_amd_test_plan_kmeans_assign`.
+ *
+ *  f32 rows have a sibling decision, `plan_kmeans_assign_f32`: the wave-per-point kernel (`assign_f32_kernel`) or the screened
+ *  64 × 128 tile (`assign_screened_kernel`), which returns the wave kernel's bits. There is no 256 × 256 tile for f32 — the screen's
+ *  contender sets would have to live beside eight accumulators per lane, and nobody has measured whether that pays: out of scope.
  */
 #pragma once
 #include <cstdint>
@@ -57,6 +61,21 @@ inline kmeans_assign_plan_t plan_kmeans_assign(std::uint64_t count, std::uint64_
         plan.lds_bytes = 0; // the 64 tile's LDS is static
     }
     return plan;
+}
+
+/// From this many centroids on, unforced f32 rows take the screened tile. Still the PLACEHOLDER of one centroid tile: the sweep in
+/// profiles/r17_kmeans_f32/README.md (65 536 × 768 on an MI355X, `scripts/kmeans_bench.py --dtype f32`, USEARCH_AMD_KMEANS_TILE = 1
+/// against = 64, three runs each) has the screened tile ahead at every centroid count it covers — 0.34 against 0.90 ms at 32, 0.36
+/// against 3.5 ms at 128, 12.7 against 32.0 ms at 1 024 — so the crossover lies below 32 centroids, where nothing was measured, nor
+/// was any other point count: the number stays where a tile is full until a sweep below 32 places it.
+constexpr std::uint64_t kmeans_screen_least_centroids_k = kmeans_tile_centroids_k;
+
+/// f32 rows: does the assignment run on the screened tile? `forced_tile`: USEARCH_AMD_KMEANS_TILE — 64 forces the screened tile at
+/// any shape, 1 the wave-per-point kernel; 256 (there is no wide f32 tile) and anything else leave the choice here.
+inline bool plan_kmeans_assign_f32(std::uint64_t count, std::uint64_t clusters, std::uint64_t forced_tile) {
+    if (!count || !clusters || forced_tile == 1)
+        return false;
+    return forced_tile == 64 || clusters >= kmeans_screen_least_centroids_k;
 }
 
 } // namespace usearch_amd

@@ -557,6 +557,18 @@ extern "C" __attribute__((visibility("default"))) void usearch_amd_test_kmeans_q
                                 (scalar_kind_t)quantization_kind, device, static_cast<std::uint8_t*>(out), out_stride));
 }
 
+// ---- k-means over f32 rows on the screened tile (kmeans.hip, `assign_screened_kernel`) whatever the planner would choose, for
+//      tests/test_gpu_kmeans_f32.py: `usearch_amd_kmeans_assign`'s results and, per point, how many contenders the closing
+//      re-measured — 0 for a point the screen handed to the wave kernel. `metric`: metric_kind_t of common.hpp.
+extern "C" __attribute__((visibility("default"))) void usearch_amd_test_kmeans_screen(const void* points, size_t count, size_t stride,
+                                                                                      const void* centroids, size_t clusters,
+                                                                                      size_t centroids_stride, size_t dimensions, int metric,
+                                                                                      int device, uint64_t* assignments, float* distances,
+                                                                                      uint32_t* contenders, usearch_amd_error_t* error) {
+    fail(error, kmeans_screen(static_cast<const std::uint8_t*>(points), count, stride, static_cast<const std::uint8_t*>(centroids), clusters,
+                              centroids_stride, dimensions, (metric_kind_t)metric, device, assignments, distances, contenders));
+}
+
 // ---- the launch planner (search_plan.hpp) on plain values, for tests/test_search_plan.py: what `search_begin` settles for the call
 //      described by `shape` and `tuning`, then one rung of the retry ladder per entry of `pending` (the queries that rung runs over: all
 //      of them, then those that outgrew their scratch), `escalate` between them, until a rung is the global one. `knobs` null = the

@@ -1313,6 +1313,10 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_kmeans_quantize.restype = None
         _test_hooks.usearch_amd_test_kmeans_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
+        _test_hooks.usearch_amd_test_kmeans_screen.restype = None
+        _test_hooks.usearch_amd_test_kmeans_screen.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                               C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                               C.POINTER(C.c_char_p)]
         _test_hooks.usearch_amd_test_device_scratch.restype = None
         _test_hooks.usearch_amd_test_device_scratch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]
@@ -1439,6 +1443,23 @@ def test_kmeans_quantize(X: np.ndarray, from_dtype: str, to_dtype: str, device: 
                                                   _pointer(out), out.strides[0], C.byref(err))
     _raise(err, "usearch_amd_test_kmeans_quantize")
     return out
+
+
+def test_kmeans_screen(X: np.ndarray, centroids: np.ndarray, metric: str, device: int = 0):
+    """`kmeans_assign(X, centroids, metric, dtype="f32")` on the screened matrix-unit tile (csrc/kmeans.hip) whatever the planner
+    would choose → (assignments uint64[N], distances float32[N], contenders uint32[N]): per point how many centroids the screen left
+    to be re-measured in the wave kernel's arithmetic, 0 for a point it handed to the wave kernel altogether."""
+    X, centroids = np.ascontiguousarray(X, dtype=np.float32), np.ascontiguousarray(centroids, dtype=np.float32)
+    count, ndim = X.shape
+    assignments, distances = np.zeros(count, dtype=np.uint64), np.zeros(count, dtype=np.float32)
+    contenders = np.zeros(count, dtype=np.uint32)
+    err = C.c_char_p()
+    test_hooks().usearch_amd_test_kmeans_screen(_pointer(X), count, X.strides[0], _pointer(centroids), len(centroids), centroids.strides[0],
+                                                ndim, ord({"ip": "i", "cos": "c", "l2sq": "e"}[metric]),  # metric_kind_t of csrc/common.hpp
+                                                device, _pointer(assignments), _pointer(distances),
+                                                _pointer(contenders), C.byref(err))
+    _raise(err, "usearch_amd_test_kmeans_screen")
+    return assignments, distances, contenders
 
 
 def test_sketch_bounds(rows: np.ndarray, queries: np.ndarray, dtype: str):
