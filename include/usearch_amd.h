@@ -286,7 +286,9 @@ USEARCH_AMD_EXPORT void usearch_amd_filtered_search_many_device(usearch_amd_snap
                                                                 usearch_amd_stats_t* stats, usearch_amd_error_t* error);
 /** `filtered_search(query, wanted, predicate, thread, exact = true)` of the class for a batch (index_dense.hpp:774-779 →
  *  `search_exact_` with the predicate, index.hpp:4252-4268): brute force over the members that pass. Host buffers, any query scalar
- *  kind; `tiled != 0` = the matrix-unit kernel (pairs and tolerances of `usearch_amd_exact_search_many_tiled`). */
+ *  kind; `tiled != 0` = the matrix-unit kernel (pairs and tolerances of `usearch_amd_exact_search_many_tiled`), except
+ *  `tiled == 2` = the screened route (pairs, bits and refusals of `usearch_amd_exact_search_many_screened`; this entry has no
+ *  `remeasured` output: how many rows were measured, and which queries were handed over, is not reported here). */
 USEARCH_AMD_EXPORT void usearch_amd_filtered_exact_search_many(usearch_amd_snapshot_t snapshot, usearch_amd_filter_t filter,
                                                                void const* queries, int query_kind, size_t queries_count,
                                                                size_t queries_stride, size_t wanted, usearch_amd_key_t* keys,
@@ -371,9 +373,27 @@ USEARCH_AMD_EXPORT void usearch_amd_exact_search_many_tiled(usearch_amd_snapshot
                                                             float* kernel_ms, usearch_amd_error_t* error);
 
 /**
+ *  The same exact search SCREENED on the matrix units (usearch_amd/csrc/exact_screened.hip): the f32 tile of the call above forms
+ *  a score and a derived error per (query, row) and rules out the rows that cannot be among a query's `wanted` nearest; the rest
+ *  are measured by the kernel of `usearch_amd_exact_search_many`, in its arithmetic. Keys, distance bits and counts are that
+ *  call's, to the bit, ties included, a query that meets a NaN distance included
+ *  (it is handed to that kernel whole). Pairs: cos / ip / l2sq over f32, `wanted` ≤ 64 — l2sq over f32 included, which the tiled call
+ *  refuses; any other pair or count is refused ("No screened exact-search kernel for this metric / scalar kind / result count"),
+ *  never sent down another kernel quietly. `remeasured` (may be NULL): per query, the rows that were measured — the stored rows
+ *  that are neither removed nor filtered out for a query handed to the other kernel whole (a NaN or an infinity in it or in a row
+ *  it could not rule out, more rows it could not rule out than its buffers hold).
+ */
+USEARCH_AMD_EXPORT void usearch_amd_exact_search_many_screened(usearch_amd_snapshot_t snapshot, void const* queries,
+                                                               int query_kind, size_t queries_count, size_t queries_stride,
+                                                               size_t wanted, usearch_amd_key_t* keys,
+                                                               usearch_amd_distance_t* distances, uint64_t* counts,
+                                                               float* kernel_ms, uint64_t* remeasured, usearch_amd_error_t* error);
+
+/**
  *  Either exact search over DEVICE buffers (queries in the storage scalar kind, `queries_stride` bytes apart; keys, distances and
  *  counts dense `[queries_count][wanted]` / `[queries_count]` in HBM), enqueued on `stream` (NULL: a stream of the snapshot);
- *  returns when the results are complete. `tiled != 0` selects the matrix-unit kernel (b1: the bit tile). `kernel_ms` (may be NULL): HIP-event
+ *  returns when the results are complete. `tiled != 0` selects the matrix-unit kernel (b1: the bit tile), except `tiled == 2`, which
+ *  selects the screened route of `usearch_amd_exact_search_many_screened` (its pairs, bits and refusals). `kernel_ms` (may be NULL): HIP-event
  *  time of the kernels. What `bench.py --exact` times.
  */
 USEARCH_AMD_EXPORT void usearch_amd_exact_search_many_device(usearch_amd_snapshot_t snapshot, void const* queries,
@@ -412,6 +432,18 @@ USEARCH_AMD_EXPORT void usearch_amd_exact_search_dataset_tiled(void const* datas
                                                                usearch_amd_key_t* keys, size_t keys_stride,
                                                                usearch_amd_distance_t* distances, size_t distances_stride,
                                                                usearch_amd_error_t* error);
+
+/**
+ *  The same call SCREENED (`usearch_amd_exact_search_many_screened`: its pairs, its refusals, the bits of
+ *  `usearch_amd_exact_search_dataset`), plus `remeasured` (`[queries_count]`, may be NULL): the rows measured per query.
+ */
+USEARCH_AMD_EXPORT void usearch_amd_exact_search_dataset_screened(void const* dataset, size_t dataset_count,
+                                                                  size_t dataset_stride, void const* queries,
+                                                                  size_t queries_count, size_t queries_stride, int scalar_kind,
+                                                                  size_t dimensions, int metric_kind, size_t wanted,
+                                                                  usearch_amd_key_t* keys, size_t keys_stride,
+                                                                  usearch_amd_distance_t* distances, size_t distances_stride,
+                                                                  uint64_t* remeasured, usearch_amd_error_t* error);
 
 /* ------------------------------------------------------------------------------------------------------------------
  *  Sharded search across the GPUs of one node — one process per GPU, one shard (its own HNSW) per process.

@@ -406,6 +406,9 @@ void usearch_amd_filtered_search_many_device(usearch_amd_snapshot_t snapshot, us
     fail_from_exception(error);
 }
 
+/// The `tiled` argument of the exact-search entries: 0 the wave kernel, 2 the screened route, anything else the tiles (as it always was).
+static int exact_route_from_c(int tiled) { return tiled == 0 ? exact_wave_k : tiled == 2 ? exact_screened_k : exact_tiled_k; }
+
 void usearch_amd_filtered_exact_search_many(usearch_amd_snapshot_t snapshot, usearch_amd_filter_t filter, void const* queries,
                                             int query_kind, size_t queries_count, size_t queries_stride, size_t wanted,
                                             usearch_amd_key_t* keys, usearch_amd_distance_t* distances, uint64_t* counts,
@@ -420,7 +423,7 @@ void usearch_amd_filtered_exact_search_many(usearch_amd_snapshot_t snapshot, use
         bits = as_filter(filter)->bits();
     }
     if (const char* e = as_snapshot(snapshot)->exact_host(queries, kind, queries_count, queries_stride, wanted, keys, distances,
-                                                          counts, kernel_ms, tiled != 0, bits))
+                                                          counts, kernel_ms, exact_route_from_c(tiled), bits))
         fail(error, e);
 } catch (...) {
     fail_from_exception(error);
@@ -464,7 +467,21 @@ void usearch_amd_exact_search_many_tiled(usearch_amd_snapshot_t snapshot, void c
     if (kind == scalar_unknown_k)
         return fail(error, "Unknown scalar kind!");
     if (const char* e = as_snapshot(snapshot)->exact_host(queries, kind, queries_count, queries_stride, wanted, keys,
-                                                          distances, counts, kernel_ms, true))
+                                                          distances, counts, kernel_ms, exact_tiled_k))
+        fail(error, e);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+void usearch_amd_exact_search_many_screened(usearch_amd_snapshot_t snapshot, void const* queries, int query_kind,
+                                            size_t queries_count, size_t queries_stride, size_t wanted,
+                                            usearch_amd_key_t* keys, usearch_amd_distance_t* distances, uint64_t* counts,
+                                            float* kernel_ms, uint64_t* remeasured, usearch_amd_error_t* error) try {
+    const scalar_kind_t kind = scalar_from_c(query_kind);
+    if (kind == scalar_unknown_k)
+        return fail(error, "Unknown scalar kind!");
+    if (const char* e = as_snapshot(snapshot)->exact_host(queries, kind, queries_count, queries_stride, wanted, keys,
+                                                          distances, counts, kernel_ms, exact_screened_k, nullptr, remeasured))
         fail(error, e);
 } catch (...) {
     fail_from_exception(error);
@@ -475,7 +492,8 @@ void usearch_amd_exact_search_many_device(usearch_amd_snapshot_t snapshot, void 
                                           usearch_amd_distance_t* distances, uint64_t* counts, void* stream, int tiled,
                                           float* kernel_ms, usearch_amd_error_t* error) try {
     if (const char* e = as_snapshot(snapshot)->exact_device(queries, queries_count, queries_stride, wanted, keys, distances,
-                                                            counts, static_cast<hipStream_t>(stream), kernel_ms, tiled != 0))
+                                                            counts, static_cast<hipStream_t>(stream), kernel_ms,
+                                                            exact_route_from_c(tiled)))
         fail(error, e);
 } catch (...) {
     fail_from_exception(error);
@@ -503,7 +521,21 @@ void usearch_amd_exact_search_dataset_tiled(void const* dataset, size_t dataset_
     if (const char* e = exact_search_dataset_host(metric_from_c(metric_kind), scalar_from_c(scalar_kind), dimensions,
                                                   dataset, dataset_count, dataset_stride, queries, queries_count,
                                                   queries_stride, wanted, keys, keys_stride, distances,
-                                                  distances_stride, true))
+                                                  distances_stride, exact_tiled_k))
+        fail(error, e);
+} catch (...) {
+    fail_from_exception(error);
+}
+
+void usearch_amd_exact_search_dataset_screened(void const* dataset, size_t dataset_count, size_t dataset_stride,
+                                               void const* queries, size_t queries_count, size_t queries_stride,
+                                               int scalar_kind, size_t dimensions, int metric_kind, size_t wanted,
+                                               usearch_amd_key_t* keys, size_t keys_stride, usearch_amd_distance_t* distances,
+                                               size_t distances_stride, uint64_t* remeasured, usearch_amd_error_t* error) try {
+    if (const char* e = exact_search_dataset_host(metric_from_c(metric_kind), scalar_from_c(scalar_kind), dimensions,
+                                                  dataset, dataset_count, dataset_stride, queries, queries_count,
+                                                  queries_stride, wanted, keys, keys_stride, distances,
+                                                  distances_stride, exact_screened_k, remeasured))
         fail(error, e);
 } catch (...) {
     fail_from_exception(error);

@@ -1354,7 +1354,7 @@ const char* exact_search_device(metric_kind_t metric, scalar_kind_t scalar, std:
 
 const char* snapshot_t::exact_device(const void* queries, std::size_t count, std::size_t stride_bytes,
                                      std::size_t wanted, std::uint64_t* keys, float* distances, std::uint64_t* counts,
-                                     hipStream_t stream, float* kernel_ms, bool tiled, const std::uint32_t* allow_bits) {
+                                     hipStream_t stream, float* kernel_ms, int tiled, const std::uint32_t* allow_bits) {
     if (!count || !wanted)
         return nullptr;
     UA_HIP(hipSetDevice(device_));
@@ -1364,6 +1364,9 @@ const char* snapshot_t::exact_device(const void* queries, std::size_t count, std
             return e;
         stream = lease.workspace->stream;
     }
+    if (tiled == exact_screened_k)
+        return exact_search_screened_device(kernel_metric(metric_), scalar_, lanes_, view_, queries, count, stride_bytes, wanted, true,
+                                            keys, distances, counts, nullptr, stream, kernel_ms, allow_bits);
     if (tiled)
         return exact_search_tiled_device(kernel_metric(metric_), scalar_, view_, queries, count, stride_bytes, wanted, true, keys,
                                          distances, counts, stream, kernel_ms, allow_bits);
@@ -1373,7 +1376,8 @@ const char* snapshot_t::exact_device(const void* queries, std::size_t count, std
 
 const char* snapshot_t::exact_host(const void* queries, scalar_kind_t query_kind, std::size_t count,
                                    std::size_t stride_bytes, std::size_t wanted, std::uint64_t* keys, float* distances,
-                                   std::uint64_t* counts, float* kernel_ms, bool tiled, const std::uint32_t* allow_bits) {
+                                   std::uint64_t* counts, float* kernel_ms, int tiled, const std::uint32_t* allow_bits,
+                                   std::uint64_t* remeasured) {
     if (!count || !wanted)
         return nullptr;
     const std::size_t bpv = view_.bytes_per_vector, dims = view_.dimensions;
@@ -1392,14 +1396,22 @@ const char* snapshot_t::exact_host(const void* queries, scalar_kind_t query_kind
         return e;
     workspace_t& ws = *lease.workspace;
     auto pad = [](std::size_t b) { return (b + 255) & ~(std::size_t)255; };
-    if (const char* e = ws.reserve_stage(pad(bpv * count) + pad(count * wanted * 8) + pad(count * wanted * 4) + pad(count * 8), 0))
+    if (const char* e = ws.reserve_stage(pad(bpv * count) + pad(count * wanted * 8) + pad(count * wanted * 4) + 2 * pad(count * 8), 0))
         return e;
     std::uint8_t* d_queries = ws.d_stage;
     std::uint64_t* d_keys = reinterpret_cast<std::uint64_t*>(d_queries + pad(bpv * count));
     float* d_distances = reinterpret_cast<float*>(reinterpret_cast<std::uint8_t*>(d_keys) + pad(count * wanted * 8));
     std::uint64_t* d_counts = reinterpret_cast<std::uint64_t*>(reinterpret_cast<std::uint8_t*>(d_distances) + pad(count * wanted * 4));
+    std::uint64_t* d_remeasured = d_counts + pad(count * 8) / 8;
     UA_HIP(hipMemcpy(d_queries, dense.data(), bpv * count, hipMemcpyHostToDevice));
-    if (tiled) {
+    if (tiled == exact_screened_k) {
+        if (const char* e = exact_search_screened_device(kernel_metric(metric_), scalar_, lanes_, view_, d_queries, count, bpv, wanted,
+                                                         true, d_keys, d_distances, d_counts, d_remeasured, ws.stream, kernel_ms,
+                                                         allow_bits))
+            return e;
+        if (remeasured)
+            UA_HIP(hipMemcpy(remeasured, d_remeasured, count * 8, hipMemcpyDeviceToHost));
+    } else if (tiled) {
         if (const char* e = exact_search_tiled_device(kernel_metric(metric_), scalar_, view_, d_queries, count, bpv, wanted,
                                                       true, d_keys, d_distances, d_counts, ws.stream, kernel_ms, allow_bits))
             return e;
@@ -1420,14 +1432,16 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
                                       const void* dataset, std::size_t dataset_count, std::size_t dataset_stride,
                                       const void* queries, std::size_t queries_count, std::size_t queries_stride,
                                       std::size_t wanted, std::uint64_t* keys, std::size_t keys_stride,
-                                      float* distances, std::size_t distances_stride, bool tiled) {
+                                      float* distances, std::size_t distances_stride, int tiled, std::uint64_t* remeasured) {
     // (f8 has the matrix-unit tiles and nothing else so far: asked for by name it is the tiles' table that answers, any other way
     // it is refused like every pair without a kernel)
     if (!kernel_available(metric, scalar) && !(tiled && scalar == scalar_f8_k))
         return "No MI355X kernel for this metric / scalar kind combination";
     if (!queries_count || !wanted)
         return nullptr;
-    if (tiled && !exact_tiled_available(metric, scalar, wanted)) // asked for by name: no quiet detour over the wave kernel
+    if (tiled == exact_screened_k && !exact_screened_available(metric, scalar, wanted)) // by name too, and never rerouted
+        return "No screened exact-search kernel for this metric / scalar kind / result count";
+    if (tiled && tiled != exact_screened_k && !exact_tiled_available(metric, scalar, wanted)) // asked for by name: no quiet detour over the wave kernel
         return "No tiled exact-search kernel for this metric / scalar kind / result count";
     if (dataset_count >= none_slot_k)
         return "Dataset is too large for 32-bit offsets";
@@ -1445,6 +1459,8 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
     UA_HIP(scratch.allocate(&d_keys, queries_count * wanted * 8));
     UA_HIP(scratch.allocate(&d_distances, queries_count * wanted * 4));
     UA_HIP(scratch.allocate(&d_counts, queries_count * 8));
+    std::uint64_t* d_remeasured = nullptr;
+    UA_HIP(scratch.allocate(&d_remeasured, queries_count * 8));
     if (const char* error = upload_rows(d_rows, row_stride, static_cast<const std::uint8_t*>(dataset), dataset_stride, bpv, dataset_count))
         return error;
     if (const char* error = upload_rows(d_queries, (std::uint32_t)bpv, static_cast<const std::uint8_t*>(queries), queries_stride, bpv,
@@ -1461,7 +1477,12 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
     // the float kinds only reach it when asked (`tiled`: a derived bound instead of bit equality), and so does b1, whose bit tile
     // (exact_bits.hip) returns the wave kernel's bits too: routing it unasked waits for its speed to be measured
     const char* error = nullptr;
-    if (tiled || (scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
+    if (tiled == exact_screened_k) {
+        error = exact_search_screened_device(kernel_metric(metric), scalar, lanes, view, d_queries, queries_count, bpv, wanted, false,
+                                             d_keys, d_distances, d_counts, d_remeasured, nullptr, nullptr);
+        if (!error && remeasured)
+            UA_HIP(hipMemcpy(remeasured, d_remeasured, queries_count * 8, hipMemcpyDeviceToHost));
+    } else if (tiled || (scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
                   !env_size("USEARCH_AMD_NO_TILED_EXACT", 0)))
         error = exact_search_tiled_device(kernel_metric(metric), scalar, view, d_queries, queries_count, bpv, wanted, false, d_keys,
                                           d_distances, d_counts, nullptr, nullptr);

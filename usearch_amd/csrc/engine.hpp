@@ -188,6 +188,9 @@ void launch_sketch_records(const std::uint8_t* vectors, std::uint32_t row_stride
                            std::uint64_t first, std::uint64_t size, const float* directions, double gram_defect, std::uint8_t* records,
                            hipStream_t stream);
 
+/// Which exact search a caller asks for — the values of the C ABI's `tiled` arguments (include/usearch_amd.h).
+enum exact_route_t : int { exact_wave_k = 0, exact_tiled_k = 1, exact_screened_k = 2 };
+
 class snapshot_t {
   public:
     friend struct sketch_test_access_t; ///< test_hooks.hip: reads the sketch back for tests/test_gpu_sketch_records.py
@@ -337,12 +340,15 @@ class snapshot_t {
     /// applies too (index.hpp:4260-4263).
     const char* exact_device(const void* queries, std::size_t count, std::size_t stride_bytes, std::size_t wanted,
                              std::uint64_t* keys, float* distances, std::uint64_t* counts, hipStream_t stream,
-                             float* kernel_ms, bool tiled = false, const std::uint32_t* allow_bits = nullptr);
-    /// Same with host buffers and any query scalar kind. `tiled`: the matrix-unit kernel where one exists for the pair
-    /// (exact_tiled.hip; an error otherwise) instead of the bit-exact wave-per-query one.
+                             float* kernel_ms, int tiled = exact_wave_k, const std::uint32_t* allow_bits = nullptr);
+    /// Same with host buffers and any query scalar kind. `tiled` = `exact_tiled_k`: the matrix-unit kernel where one exists for the
+    /// pair (exact_tiled.hip; an error otherwise) instead of the bit-exact wave-per-query one; `exact_screened_k`: the screened
+    /// route (exact_screened.hip; the wave kernel's bits, an error for a pair without it), which also fills `remeasured` ([count],
+    /// host, optional: rows measured per query).
     const char* exact_host(const void* queries, scalar_kind_t query_kind, std::size_t count, std::size_t stride_bytes,
                            std::size_t wanted, std::uint64_t* keys, float* distances, std::uint64_t* counts,
-                           float* kernel_ms, bool tiled = false, const std::uint32_t* allow_bits = nullptr);
+                           float* kernel_ms, int tiled = exact_wave_k, const std::uint32_t* allow_bits = nullptr,
+                           std::uint64_t* remeasured = nullptr);
 
     /// out[q][j] = metric(query q, stored row slots[q][j]); host buffers, queries in storage kind.
     const char* distances_host(const void* queries, std::size_t count, std::size_t stride_bytes,
@@ -521,6 +527,32 @@ struct exact_params_t {
     std::uint64_t* out_counts; ///< [partitions][queries]
 };
 
+/// The screened exact search's closing pass (`exact_remeasure_kernel`, kernels.hpp): device pointers, layouts as that kernel names them.
+struct exact_remeasure_params_t {
+    std::uint32_t lanes;
+    std::uint32_t lds_bytes;
+    hipStream_t stream;
+    const std::uint8_t* queries;
+    std::uint64_t query_stride;
+    std::uint32_t query_count;
+    std::uint32_t wanted;
+    std::uint32_t partitions;
+    std::uint32_t capacity;
+    const std::uint32_t* contender_slots; ///< [queries][partitions][capacity]
+    const float* contender_lows;
+    const std::uint32_t* contender_counts; ///< [queries][partitions]
+    const float* bounds;
+    std::uint32_t map_keys;
+    std::uint32_t* handed;     ///< [queries]
+    float* out_distances;      ///< [queries][wanted]
+    std::uint64_t* out_keys;
+    std::uint64_t* out_counts; ///< [queries]
+    std::uint64_t* remeasured; ///< [queries], optional
+};
+hipError_t launch_exact_remeasure_cos_f32(const exact_remeasure_params_t&, const snapshot_view_t&);
+hipError_t launch_exact_remeasure_ip_f32(const exact_remeasure_params_t&, const snapshot_view_t&);
+hipError_t launch_exact_remeasure_l2sq_f32(const exact_remeasure_params_t&, const snapshot_view_t&);
+
 /// One launch of the distance kernel behind `usearch_amd_distances` for the index's (metric, scalar) pair (engine.hip): `count` waves,
 /// `slots_per_query` rows each. Also what the merges and the closing distances of clustering.hip run.
 hipError_t launch_distances(metric_kind_t metric, scalar_kind_t scalar, const distances_params_t& p, const snapshot_view_t& view);
@@ -555,6 +587,19 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
                                       bool map_keys, std::uint64_t* keys, float* distances, std::uint64_t* counts,
                                       hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits = nullptr);
 
+/// Screened exact search (exact_screened.hip) of the pairs of `exact_screened_pair` (exact_plan.hpp: cos, ip and l2sq over f32): the
+/// f32 matrix-unit tile forms a score and a derived error per (query, row) and keeps the rows that can be among the `wanted`
+/// nearest; `exact_remeasure_kernel` measures those with `exact_kernel`'s instantiation for `lanes`. Keys, distance bits and counts
+/// are `exact_search_device`'s; queries the screen cannot decide are handed to that function. Same contract as it, plus
+/// `remeasured` ([count], device, optional): rows measured per query. Every other pair or count is refused by name.
+/// `exact_screened_available`: the table (`exact_screened_pair`) for callers that want the refusal before they upload anything.
+bool exact_screened_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted);
+const char* exact_search_screened_device(metric_kind_t metric, scalar_kind_t scalar, std::uint32_t lanes, const snapshot_view_t& view,
+                                         const void* queries, std::size_t count, std::size_t stride_bytes, std::size_t wanted,
+                                         bool map_keys, std::uint64_t* keys, float* distances, std::uint64_t* counts,
+                                         std::uint64_t* remeasured, hipStream_t stream, float* kernel_ms,
+                                         const std::uint32_t* allow_bits = nullptr);
+
 /// The bit tile (exact_bits.hip): rows are read once per 256 queries, popcount(a ∧ b) on the vector ALU. `metric`: hamming, tanimoto,
 /// jaccard or sorensen; the view's rows are b1. Same contract and the same refusals as `exact_search_tiled_device`, which is its
 /// one caller.
@@ -563,13 +608,15 @@ const char* exact_search_bits_device(metric_kind_t metric, const snapshot_view_t
                                      std::uint64_t* counts, hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits = nullptr);
 
 /// Host-buffer exact search of a raw dataset — `usearch_exact_search` (c/usearch.h:467-474): keys are dataset offsets.
-/// `tiled`: the matrix-unit kernel (or the bit tile) over the uploaded rows for any pair that has one (`exact_tiled_available`; refused otherwise)
-/// instead of the bit-exact wave-per-query one, which stays what the float kinds get unasked.
+/// `tiled` = `exact_tiled_k`: the matrix-unit kernel (or the bit tile) over the uploaded rows for any pair that has one (`exact_tiled_available`; refused otherwise)
+/// instead of the bit-exact wave-per-query one, which stays what the float kinds get unasked. `exact_screened_k`: the screened route
+/// over the uploaded rows (refused for a pair without it); `remeasured`: [queries_count], host, optional.
 const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar, std::size_t dimensions,
                                       const void* dataset, std::size_t dataset_count, std::size_t dataset_stride,
                                       const void* queries, std::size_t queries_count, std::size_t queries_stride,
                                       std::size_t wanted, std::uint64_t* keys, std::size_t keys_stride,
-                                      float* distances, std::size_t distances_stride, bool tiled = false);
+                                      float* distances, std::size_t distances_stride, int tiled = exact_wave_k,
+                                      std::uint64_t* remeasured = nullptr);
 
 /// Lanes per stored row, the row pitch and the 16-byte chunks the kernels read of a row of `bytes` bytes (the summation layout
 /// of DESIGN.md §3.3; the pitch may exceed chunks × 16 so that short rows never straddle a 128-byte line).

@@ -111,6 +111,62 @@ inline const char* plan_exact(std::uint64_t rows, std::uint64_t bytes_per_vector
     return nullptr;
 }
 
+// ---- the screened route (exact_screened.hip): the f32 matrix-unit tile rules rows out, the wave kernel's arithmetic measures the rest
+
+/// Which (metric, scalar kind) pairs the screened route takes, and for how many results per query: cos, ip and l2sq over f32,
+/// 1 … `max_wanted_k` results — l2sq over f32 included, which `exact_tiled_pair` refuses: the screen never publishes a sum of its
+/// own, the distances are the wave kernel's. A table of its own; `exact_tiled_pair` stays as tests/test_exact_tiled_pairs.py pins
+/// it. tests/test_exact_screened_plan.py pins this one through `usearch_amd_test_exact_screened_pair`.
+inline bool exact_screened_pair(metric_kind_t metric, scalar_kind_t scalar, std::uint64_t wanted) {
+    if (!wanted || wanted > (std::uint64_t)max_wanted_k || scalar != scalar_f32_k)
+        return false;
+    return metric == metric_cos_k || metric == metric_ip_k || metric == metric_l2sq_k;
+}
+
+/// What `plan_exact_screened` settles: a grid of (query_tiles, partitions) workgroups of the 64 × 128 tile, and per
+/// (query, partition) a buffer of `capacity` contenders.
+struct exact_screened_plan_t {
+    std::uint64_t query_tiles = 0;
+    std::uint64_t partitions = 0;
+    std::uint64_t rows_per_partition = 0;
+    std::uint64_t capacity = 0;      ///< contenders (slot, lower bound: 8 bytes) a (query, partition) buffer holds
+    std::uint64_t scratch_bytes = 0; ///< what the call allocates before it launches: Σx² of rows and queries, buffers, counters,
+                                     ///< bounds, flags — NOT the hand-over's batch (gathered queries, the wave kernel's results), which
+                                     ///< is sized by the number of queries handed over and allocated once that is known
+};
+
+/// Partitions as `plan_exact`'s 64-tile branch deals them. The capacity rule: a row is appended when its lower bound is at most the
+/// `wanted`-th lowest upper bound seen so far in its partition; over rows in random order the i-th row of a partition does so with
+/// probability ≈ wanted / i, wanted · (1 + ln(R / wanted)) rows of R in all. The buffer holds wanted · (2 + 2 · ⌈log₂⌈R / wanted⌉⌉)
+/// — about three times that (2 · log₂ = 2.9 · ln), at least 32, never more than the partition has rows (then it cannot overflow).
+/// A query whose buffer overflows all the same (rows sorted by falling distance, many equal rows) is handed to the wave kernel
+/// whole: capacity costs memory and time, never results. `scratch_limit`: bytes the caller can spare on the device.
+/// → nullptr, or why the call is refused.
+inline const char* plan_exact_screened(std::uint64_t rows, std::uint64_t bytes_per_vector, std::uint64_t row_stride, std::uint64_t count,
+                                       std::uint64_t wanted, std::uint64_t scratch_limit, exact_screened_plan_t& plan) {
+    plan = exact_screened_plan_t{};
+    if (!wanted || wanted > (std::uint64_t)max_wanted_k)
+        return "No screened exact-search kernel for this metric / scalar kind / result count";
+    if (!count)
+        return nullptr;
+    exact_plan_t tiles;
+    if (const char* refusal = plan_exact(rows, bytes_per_vector, row_stride, count, wanted, tile_queries_k, false, tiles))
+        return refusal;
+    plan.query_tiles = tiles.query_tiles;
+    plan.partitions = tiles.partitions;
+    plan.rows_per_partition = tiles.rows_per_partition;
+    const std::uint64_t longest = std::min(rows, plan.rows_per_partition), ratio = (longest + wanted - 1) / wanted;
+    std::uint64_t log2_ratio = 0;
+    while ((1ull << log2_ratio) < ratio)
+        ++log2_ratio;
+    plan.capacity = std::min(longest, std::max<std::uint64_t>(32, wanted * (2 + 2 * log2_ratio)));
+    const std::uint64_t cells = count * plan.partitions;
+    plan.scratch_bytes = rows * 4 + count * 4 + cells * plan.capacity * 8 + cells * 8 + count * 4;
+    if (plan.scratch_bytes > scratch_limit)
+        return "Not enough device memory for the screened exact search's contender buffers";
+    return nullptr;
+}
+
 // ---- the bit tile (exact_bits.hip): hamming, tanimoto / jaccard and sorensen over b1, popcount(a ∧ b) on the vector ALU
 
 constexpr int bits_wave_queries_k = 64; ///< queries a wave owns: their lists are its own, no wave ever inserts into another's

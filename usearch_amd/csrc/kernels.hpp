@@ -2550,4 +2550,107 @@ __global__ __launch_bounds__(64) void exact_kernel(const snapshot_view_t ix, con
         out_counts[(std::uint64_t)partition * query_count + q] = top.size;
 }
 
+/**
+ *  The closing pass of the screened exact search (exact_screened.hip): one wave per query measures only the rows the matrix-unit
+ *  screen could not rule out, with `exact_kernel`'s own `measure_rows` instantiation and its own insert loop, so keys, distance
+ *  bits, counts and padding are that kernel's. The screen left, per (query, partition), up to `capacity` contenders — slot and lower
+ *  bound s − e of the distance's image — and its bound τ (the `wanted`-th lowest upper bound it saw, +inf below `wanted` rows). A
+ *  contender stays if its lower bound is at most the query's final bound, the lowest τ of any partition: `wanted` rows at most that
+ *  far exist, so a row above it is in no top-`wanted`.
+ *
+ *  Order: a (query, partition) buffer is appended to by the one wave that owns the query, tile by tile and lane by lane, so it is
+ *  ascending in slot; partitions are ascending ranges; compaction keeps the order. The inserts below therefore arrive in ascending
+ *  slot order like `exact_kernel`'s, and the lower_bound insert gives the same (distance ↑, slot ↓) list — one list per query, where
+ *  `exact_kernel` folds one per partition through `merge_kernel` to the same top-`wanted` of that total order.
+ *
+ *  `handed[q]` != 0 on entry: the screen gave the query up (a buffer overflowed, Σa² out of band) — nothing is written for it. Set
+ *  here when a measured distance is a NaN: where NaNs go in `top` is `exact_kernel`'s business, and the caller runs that kernel for
+ *  every handed-over query. Results are final: out_* are [query][wanted] / [query], no merge follows.
+ */
+template <int metric_ak, int scalar_ak, int lanes_ak, int unroll_ak>
+__global__ __launch_bounds__(64) void exact_remeasure_kernel(const snapshot_view_t ix, const std::uint8_t* queries,
+                                                             std::uint64_t query_stride, std::uint32_t wanted,
+                                                             std::uint32_t partitions, std::uint32_t capacity,
+                                                             const std::uint32_t* contender_slots, const float* contender_lows,
+                                                             const std::uint32_t* contender_counts, const float* bounds,
+                                                             std::uint32_t map_keys, std::uint32_t* handed, float* out_distances,
+                                                             std::uint64_t* out_keys, std::uint64_t* out_counts,
+                                                             std::uint64_t* remeasured) {
+    extern __shared__ __attribute__((aligned(16))) std::uint8_t lds[];
+    const std::uint32_t lane = lane_id();
+    const std::uint32_t q = blockIdx.x;
+    if (uniform_u32(handed[q]))
+        return;
+    std::uint8_t* query_lds = lds;
+    std::uint32_t* cand_slots = reinterpret_cast<std::uint32_t*>(lds + query_lds_bytes<scalar_ak>(ix.chunks));
+    float* cand_distances = reinterpret_cast<float*>(cand_slots + 64);
+    top_gt<0, false> top;
+    top.reset(reinterpret_cast<cand_t*>(cand_distances + 64));
+    const query_norm_t a2 = stage_query<metric_ak, scalar_ak, lanes_ak>(ix, queries + (std::uint64_t)q * query_stride, query_lds);
+
+    float bound = __builtin_inff(); // the lowest τ of any partition; upper bounds are finite or +inf, never a NaN
+    for (std::uint32_t p = lane; p < partitions; p += 64)
+        bound = __builtin_fminf(bound, bounds[(std::uint64_t)q * partitions + p]);
+#pragma unroll
+    for (int offset = 32; offset >= 1; offset >>= 1)
+        bound = __builtin_fminf(bound, xor_lane(bound, offset));
+
+    float worst = 0.f;
+    std::uint32_t measured = 0;
+    bool nan_seen = false;
+    for (std::uint32_t p = 0; p < partitions; ++p) {
+        const std::uint64_t cell = (std::uint64_t)q * partitions + p;
+        const std::uint32_t appended = uniform_u32(contender_counts[cell]);
+        const std::uint32_t held = appended < capacity ? appended : capacity; // (more were appended: the query was handed over)
+        for (std::uint32_t base = 0; base < held; base += 64) {
+            const bool inside = base + lane < held;
+            const std::uint64_t at = cell * capacity + base + lane;
+            const std::uint32_t slot = inside ? contender_slots[at] : 0u;
+            const bool stays = inside && !(contender_lows[at] > bound);
+            const std::uint64_t stays_mask = ballot(stays);
+            const std::uint32_t count = popcount64(stays_mask);
+            if (!count)
+                continue;
+            if (stays)
+                cand_slots[rank_below(stays_mask, lane)] = slot;
+            wave_sync<false>();
+            measure_rows<metric_ak, scalar_ak, lanes_ak, unroll_ak, false>(ix, query_lds, a2, cand_slots, cand_distances, count);
+            const float mine = lane < count ? cand_distances[lane] : 0.f;
+            const std::uint32_t mine_slot = lane < count ? cand_slots[lane] : 0u;
+            nan_seen = nan_seen || ballot(mine != mine) != 0;
+            measured += count;
+            // `exact_kernel`'s loop, word for word
+            std::uint64_t pending = ballot(lane < count && (top.size < wanted || !(mine > worst)));
+            while (pending) {
+                const std::uint32_t i = (std::uint32_t)__ffsll((long long)pending) - 1;
+                pending &= pending - 1;
+                const float d = read_lane_f32(mine, i);
+                if (top.size == wanted && d > worst)
+                    continue;
+                top.insert(d, read_lane_u32(mine_slot, i), wanted, worst);
+            }
+            wave_sync<false>();
+        }
+    }
+    const std::uint64_t row = (std::uint64_t)q * wanted;
+    for (std::uint32_t i = lane; i < wanted; i += 64) {
+        std::uint64_t key = 0;
+        std::uint32_t bits = signaling_nan_bits_k;
+        if (i < top.size) {
+            const cand_t c = top.cells[i];
+            key = map_keys ? ix.keys[cand_slot(c)] : (std::uint64_t)cand_slot(c);
+            bits = (std::uint32_t)c;
+        }
+        out_keys[row + i] = key;
+        reinterpret_cast<std::uint32_t*>(out_distances)[row + i] = bits;
+    }
+    if (lane == 0) {
+        out_counts[q] = top.size;
+        if (remeasured)
+            remeasured[q] = measured;
+        if (nan_seen)
+            handed[q] = 1u;
+    }
+}
+
 } // namespace usearch_amd

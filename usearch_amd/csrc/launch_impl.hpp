@@ -183,6 +183,32 @@ hipError_t launch_exact_metric(const exact_params_t& p, const snapshot_view_t& v
     }
 }
 
+/// The screened exact search's closing pass: the lanes / unroll pair `launch_exact_one` gives `exact_kernel` — the distance bits
+/// depend on the instantiation, and they have to be that kernel's.
+template <int metric_ak, int scalar_ak, int lanes_ak>
+hipError_t launch_exact_remeasure_one(const exact_remeasure_params_t& p, const snapshot_view_t& view) {
+    auto kernel = exact_remeasure_kernel<metric_ak, scalar_ak, lanes_ak, lanes_ak == 8 ? 8 : 4>;
+    hipLaunchKernelGGL(kernel, dim3(p.query_count), dim3(64), p.lds_bytes, p.stream, view, p.queries, p.query_stride, p.wanted,
+                       p.partitions, p.capacity, p.contender_slots, p.contender_lows, p.contender_counts, p.bounds, p.map_keys,
+                       p.handed, p.out_distances, p.out_keys, p.out_counts, p.remeasured);
+    return hipGetLastError();
+}
+
+template <int metric_ak, int scalar_ak>
+hipError_t launch_exact_remeasure_metric(const exact_remeasure_params_t& p, const snapshot_view_t& view) {
+    switch (p.lanes) {
+    case 1: return launch_exact_remeasure_one<metric_ak, scalar_ak, 1>(p, view);
+    case 2: return launch_exact_remeasure_one<metric_ak, scalar_ak, 2>(p, view);
+    case 4: // as `launch_exact_metric`: only ever forced
+        if constexpr (all_kernel_builds((metric_kind_t)metric_ak, (scalar_kind_t)scalar_ak))
+            return launch_exact_remeasure_one<metric_ak, scalar_ak, 4>(p, view);
+        else
+            return hipErrorInvalidValue;
+    case 8: return launch_exact_remeasure_one<metric_ak, scalar_ak, 8>(p, view);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 } // namespace usearch_amd
 
 #include "build_launch_impl.hpp" // the link kernels' launchers (not part of the walk's sources)
@@ -203,6 +229,12 @@ namespace usearch_amd {
     }                                                                                                                  \
     hipError_t launch_build_##name(const build_params_t& p, const snapshot_view_t& view, const build_args_t& args) {   \
         return launch_build_metric<metric_kind, scalar_kind>(p, view, args);                                           \
+    }
+
+/// The three f32 units (cos, ip, l2sq) carry the screened exact search's closing pass besides.
+#define USEARCH_AMD_DEFINE_SCREENED_LAUNCHER(name, metric_kind, scalar_kind)                                           \
+    hipError_t launch_exact_remeasure_##name(const exact_remeasure_params_t& p, const snapshot_view_t& view) {         \
+        return launch_exact_remeasure_metric<metric_kind, scalar_kind>(p, view);                                       \
     }
 
 } // namespace usearch_amd

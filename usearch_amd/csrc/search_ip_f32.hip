@@ -2,4 +2,5 @@
 #include "launch_impl.hpp"
 namespace usearch_amd {
 USEARCH_AMD_DEFINE_LAUNCHERS(ip_f32, metric_ip_k, scalar_f32_k)
+USEARCH_AMD_DEFINE_SCREENED_LAUNCHER(ip_f32, metric_ip_k, scalar_f32_k)
 }

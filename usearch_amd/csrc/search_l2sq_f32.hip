@@ -2,4 +2,5 @@
 #include "launch_impl.hpp"
 namespace usearch_amd {
 USEARCH_AMD_DEFINE_LAUNCHERS(l2sq_f32, metric_l2sq_k, scalar_f32_k)
+USEARCH_AMD_DEFINE_SCREENED_LAUNCHER(l2sq_f32, metric_l2sq_k, scalar_f32_k)
 }

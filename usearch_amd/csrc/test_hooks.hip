@@ -645,6 +645,23 @@ extern "C" __attribute__((visibility("default"))) int usearch_amd_test_plan_exac
     return 1;
 }
 
+// ---- and for the screened route (exact_screened.hip): its table (`exact_screened_pair`) and its planner (`plan_exact_screened`;
+//      `scratch_limit`: the bytes the device could spare, which the product asks the runtime for), for tests/test_exact_screened_plan.py.
+extern "C" __attribute__((visibility("default"))) int usearch_amd_test_exact_screened_pair(int metric, int scalar, uint64_t wanted) {
+    return usearch_amd::exact_screened_pair((usearch_amd::metric_kind_t)metric, (usearch_amd::scalar_kind_t)scalar, wanted) ? 1 : 0;
+}
+extern "C" __attribute__((visibility("default"))) int usearch_amd_test_plan_exact_screened(uint64_t rows, uint64_t bytes_per_vector,
+                                                                                           uint64_t row_stride, uint64_t count,
+                                                                                           uint64_t wanted, uint64_t scratch_limit,
+                                                                                           usearch_amd::exact_screened_plan_t* plan,
+                                                                                           usearch_amd_error_t* error) {
+    if (const char* e = usearch_amd::plan_exact_screened(rows, bytes_per_vector, row_stride, count, wanted, scratch_limit, *plan)) {
+        fail(error, e);
+        return 0;
+    }
+    return 1;
+}
+
 // ---- the k-means assignment's planner (kmeans_plan.hpp) on plain values, for the route assertions of tests/test_gpu_kmeans_wide.py:
 //      which tile `count` points against `clusters` centroids take, quantised rows `stride` bytes apart. `forced_tile` < 0 = the
 //      environment (USEARCH_AMD_KMEANS_TILE), read as kmeans.hip reads it.

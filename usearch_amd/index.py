@@ -164,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "usearch_amd_last_distances_ms", "usearch_amd_merge_many", "usearch_amd_merge_many_device",
     "usearch_amd_exact_search_many", "usearch_amd_exact_search_many_tiled", "usearch_amd_exact_search_dataset",
     "usearch_amd_exact_search_many_device", "usearch_amd_exact_search_dataset_tiled",
+    "usearch_amd_exact_search_many_screened", "usearch_amd_exact_search_dataset_screened",
     "usearch_amd_cluster_many",
     "usearch_amd_clustering", "usearch_amd_clustering_members", "usearch_amd_snapshot_live_keys",
     "usearch_amd_filter_from_key_range", "usearch_amd_filter_from_keys", "usearch_amd_filter_from_bits",
@@ -270,6 +271,7 @@ def library() -> C.CDLL:
     L.usearch_amd_exact_search_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), err_p]
     L.usearch_amd_exact_search_many_tiled.argtypes = L.usearch_amd_exact_search_many.argtypes
+    L.usearch_amd_exact_search_many_screened.argtypes = L.usearch_amd_exact_search_many.argtypes[:-1] + [C.c_void_p, err_p]
     L.usearch_amd_exact_search_many_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float),
                                                        C.POINTER(C.c_char_p)]
@@ -277,6 +279,7 @@ def library() -> C.CDLL:
                                                    C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p,
                                                    C.c_size_t, C.c_void_p, C.c_size_t, err_p]
     L.usearch_amd_exact_search_dataset_tiled.argtypes = L.usearch_amd_exact_search_dataset.argtypes
+    L.usearch_amd_exact_search_dataset_screened.argtypes = L.usearch_amd_exact_search_dataset.argtypes[:-1] + [C.c_void_p, err_p]
     L.usearch_amd_filter_from_key_range.restype = C.c_void_p
     L.usearch_amd_filter_from_key_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, err_p]
     L.usearch_amd_filter_from_keys.restype = C.c_void_p
@@ -709,7 +712,11 @@ class Index:
         """`Index.search` (index.py:700-748): one vector → `Matches`, a 2-D batch → `BatchMatches`.
 
         `dtype` names the scalar kind of `vectors` when numpy cannot tell (bit-packed `b1` rows are `uint8`);
-        by default it is derived from the array's dtype, `uint8` meaning bits."""
+        by default it is derived from the array's dtype, `uint8` meaning bits.
+
+        `exact="screened"` (cos / ip / l2sq over f32): `exact=True`'s keys and distance bits from a batched route; `computed` then holds
+        the rows measured per query (every live row for a query handed to the wave kernel whole). With a `filter` the C entry has no
+        such output and `computed` stays zero: whether the screen ran is not reported on that path."""
         vectors = np.asarray(vectors)
         single = vectors.ndim == 1
         if single:
@@ -732,14 +739,25 @@ class Index:
         stats = Stats()
         err = C.c_char_p()
         if exact and filter is not None:  # brute force over the members the filter lets through (index.hpp:4260-4263)
+            # (exact="screened" too, `tiled` = 2 — but the filtered entry has no `remeasured` output: `computed` stays zero here)
             kernel_ms = C.c_float()
             library().usearch_amd_filtered_exact_search_many(
                 self._handle, filter._handle, _pointer(vectors), SCALAR_KINDS[dtype], q,
                 vectors.shape[1] * vectors.itemsize if q <= 1 else vectors.strides[0], count, _pointer(keys), _pointer(distances),
-                _pointer(counts), int(exact == "tiled"), C.byref(kernel_ms), C.byref(err))
+                _pointer(counts), 2 if exact == "screened" else int(exact == "tiled"), C.byref(kernel_ms), C.byref(err))
             _raise(err, "usearch_amd_filtered_exact_search_many")
             stats.kernel_ms = kernel_ms.value
             batch = BatchMatches(keys, distances, counts, 0, 0, visited, computed, stats)
+            return batch[0] if single else batch
+        if exact == "screened":  # the matrix units rule rows out, the wave kernel measures the rest: exact=True's bits (exact_screened.hip)
+            kernel_ms = C.c_float()
+            library().usearch_amd_exact_search_many_screened(
+                self._handle, _pointer(vectors), SCALAR_KINDS[dtype], q,
+                vectors.shape[1] * vectors.itemsize if q <= 1 else vectors.strides[0], count, _pointer(keys), _pointer(distances),
+                _pointer(counts), C.byref(kernel_ms), _pointer(computed), C.byref(err))
+            _raise(err, "usearch_amd_exact_search_many_screened")
+            stats.kernel_ms = kernel_ms.value
+            batch = BatchMatches(keys, distances, counts, 0, int(computed.sum()), visited, computed, stats)  # computed: rows measured
             return batch[0] if single else batch
         if exact:  # brute force over every stored vector (Index.search(..., exact=True), index.py:700-748)
             kernel_ms = C.c_float()
@@ -802,14 +820,15 @@ class Index:
         return stats
 
     def exact_search_device(self, queries_ptr: int, queries_count: int, queries_stride: int, count: int, keys_ptr: int,
-                            distances_ptr: int, counts_ptr: int, stream: int = 0, tiled: bool = True) -> float:
+                            distances_ptr: int, counts_ptr: int, stream: int = 0, tiled: Union[bool, str] = True) -> float:
         """Exact search of an HBM-resident batch into HBM-resident results (`search(…, exact = true)` of the class for a batch);
-        returns the kernels' HIP-event time in ms. `tiled`: the matrix-unit kernel (exact_tiled.hip), for b1 the bit tile (exact_bits.hip)."""
+        returns the kernels' HIP-event time in ms. `tiled`: the matrix-unit kernel (exact_tiled.hip), for b1 the bit tile (exact_bits.hip);
+        "screened": the screened route (exact_screened.hip: cos / ip / l2sq over f32, the wave kernel's bits)."""
         kernel_ms = C.c_float(0)
         err = C.c_char_p()
         library().usearch_amd_exact_search_many_device(self._handle, C.c_void_p(queries_ptr), queries_count, queries_stride,
                                                        count, C.c_void_p(keys_ptr), C.c_void_p(distances_ptr),
-                                                       C.c_void_p(counts_ptr), C.c_void_p(stream), int(tiled),
+                                                       C.c_void_p(counts_ptr), C.c_void_p(stream), 2 if tiled == "screened" else int(tiled),
                                                        C.byref(kernel_ms), C.byref(err))
         _raise(err, "usearch_amd_exact_search_many_device")
         return float(kernel_ms.value)
@@ -1095,13 +1114,15 @@ def build(vectors, metric: str = "cos", dtype: Optional[str] = None, *, keys: Op
 
 
 def exact_search(dataset: np.ndarray, queries: np.ndarray, count: int, metric: str = "cos",
-                 dtype: Optional[str] = None, tiled: bool = False):
+                 dtype: Optional[str] = None, tiled: Union[bool, str] = False):
     """`usearch.index.search(dataset, queries, count, exact=True)` (index.py:1608-1700) → (keys = row offsets [Q, k],
     distances [Q, k]); both matrices in the same scalar kind, rows may be strided. `tiled`: the matrix-unit kernel
     (csrc/exact_tiled.hip) over the uploaded rows — cos / ip / l2sq over f16, bf16, i8 and f8, cos / ip over f32 — or the bit tile
     (csrc/exact_bits.hip: hamming / tanimoto / jaccard / sorensen over b1, the wave kernel's bits), count ≤ 64, any
     other pair is refused; float distances then lie within a derived bound of the f64 distance instead of being the wave kernel's bits (f32:
-    not promised within 1e-5 of them). The default stays the bit-exact wave-per-query kernel.
+    not promised within 1e-5 of them). The default stays the bit-exact wave-per-query kernel. `tiled="screened"`: the screened route
+    (csrc/exact_screened.hip) — cos / ip / l2sq over f32, count ≤ 64, any other pair refused: the matrix units rule rows out, the
+    wave kernel measures the rest, so keys and distance bits are the default's.
     f8: `uint8` matrices of OCP e4m3 codes (`cast_rows` makes them), `dtype="f8"` named — a `uint8` matrix alone reads as b1. Tiled
     exact search is ALL f8 has so far: `tiled=False` refuses it, and so do `build`, `Index.restore`, the walk and `kmeans`."""
     dataset, queries = np.asarray(dataset), np.asarray(queries)
@@ -1112,6 +1133,12 @@ def exact_search(dataset: np.ndarray, queries: np.ndarray, count: int, metric: s
     keys = np.zeros((len(queries), count), dtype=np.uint64)
     distances = np.zeros((len(queries), count), dtype=np.float32)
     err = C.c_char_p()
+    if tiled == "screened":
+        library().usearch_amd_exact_search_dataset_screened(
+            _pointer(dataset), len(dataset), dataset.strides[0], _pointer(queries), len(queries), queries.strides[0], SCALAR_KINDS[dtype],
+            ndim, metric_kind, count, _pointer(keys), keys.strides[0], _pointer(distances), distances.strides[0], None, C.byref(err))
+        _raise(err, "usearch_amd_exact_search_dataset_screened")
+        return keys, distances
     entry = "usearch_amd_exact_search_dataset_tiled" if tiled else "usearch_amd_exact_search_dataset"
     getattr(library(), entry)(_pointer(dataset), len(dataset), dataset.strides[0], _pointer(queries), len(queries),
                               queries.strides[0], SCALAR_KINDS[dtype], ndim, metric_kind, count, _pointer(keys), keys.strides[0],
@@ -1306,6 +1333,10 @@ def test_hooks() -> C.CDLL:
         _test_hooks.usearch_amd_test_exact_tiled_pair.argtypes = [C.c_int, C.c_int, C.c_uint64]
         _test_hooks.usearch_amd_test_exact_bits_pair.restype = C.c_int
         _test_hooks.usearch_amd_test_exact_bits_pair.argtypes = [C.c_int, C.c_int, C.c_uint64]
+        _test_hooks.usearch_amd_test_exact_screened_pair.restype = C.c_int
+        _test_hooks.usearch_amd_test_exact_screened_pair.argtypes = [C.c_int, C.c_int, C.c_uint64]
+        _test_hooks.usearch_amd_test_plan_exact_screened.restype = C.c_int
+        _test_hooks.usearch_amd_test_plan_exact_screened.argtypes = [C.c_uint64] * 6 + [C.c_void_p, C.POINTER(C.c_char_p)]
         _test_hooks.usearch_amd_test_plan_exact_bits.restype = C.c_int
         _test_hooks.usearch_amd_test_plan_exact_bits.argtypes = [C.c_uint64] * 5 + [C.c_void_p, C.POINTER(C.c_char_p)]
         _test_hooks.usearch_amd_test_plan_kmeans_assign.restype = None
@@ -1396,6 +1427,31 @@ def test_exact_tiled_pair(metric: str, dtype: str, wanted: int) -> bool:
 
 # the bit tile's plan (csrc/exact_plan.hpp: exact_bits_plan_t)
 ExactBitsPlan = _struct("ExactBitsPlan", (C.c_uint64, "query_tiles partitions rows_per_partition padded_queries padded_query_bytes lds_bytes"))
+
+
+def test_exact_screened_pair(metric: str, dtype: str, wanted: int) -> bool:
+    """Does the screened route (csrc/exact_screened.hip) take `metric` over `dtype` rows for `wanted` results per query? The table of
+    csrc/exact_plan.hpp (`exact_screened_pair`): cos, ip and l2sq over f32, 1 … 64 results; no GPU involved."""
+    metric_kind = ord({"ip": "i", "cos": "c", "l2sq": "e", "hamming": "b", "pearson": "p", "haversine": "h", "divergence": "d",
+                       "jaccard": "j", "tanimoto": "t", "sorensen": "s"}[metric])  # metric_kind_t and scalar_kind_t of csrc/common.hpp
+    scalar_kind = {"b1": 1, "bf16": 4, "f64": 10, "f32": 11, "f16": 12, "f8": 13, "i8": 23}[dtype]
+    return bool(test_hooks().usearch_amd_test_exact_screened_pair(metric_kind, scalar_kind, wanted))
+
+
+# the screened route's plan (csrc/exact_plan.hpp: exact_screened_plan_t)
+ExactScreenedPlan = _struct("ExactScreenedPlan", (C.c_uint64, "query_tiles partitions rows_per_partition capacity scratch_bytes"))
+
+
+def test_plan_exact_screened(rows: int, bytes_per_vector: int, row_stride: int, count: int, wanted: int,
+                             scratch_limit: int = 1 << 62) -> dict:
+    """The screened route's planner (csrc/exact_plan.hpp, `plan_exact_screened`) on plain values, no GPU involved: the grid of (query
+    tiles of 64, row partitions), the contenders a (query, partition) buffer holds and the device memory the call takes in all;
+    `scratch_limit`: what the device could spare. → the fields of `ExactScreenedPlan` as a dict; a refusal raises."""
+    plan, err = ExactScreenedPlan(), C.c_char_p()
+    test_hooks().usearch_amd_test_plan_exact_screened(rows, bytes_per_vector, row_stride, count, wanted, scratch_limit, C.byref(plan),
+                                                      C.byref(err))
+    _raise(err, "usearch_amd_test_plan_exact_screened")
+    return plan.as_dict()
 
 
 def test_exact_bits_pair(metric: str, dtype: str, wanted: int) -> bool:
