@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """scripts/kernel_registers.py <remarks file> [filter] — tabulates what `hipcc -Rpass-analysis=kernel-resource-usage` reports
-for every `search_kernel` instantiation of one translation unit: VGPRs, spills, waves per SIMD. Template arguments are
+for every `search_kernel` instantiation of one translation unit: VGPRs, spills, waves per SIMD, scratch, static LDS. Template arguments are
 <metric, scalar, lanes per row, variant, scratch mode, top cells per lane, frontier>."""
 import re
 import subprocess
@@ -19,7 +19,7 @@ for block in re.split(r"remark: (?:\S+: )?Function Name: ", text)[1:]:  # with o
         return int(found.group(1)) if found else -1
 
     arguments = re.search(r"<(.*?)>", pretty)
-    waves, scratch = field(r"Occupancy \[waves/SIMD\]"), field(r"ScratchSize \[bytes/lane\]")
+    waves, scratch, lds = field(r"Occupancy \[waves/SIMD\]"), field(r"ScratchSize \[bytes/lane\]"), field(r"LDS Size \[bytes/block\]")
     print(f"{pretty.split('<')[0].split()[-1]}<{arguments.group(1) if arguments else ''}>  VGPRs {field('VGPRs')}  "
           f"AGPRs {field('AGPRs')}  spilled {field('VGPRs Spill')}  SGPR spills {field('SGPRs Spill')}  waves/SIMD {waves}  "
-          f"scratch {scratch}")
+          f"scratch {scratch}  LDS {lds}")

@@ -1,7 +1,12 @@
 /**
  *  usearch_amd/csrc/device_math.hpp — what several kernel files must agree on TO THE BIT, stated once: the matrix-unit product and
- *  its fragment geometry, the 64 × 128 staged tile, Σx² of a row, the metrics' closing arithmetic, the order-preserving float →
- *  u32 map. Users: exact_tiled.hip (both tiles), kmeans.hip (the assignment), join.hip and clustering.hip (ordered bits).
+ *  its fragment geometry; the 64 × 128 staged tile — its LDS layout, the stream that brings a step's rows global → registers → LDS
+ *  (`staged_rows_gt`, `staged_stream_gt`), the product of a chunk and the pipelined product of a B tile; Σx² of a row; the metrics'
+ *  closing arithmetic; the order-preserving float → u32 map; "a live member the caller allows" (`row_is_allowed`).
+ *  Users: exact_tiled.hip (`exact_tiled_kernel`: the stream and the product of a chunk; the wide tile: `multiply` and the geometry),
+ *  exact_screened.hip (`screen_kernel`) and kmeans.hip (`assign_tiled_kernel`, `assign_screened_kernel`; the wide tile as above): the
+ *  pipelined product — screen_math.hpp, built on this header, holds what the two screens share besides — exact_bits.hip (the closing
+ *  arithmetic, `row_is_allowed`), wide_stage.hpp (`chunk_bytes_k`), join.hip and clustering.hip (ordered bits).
  *  Depends on common.hpp and the HIP runtime only — kmeans.o is linked without the engine.
  *
  *  Fragment geometry of `v_mfma_f32_32x32x16_{f16,bf16}` / `v_mfma_i32_32x32x32_i8` / `v_mfma_f32_32x32x2_f32`. Both operands are
@@ -30,6 +35,7 @@
 namespace usearch_amd {
 
 // ---- the staged tile: a workgroup of 4 waves multiplies 64 A rows with 128 B rows, `chunk_bytes_k` bytes of every row at a time
+constexpr int staged_a_rows_k = 64, staged_b_rows_k = 128;
 constexpr int chunk_bytes_k = 128;          ///< bytes of every row staged per step of the summation loop (4 MFMA steps of 32 bytes)
 constexpr int pitch_k = chunk_bytes_k + 16; ///< LDS row pitch: keeps 16-byte reads of consecutive rows off the same banks
 
@@ -123,6 +129,128 @@ __device__ __forceinline__ void multiply_staged_chunk(const std::uint8_t* stage_
             acc[t] = multiply<scalar_ak>(a, b, acc[t]);
         }
     }
+}
+
+/// One operand's rows in global memory, as the staged tile reads them. A tile's rows at and beyond `end` and a row's bytes at and
+/// beyond `bytes` are staged as zeros. `row_at`, `stride_at`: the caller's own integer widths (row numbers of 32 bits are compared
+/// in 32 bits). `ragged_ak`: a caller's query batch — a row may end inside a 16-byte piece, and nothing is promised about alignment.
+template <typename row_at, typename stride_at, bool ragged_ak = false> struct staged_rows_gt {
+    using row_t = row_at;
+    static constexpr bool ragged_k = ragged_ak;
+    const std::uint8_t* base; ///< of row 0
+    stride_at stride;         ///< bytes from a row to the next
+    row_at first, end;        ///< the rows the workgroup multiplies: A rows [first, first + 64), B tiles of 128 rows from `first` on
+    std::uint32_t bytes;      ///< of every row that may be read — the caller's bound; whole 16-byte pieces unless `ragged_ak`
+    bool aligned;             ///< `base` and `stride` are multiples of 16: 16-byte loads are safe (always, unless `ragged_ak`)
+};
+
+/// A snapshot's stored rows [first, end): 16-byte aligned and zero padded to whole 16-byte pieces (`ix.chunks`).
+__device__ __forceinline__ staged_rows_gt<std::uint64_t, std::uint32_t> stored_rows(const snapshot_view_t& ix, std::uint64_t first,
+                                                                                   std::uint64_t end) {
+    return {ix.vectors, ix.row_stride, first, end, ix.chunks * 16u, true};
+}
+/// Rows [first, end) of a caller's query batch, `bytes` each, at whatever stride and alignment.
+__device__ __forceinline__ staged_rows_gt<std::uint32_t, std::uint64_t, true> query_rows(const std::uint8_t* queries, std::uint64_t stride,
+                                                                                         std::uint32_t first, std::uint32_t end,
+                                                                                         std::uint32_t bytes) {
+    return {queries, stride, first, end, bytes, stride % 16 == 0 && (std::uintptr_t)queries % 16 == 0};
+}
+
+/// 16 bytes of a row from `byte` on; byte by byte where a ragged operand's row ends inside them or the operand is not aligned.
+template <typename rows_at> __device__ __forceinline__ i32x4_t fetch_staged_piece(const rows_at& rows, typename rows_at::row_t row, std::uint32_t byte) {
+    i32x4_t value = {0, 0, 0, 0}; // (one 128-bit value, not HIP's struct of four: nothing tempts the compiler to take it apart)
+    if (row < rows.end && byte < rows.bytes) {
+        const std::uint8_t* source = rows.base + (std::uint64_t)row * rows.stride + byte;
+        if (!rows_at::ragged_k || (byte + 16 <= rows.bytes && rows.aligned))
+            value = *reinterpret_cast<const i32x4_t*>(source);
+        else {
+            std::uint8_t parts[16] = {0};
+#pragma clang loop vectorize(disable) unroll(disable) // (the rare path stays one small loop: widened eight times, its 16-way
+                                                      // selects are half of a kernel's code)
+            for (std::uint32_t b = 0; b < 16 && byte + b < rows.bytes; ++b)
+                parts[b] = source[b];
+            value = *reinterpret_cast<const i32x4_t*>(parts);
+        }
+    }
+    return value;
+}
+
+/**
+ *  The staged tile's stream: the rows of a step (B tile, chunk) travel global → registers → LDS. 8 consecutive threads take one
+ *  row's 128 bytes of the chunk, 16 each; a thread makes two passes of A rows and four of B rows (row 32·pass + thread / 8 of the
+ *  tile): six 16-byte loads (`fetch`), six LDS stores (`stash`). The registers in between are what lets the NEXT step's rows fly
+ *  behind this step's products (`multiply_staged_tile`). The byte-by-byte path exists only where A is a ragged operand
+ *  (`query_rows`); B is never one.
+ */
+template <typename a_rows_at, typename b_rows_at> struct staged_stream_gt {
+    static_assert(!b_rows_at::ragged_k, "B rows are read in whole 16-byte pieces");
+    using b_row_t = typename b_rows_at::row_t;
+    a_rows_at a;
+    b_rows_at b;
+    std::uint8_t* stage; ///< LDS: [64][pitch_k] of A, then [128][pitch_k] of B
+    std::uint32_t thread;
+    i32x4_t fetched[(staged_a_rows_k + staged_b_rows_k) / 32];
+
+    __device__ __forceinline__ staged_stream_gt(a_rows_at a_rows, b_rows_at b_rows, std::uint8_t* lds, std::uint32_t thread_in_block)
+        : a(a_rows), b(b_rows), stage(lds), thread(thread_in_block) {}
+    __device__ __forceinline__ std::uint8_t* stage_a() const { return stage; }
+    __device__ __forceinline__ std::uint8_t* stage_b() const { return stage + staged_a_rows_k * pitch_k; }
+
+    /// Requests chunk `chunk` of the A rows and of the B tile that begins at row `b_row`.
+    __device__ __forceinline__ void fetch(b_row_t b_row, std::uint32_t chunk) {
+        const std::uint32_t byte = chunk * chunk_bytes_k + thread % 8 * 16;
+#pragma unroll
+        for (std::uint32_t pass = 0; pass < staged_a_rows_k / 32; ++pass)
+            fetched[pass] = fetch_staged_piece(a, a.first + pass * 32 + thread / 8, byte);
+#pragma unroll
+        for (std::uint32_t pass = 0; pass < staged_b_rows_k / 32; ++pass)
+            fetched[staged_a_rows_k / 32 + pass] = fetch_staged_piece(b, b_row + pass * 32 + thread / 8, byte);
+    }
+    /// What was fetched, into the staging area (the caller's barrier follows).
+    __device__ __forceinline__ void stash() {
+#pragma unroll
+        for (std::uint32_t pass = 0; pass < staged_a_rows_k / 32; ++pass)
+            *reinterpret_cast<i32x4_t*>(stage_a() + (pass * 32 + thread / 8) * pitch_k + thread % 8 * 16) = fetched[pass];
+#pragma unroll
+        for (std::uint32_t pass = 0; pass < staged_b_rows_k / 32; ++pass)
+            *reinterpret_cast<i32x4_t*>(stage_b() + (pass * 32 + thread / 8) * pitch_k + thread % 8 * 16) = fetched[staged_a_rows_k / 32 + pass];
+    }
+};
+
+/**
+ *  The pipelined product of the A rows with the B tile that begins at row `b_row`, whose chunk 0 has been fetched: `acc` = 0, then
+ *  per chunk stash, barrier, request the next step's rows — the next chunk, or chunk 0 of the next B tile if there is one: that
+ *  flight crosses the caller's epilogue — `multiply_staged_chunk`, barrier. `announce` runs between the zeroing and
+ *  the first barrier: the caller's per-tile norms and flags in LDS, which nobody reads before that barrier.
+ */
+template <int scalar_ak, typename stream_at, typename announce_at>
+__device__ __forceinline__ void multiply_staged_tile(stream_at& stream, typename stream_at::b_row_t b_row, std::uint32_t chunks,
+                                                     typename accumulator_gt<scalar_ak>::type (&acc)[2], announce_at&& announce) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            acc[t][r] = 0;
+    announce();
+    for (std::uint32_t chunk = 0; chunk < chunks; ++chunk) {
+        stream.stash();
+        __syncthreads();
+        if (chunk + 1 < chunks)
+            stream.fetch(b_row, chunk + 1);
+        else if (b_row + staged_b_rows_k < stream.b.end)
+            stream.fetch(b_row + staged_b_rows_k, 0);
+        multiply_staged_chunk<scalar_ak>(stream.stage_a(), stream.stage_b(), stream.thread / 64, stream.thread % 64, acc);
+        __syncthreads();
+    }
+}
+
+/// Row `row` of the snapshot is a live member the caller allows: no tombstone, and the row's bit of `allow_bits` set (one bit per
+/// slot, index.hpp:4260-4263; null = no predicate).
+__device__ __forceinline__ bool row_is_allowed(const snapshot_view_t& ix, const std::uint32_t* allow_bits, std::uint64_t row) {
+    bool member = !ix.has_tombstones || ix.keys[row] != free_key_k;
+    if (allow_bits && member)
+        member = ((allow_bits[row >> 5] >> (row & 31)) & 1u) != 0;
+    return member;
 }
 
 /**

@@ -176,10 +176,7 @@ __global__ __launch_bounds__(bits_waves_k * 64) void exact_bits_kernel(const sna
         const std::uint64_t row = base + lane;
         const bool inside = row < last_row;
         // the `allow` predicate as `exact_kernel` has it: tombstones, then the caller's one bit per slot
-        bool member = inside && (!ix.has_tombstones || ix.keys[row] != free_key_k);
-        if (allow_bits && member)
-            member = ((allow_bits[row >> 5] >> (row & 31)) & 1u) != 0;
-        const std::uint64_t members = __ballot(member);
+        const std::uint64_t members = __ballot(inside && row_is_allowed(ix, allow_bits, row));
         if (!members)
             continue;
         const std::uint64_t fetched = inside ? row : first_row; // a lane past the end reads a row that exists, and is never a member

@@ -15,8 +15,8 @@
 
 namespace usearch_amd {
 
-constexpr int tile_queries_k = 64;  ///< queries per workgroup
-constexpr int tile_rows_k = 128;    ///< dataset rows per inner tile
+constexpr int tile_queries_k = staged_a_rows_k; ///< queries per workgroup: 64
+constexpr int tile_rows_k = staged_b_rows_k;    ///< dataset rows per inner tile: 128
 constexpr int max_wanted_k = 64;    ///< per-query results the epilogue keeps (one lane per entry)
 
 constexpr int wide_queries_k = 256; ///< queries per workgroup: a row is read once per 256 queries

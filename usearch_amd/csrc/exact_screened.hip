@@ -7,12 +7,8 @@
  *  from Σa² + Σb² − 2Σab cancels. Here the tile's sums decide nothing but who CAN be among a query's `wanted` nearest:
  *
  *    1. `screen_kernel` — the 64-query × 128-row tile (`multiply_staged_chunk<scalar_f32_k>`, partitions of the rows as the tiled
- *       kernel has them). Per (query, row) a score s and an error e with |s − (d − c)·f| ≤ e, where d is the distance `measure_rows`
- *       gives the pair and c, f > 0 depend on the query alone (DESIGN.md §9 derives e for that kernel's lane-group sums;
- *       g = 4·(dimensions + 16)·2⁻²⁴, A = √Σa², B = √Σb² from `launch_row_norms<scalar_f32_k>`):
- *           l2sq  s = Σb² − 2Σab        e = g·(A + B)²
- *           ip    s = −Σab              e = g·A·B + 2⁻²³
- *           cos   s = −Σab / √Σb²       e = g·A
+ *       kernel has them). Per (query, row) the score s and the error e of screen_math.hpp, with `measure_rows` as the measuring
+ *       kernel (`screen_g_lane_groups`).
  *       Per (query, partition) the wave that owns the query keeps the ordered list of the `wanted` lowest upper bounds s + e it has
  *       seen (one lane per entry); τ is the last of them, +inf while the list is filling. A row with s − e ≤ τ is a contender: its
  *       slot and s − e are appended to the (query, partition) buffer. τ only falls, so the buffer is a superset of what the final τ
@@ -38,19 +34,11 @@
 #include "engine.hpp"
 #include "exact_plan.hpp"
 #include "host_util.hpp"
+#include "screen_math.hpp"
 
 namespace usearch_amd {
 
 namespace {
-
-constexpr float screen_least_square_k = 0x1p-60f, screen_most_square_k = 0x1p+60f;
-
-/// Σx² for which the derivation of e does not hold. `zero_too`: cos, whose closing arithmetic special-cases a zero norm.
-__device__ __forceinline__ bool square_out_of_band(float x2, bool zero_too) {
-    if (x2 == 0.f)
-        return zero_too;
-    return !(x2 >= screen_least_square_k && x2 <= screen_most_square_k); // a NaN is out of band
-}
 
 constexpr std::uint32_t row_live_k = 1u, row_out_of_band_k = 2u;
 
@@ -73,9 +61,7 @@ __global__ __launch_bounds__(256) void screen_kernel(const snapshot_view_t ix, c
                                                      std::uint32_t* contender_slots, float* contender_lows,
                                                      std::uint32_t* contender_counts, float* bounds, std::uint32_t* handed) {
     constexpr int scalar_ak = scalar_f32_k;
-    extern __shared__ __attribute__((aligned(16))) std::uint8_t lds[];
-    std::uint8_t* stage_q = lds;                                // [64][pitch]
-    std::uint8_t* stage_r = stage_q + tile_queries_k * pitch_k; // [128][pitch]
+    extern __shared__ __attribute__((aligned(16))) std::uint8_t lds[]; // the staged tile first: [64 + 128][pitch]
     float* tile_s = reinterpret_cast<float*>(lds);              // [64][129] scores, aliases the staging area after the products
     float* uppers = reinterpret_cast<float*>(lds + staged_tile_bytes(tile_queries_k, tile_rows_k)); // [64][max_wanted_k], ascending
     std::uint32_t* list_n = reinterpret_cast<std::uint32_t*>(uppers + tile_queries_k * max_wanted_k); // [64] entries of a list
@@ -92,7 +78,7 @@ __global__ __launch_bounds__(256) void screen_kernel(const snapshot_view_t ix, c
     const std::uint64_t last_row = first_row + rows_per_partition < ix.size ? first_row + rows_per_partition : ix.size;
     const std::uint32_t bytes = ix.bytes_per_vector;
     const std::uint32_t chunks = (bytes + chunk_bytes_k - 1) / chunk_bytes_k;
-    const float g = 4.f * (float)(ix.dimensions + 16) * 0x1p-24f;
+    const float g = screen_g_lane_groups(ix.dimensions);
     constexpr bool zero_too = metric_ak == metric_cos_k;
 
     if (thread < tile_queries_k) {
@@ -107,98 +93,26 @@ __global__ __launch_bounds__(256) void screen_kernel(const snapshot_view_t ix, c
     }
     __syncthreads();
 
-    // ---- staging: 8 consecutive threads fetch one row's 128 bytes of a chunk, the next chunk's while this one is multiplied
-    const std::uint32_t segment = thread % 8;
-    const bool queries_aligned = query_stride % 16 == 0 && (std::uintptr_t)queries % 16 == 0;
-    uint4 fetched[(tile_queries_k + tile_rows_k) / 32];
-    auto fetch = [&](std::uint64_t tile_row, std::uint32_t chunk) {
-        const std::uint32_t byte = chunk * chunk_bytes_k + segment * 16;
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_queries_k / 32; ++pass) {
-            const std::uint32_t i = pass * 32 + thread / 8;
-            uint4 value = {0u, 0u, 0u, 0u};
-            if (first_query + i < query_count && byte < bytes) {
-                const std::uint8_t* source = queries + (std::uint64_t)(first_query + i) * query_stride + byte;
-                if (byte + 16 <= bytes && queries_aligned)
-                    value = *reinterpret_cast<const uint4*>(source);
-                else { // ragged end of a row, or an unaligned batch: byte by byte
-                    std::uint8_t parts[16] = {0};
-                    for (std::uint32_t b = 0; b < 16 && byte + b < bytes; ++b)
-                        parts[b] = source[b];
-                    value = *reinterpret_cast<const uint4*>(parts);
-                }
-            }
-            fetched[pass] = value;
-        }
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_rows_k / 32; ++pass) {
-            const std::uint64_t row = tile_row + pass * 32 + thread / 8;
-            uint4 value = {0u, 0u, 0u, 0u};
-            // stored rows are 16-byte aligned and zero padded to whole 16-byte chunks (`ix.chunks`)
-            if (row < last_row && byte < ix.chunks * 16u)
-                value = *reinterpret_cast<const uint4*>(ix.vectors + row * ix.row_stride + byte);
-            fetched[tile_queries_k / 32 + pass] = value;
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_queries_k / 32; ++pass)
-            *reinterpret_cast<uint4*>(stage_q + (pass * 32 + thread / 8) * pitch_k + segment * 16) = fetched[pass];
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_rows_k / 32; ++pass)
-            *reinterpret_cast<uint4*>(stage_r + (pass * 32 + thread / 8) * pitch_k + segment * 16) = fetched[tile_queries_k / 32 + pass];
-    };
+    // ---- staging: the staged-tile stream of device_math.hpp, the next chunk's rows in flight while this one is multiplied
+    staged_stream_gt stream(query_rows(queries, query_stride, first_query, query_count, bytes), stored_rows(ix, first_row, last_row), lds, thread);
     if (first_row < last_row)
-        fetch(first_row, 0);
+        stream.fetch(first_row, 0);
 
     for (std::uint64_t tile_row = first_row; tile_row < last_row; tile_row += tile_rows_k) {
         f32x16_t acc[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                acc[t][r] = 0;
-        if (thread < tile_rows_k) { // read after the chunks' barriers; written again after the fold's
-            const std::uint64_t row = tile_row + thread;
-            const bool inside = row < last_row;
-            const float b2 = inside ? __builtin_bit_cast(float, row_norms[row]) : 0.f;
-            bool member = inside && (!ix.has_tombstones || ix.keys[row] != free_key_k);
-            if (allow_bits && member) // the caller's predicate, one bit per slot (index.hpp:4260-4263)
-                member = ((allow_bits[row >> 5] >> (row & 31)) & 1u) != 0;
-            squares_r[thread] = b2, roots_r[thread] = __builtin_sqrtf(b2);
-            flags_r[thread] = (member ? row_live_k : 0u) | (square_out_of_band(b2, zero_too) ? row_out_of_band_k : 0u);
-        }
-        for (std::uint32_t chunk = 0; chunk < chunks; ++chunk) {
-            stash();
-            __syncthreads();
-            if (chunk + 1 < chunks)
-                fetch(tile_row, chunk + 1);
-            else if (tile_row + tile_rows_k < last_row)
-                fetch(tile_row + tile_rows_k, 0);
-            multiply_staged_chunk<scalar_ak>(stage_q, stage_r, wave, lane, acc);
-            __syncthreads();
-        }
+        multiply_staged_tile<scalar_ak>(stream, tile_row, chunks, acc, [&] {
+            if (thread < tile_rows_k) { // read after the chunks' barriers; written again after the fold's
+                const std::uint64_t row = tile_row + thread;
+                const bool inside = row < last_row;
+                const float b2 = inside ? __builtin_bit_cast(float, row_norms[row]) : 0.f;
+                const bool member = inside && row_is_allowed(ix, allow_bits, row);
+                squares_r[thread] = b2, roots_r[thread] = __builtin_sqrtf(b2);
+                flags_r[thread] = (member ? row_live_k : 0u) | (square_out_of_band(b2, zero_too) ? row_out_of_band_k : 0u);
+            }
+        });
 
         // ---- scores of the tile into LDS (the staging area is free now): S[query][row of the tile]
-        {
-            const std::uint32_t j = wave * 32 + accumulator_column(lane);
-            const float b2 = squares_r[j], root_b = roots_r[j];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const std::uint32_t i = t * 32 + accumulator_row(r, lane);
-                    float score;
-                    if constexpr (metric_ak == metric_l2sq_k)
-                        score = b2 - 2.f * acc[t][r];
-                    else if constexpr (metric_ak == metric_ip_k)
-                        score = -acc[t][r];
-                    else
-                        score = -acc[t][r] / root_b; // (Σb² = 0 is out of band under cos: that score is never looked at)
-                    tile_s[i * (tile_rows_k + 1) + j] = score;
-                }
-            }
-        }
+        store_screen_scores<metric_ak>(acc, squares_r, roots_r, wave, lane, tile_s);
         __syncthreads();
 
         // ---- fold: wave w owns queries [16w, 16w + 16). Per half tile (lane ↔ row): the uppers that beat τ enter the list in
@@ -217,15 +131,7 @@ __global__ __launch_bounds__(256) void screen_kernel(const snapshot_view_t ix, c
                 const std::uint32_t j = half * 64 + lane;
                 const std::uint32_t flags = flags_r[j];
                 const bool live = (flags & row_live_k) != 0, banded = !(flags & row_out_of_band_k);
-                const float s = tile_s[i * (tile_rows_k + 1) + j];
-                float e;
-                if constexpr (metric_ak == metric_l2sq_k) {
-                    const float both = root_a + roots_r[j];
-                    e = g * both * both;
-                } else if constexpr (metric_ak == metric_ip_k)
-                    e = __builtin_fmaf(g * root_a, roots_r[j], 0x1p-23f);
-                else
-                    e = g * root_a;
+                const float s = tile_s[i * (tile_rows_k + 1) + j], e = screen_error<metric_ak>(g, root_a, roots_r[j]);
                 const float upper = s + e, lower = banded ? s - e : -__builtin_inff();
                 float tau = size == wanted ? list[size - 1] : __builtin_inff();
                 std::uint64_t pending = __ballot(live && banded && upper < tau);
@@ -293,10 +199,7 @@ __global__ __launch_bounds__(256) void count_allowed_kernel(const snapshot_view_
                                                             unsigned long long* out) {
     for (std::uint64_t base = ((std::uint64_t)blockIdx.x * 256 + threadIdx.x) / 64 * 64; base < ix.size; base += (std::uint64_t)gridDim.x * 256) {
         const std::uint64_t row = base + threadIdx.x % 64;
-        bool allowed = row < ix.size && (!ix.has_tombstones || ix.keys[row] != free_key_k);
-        if (allow_bits && allowed)
-            allowed = ((allow_bits[row >> 5] >> (row & 31)) & 1u) != 0;
-        const std::uint64_t mask = __ballot(allowed);
+        const std::uint64_t mask = __ballot(row < ix.size && row_is_allowed(ix, allow_bits, row));
         if (threadIdx.x % 64 == 0 && mask)
             atomicAdd(out, (unsigned long long)__popcll(mask));
     }

@@ -76,9 +76,7 @@ __global__ __launch_bounds__(256) void exact_tiled_kernel(const snapshot_view_t 
                                                           float* out_distances, std::uint64_t* out_keys,
                                                           std::uint64_t* out_counts) {
     using accumulator_t = typename accumulator_gt<scalar_ak>::type;
-    extern __shared__ __attribute__((aligned(16))) std::uint8_t lds[];
-    std::uint8_t* stage_q = lds;                                      // [64][pitch]
-    std::uint8_t* stage_r = stage_q + tile_queries_k * pitch_k;       // [128][pitch]
+    extern __shared__ __attribute__((aligned(16))) std::uint8_t lds[]; // the staged tile first: [64 + 128][pitch]
     float* tile_d = reinterpret_cast<float*>(lds);                    // [64][129], aliases the staging area after the products
     float* top_d = reinterpret_cast<float*>(lds + staged_tile_bytes(tile_queries_k, tile_rows_k)); // [64][max_wanted_k]
     std::uint32_t* top_s = reinterpret_cast<std::uint32_t*>(top_d + tile_queries_k * max_wanted_k);
@@ -99,6 +97,7 @@ __global__ __launch_bounds__(256) void exact_tiled_kernel(const snapshot_view_t 
         norms_q[thread] = first_query + thread < query_count ? query_norms[first_query + thread] : 0u;
     }
     __syncthreads();
+    staged_stream_gt stream(query_rows(queries, query_stride, first_query, query_count, bytes), stored_rows(ix, first_row, last_row), lds, thread);
 
     for (std::uint64_t tile_row = first_row; tile_row < last_row; tile_row += tile_rows_k) {
         accumulator_t acc[2];
@@ -111,43 +110,14 @@ __global__ __launch_bounds__(256) void exact_tiled_kernel(const snapshot_view_t 
             const std::uint64_t row = tile_row + thread;
             const bool inside = row < last_row;
             norms_r[thread] = inside ? row_norms[row] : 0u;
-            bool member = inside && (!ix.has_tombstones || ix.keys[row] != free_key_k);
-            if (allow_bits && member) // the caller's predicate, one bit per slot (index.hpp:4260-4263)
-                member = ((allow_bits[row >> 5] >> (row & 31)) & 1u) != 0;
-            valid_r[thread] = member ? 1u : 0u;
+            valid_r[thread] = inside && row_is_allowed(ix, allow_bits, row) ? 1u : 0u;
         }
         for (std::uint32_t chunk = 0; chunk < chunks; ++chunk) {
-            // ---- stage 128 bytes of every query and of every row of the tile: 8 consecutive threads fetch one row's 128 bytes
-            const std::uint32_t segment = thread % 8, byte = chunk * chunk_bytes_k + segment * 16;
-            {
-                for (std::uint32_t pass = 0; pass < tile_queries_k / 32; ++pass) {
-                    const std::uint32_t i = pass * 32 + thread / 8;
-                    uint4 value = {0u, 0u, 0u, 0u};
-                    if (first_query + i < query_count && byte < bytes) {
-                        const std::uint8_t* source = queries + (std::uint64_t)(first_query + i) * query_stride + byte;
-                        if (byte + 16 <= bytes && (query_stride % 16 == 0) && ((std::uintptr_t)queries % 16 == 0))
-                            value = *reinterpret_cast<const uint4*>(source);
-                        else { // ragged end of a row, or an unaligned batch: byte by byte
-                            std::uint8_t parts[16] = {0};
-                            for (std::uint32_t b = 0; b < 16 && byte + b < bytes; ++b)
-                                parts[b] = source[b];
-                            value = *reinterpret_cast<const uint4*>(parts);
-                        }
-                    }
-                    *reinterpret_cast<uint4*>(stage_q + i * pitch_k + segment * 16) = value;
-                }
-                for (std::uint32_t pass = 0; pass < tile_rows_k / 32; ++pass) {
-                    const std::uint32_t j = pass * 32 + thread / 8;
-                    const std::uint64_t row = tile_row + j;
-                    uint4 value = {0u, 0u, 0u, 0u};
-                    // stored rows are 16-byte aligned and zero padded to whole 16-byte chunks (`ix.chunks`)
-                    if (row < last_row && byte < ix.chunks * 16u)
-                        value = *reinterpret_cast<const uint4*>(ix.vectors + row * ix.row_stride + byte);
-                    *reinterpret_cast<uint4*>(stage_r + j * pitch_k + segment * 16) = value;
-                }
-            }
+            // ---- stage 128 bytes of every query and of every row of the tile, then multiply: no look-ahead here
+            stream.fetch(tile_row, chunk);
+            stream.stash();
             __syncthreads();
-            multiply_staged_chunk<scalar_ak>(stage_q, stage_r, wave, lane, acc);
+            multiply_staged_chunk<scalar_ak>(stream.stage_a(), stream.stage_b(), wave, lane, acc);
             __syncthreads();
         }
 

@@ -24,7 +24,7 @@
  *    cast         rows of the caller's kind → quantised rows, zero padded to 16 bytes (`cast_vector`'s bits; the i8 magnitude is an
  *                 f64 sum in ascending dimension order, one lane per row);
  *    assignment   f16 / bf16 / i8: a tile of 64 points × 128 centroids per step on `v_mfma_f32_32x32x16_{f16,bf16}` /
- *                 `v_mfma_i32_32x32x32_i8`. The product of a staged chunk, the fragment layout, Σx² and the closing arithmetic
+ *                 `v_mfma_i32_32x32x32_i8`. The staged tile's stream and product, the fragment layout, Σx² and the closing arithmetic
  *                 are device_math.hpp's — the very code the 64-query tile of exact search (exact_tiled.hip) runs, so the two close
  *                 a pair to the same bits (tests/test_gpu_kmeans.py) and i8 distances are bit-identical to the wave kernel's. The
  *                 epilogue keeps ONE (distance, index) per point under (distance ↑, centroid index ↑). The centroids (k · row
@@ -69,6 +69,7 @@
 #include "host_util.hpp"
 #include "kmeans.hpp"
 #include "kmeans_plan.hpp"
+#include "screen_math.hpp"
 #include "wide_stage.hpp"
 
 namespace usearch_amd {
@@ -201,9 +202,15 @@ __device__ __forceinline__ void publish_assignment(std::uint32_t point, bool ins
         atomicAdd(shifted, movers);
 }
 
+/// Rows [first, end) of one of k-means' own matrices as the staged tile reads them: `stride` bytes apart, 16-byte aligned and zero
+/// padded up to `stride`.
+__device__ __forceinline__ staged_rows_gt<std::uint32_t, std::uint32_t> kmeans_rows(const std::uint8_t* rows, std::uint32_t first, std::uint32_t end, std::uint32_t stride) {
+    return {rows, stride, first, end, stride, true};
+}
+
 /**
  *  grid = point tiles, 256 threads = 4 waves. Wave w multiplies all 64 points of the tile with centroids [32w, 32w + 32) of every
- *  centroid tile: two 32 × 32 accumulators. Rows of both matrices are `stride` bytes apart, 16-byte aligned and zero padded.
+ *  centroid tile: two 32 × 32 accumulators.
  */
 template <int metric_ak, int scalar_ak>
 __global__ __launch_bounds__(256) void assign_tiled_kernel(const std::uint8_t* points, std::uint32_t count, const std::uint8_t* centroids,
@@ -216,8 +223,6 @@ __global__ __launch_bounds__(256) void assign_tiled_kernel(const std::uint8_t* p
     __shared__ std::uint32_t part_i[4][tile_points_k];
     __shared__ std::uint32_t norms_p[tile_points_k];
     __shared__ std::uint32_t norms_c[tile_centroids_k];
-    std::uint8_t* stage_p = lds;                                 // [64][pitch]
-    std::uint8_t* stage_c = stage_p + tile_points_k * pitch_k;   // [128][pitch]
     float* tile_d = reinterpret_cast<float*>(lds);               // [64][129], aliases the staging area after the products
 
     const std::uint32_t thread = threadIdx.x, wave = thread / 64, lane = thread % 64;
@@ -231,59 +236,16 @@ __global__ __launch_bounds__(256) void assign_tiled_kernel(const std::uint8_t* p
     std::uint32_t best_i = 0;
     __syncthreads();
 
-    // ---- the rows of a step (centroid tile, chunk) travel global → registers → LDS: 8 consecutive threads fetch one row's 128 bytes,
-    //      two passes of points and four of centroids per thread. The NEXT step's rows are requested before this step's products
-    //      (also across the epilogue of a tile), so their flight hides behind the matrix unit.
-    const std::uint32_t segment = thread % 8;
-    uint4 fetched[(tile_points_k + tile_centroids_k) / 32];
-    auto fetch = [&](std::uint32_t tile, std::uint32_t chunk) {
-        const std::uint32_t byte = chunk * chunk_bytes_k + segment * 16;
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_points_k / 32; ++pass) {
-            const std::uint32_t i = pass * 32 + thread / 8;
-            uint4 value = {0u, 0u, 0u, 0u};
-            if (first_point + i < count && byte < stride)
-                value = *reinterpret_cast<const uint4*>(points + (std::uint64_t)(first_point + i) * stride + byte);
-            fetched[pass] = value;
-        }
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_centroids_k / 32; ++pass) {
-            const std::uint32_t j = pass * 32 + thread / 8;
-            uint4 value = {0u, 0u, 0u, 0u};
-            if (tile + j < clusters && byte < stride)
-                value = *reinterpret_cast<const uint4*>(centroids + (std::uint64_t)(tile + j) * stride + byte);
-            fetched[tile_points_k / 32 + pass] = value;
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_points_k / 32; ++pass)
-            *reinterpret_cast<uint4*>(stage_p + (pass * 32 + thread / 8) * pitch_k + segment * 16) = fetched[pass];
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_centroids_k / 32; ++pass)
-            *reinterpret_cast<uint4*>(stage_c + (pass * 32 + thread / 8) * pitch_k + segment * 16) = fetched[tile_points_k / 32 + pass];
-    };
-    fetch(0, 0);
+    // ---- the staged-tile stream of device_math.hpp: the next step's rows are in flight behind this step's products
+    staged_stream_gt stream(kmeans_rows(points, first_point, count, stride), kmeans_rows(centroids, 0, clusters, stride), lds, thread);
+    stream.fetch(0, 0);
 
     for (std::uint32_t tile = 0; tile < clusters; tile += tile_centroids_k) {
         accumulator_t acc[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                acc[t][r] = 0;
-        if (thread < tile_centroids_k)
-            norms_c[thread] = tile + thread < clusters ? centroid_norms[tile + thread] : 0u;
-        for (std::uint32_t chunk = 0; chunk < chunks; ++chunk) {
-            stash();
-            __syncthreads();
-            if (chunk + 1 < chunks)
-                fetch(tile, chunk + 1);
-            else if (tile + tile_centroids_k < clusters)
-                fetch(tile + tile_centroids_k, 0);
-            multiply_staged_chunk<scalar_ak>(stage_p, stage_c, wave, lane, acc);
-            __syncthreads();
-        }
+        multiply_staged_tile<scalar_ak>(stream, tile, chunks, acc, [&] {
+            if (thread < tile_centroids_k)
+                norms_c[thread] = tile + thread < clusters ? centroid_norms[tile + thread] : 0u;
+        });
 
         // ---- distances of the tile into LDS (the staging area is free now): D[point][centroid of the tile]
 #pragma unroll
@@ -615,12 +577,8 @@ __global__ __launch_bounds__(256) void assign_f32_kernel(const std::uint8_t* poi
 /**
  *  f32 rows on the matrix units, with the wave kernel's bits. The 64 tile's geometry and staging (64 points per workgroup, centroid
  *  tiles of 128 streamed past them, `multiply_staged_chunk<scalar_f32_k>`); what differs is what a sum is used for. The matrix unit
- *  adds in another order than `wave_distance_f32`, so its sums only SCREEN: per (point i, centroid j) a score s and an error e with
- *      | s − (d − cᵢ)·fᵢ | ≤ e       d = the wave kernel's distance, cᵢ and fᵢ > 0 the same for every centroid of the point
- *  (DESIGN.md §9 derives e; g = 2·(dimensions + 16)·2⁻²⁴, A = √Σa², B = √Σb² from `launch_row_norms<scalar_f32_k>`):
- *      l2sq  s = Σb² − 2Σab        e = g·(A + B)²
- *      ip    s = −Σab              e = g·A·B + 2⁻²³
- *      cos   s = −Σab / √Σb²       e = g·A            (Σb² = 0: s = 0, which is (1 − 1)·A to the bit)
+ *  adds in another order than `wave_distance_f32`, so its sums only SCREEN: per (point, centroid) the score s and the error e of
+ *  screen_math.hpp, with `wave_distance_f32` as the measuring kernel (`screen_g_wave`).
  *  A centroid can be the wave kernel's answer only if s − e ≤ min over all centroids of (s + e): whoever fails that is farther than
  *  the holder of the minimum in the wave kernel's own arithmetic. Thread (point i, quarter q) scans centroids [32q, 32q + 32) of every
  *  tile, as the 64 tile's epilogue does, and keeps in registers the running bound min (s + e) and up to four contenders (s − e, j)
@@ -636,11 +594,6 @@ __global__ __launch_bounds__(256) void assign_f32_kernel(const std::uint8_t* poi
  *  the number re-measured, 0 for a point handed over.
  */
 constexpr int screen_slots_k = 4;
-constexpr float screen_least_square_k = 0x1p-60f, screen_most_square_k = 0x1p+60f;
-
-__device__ __forceinline__ bool screen_square_out_of_band(float x2) {
-    return !(x2 >= screen_least_square_k && x2 <= screen_most_square_k) && x2 != 0.f; // a NaN is out of band
-}
 
 template <int metric_ak>
 __global__ __launch_bounds__(256) void assign_screened_kernel(const std::uint8_t* points, std::uint32_t count, const std::uint8_t* centroids,
@@ -656,21 +609,19 @@ __global__ __launch_bounds__(256) void assign_screened_kernel(const std::uint8_t
     __shared__ std::uint32_t out_of_band;         // some centroid's Σb² was: nothing of this workgroup is decided here
     __shared__ std::uint32_t final_count[tile_points_k];
     __shared__ std::uint32_t final_index[tile_points_k][screen_slots_k];
-    std::uint8_t* stage_p = lds;                               // [64][pitch]
-    std::uint8_t* stage_c = stage_p + tile_points_k * pitch_k; // [128][pitch]
     float* tile_s = reinterpret_cast<float*>(lds);             // [64][129], aliases the staging area after the products
     static_assert(sizeof(lds) >= 256 * (2 * screen_slots_k + 2) * 4, "the quarters' sets are folded through the staging area");
 
     const std::uint32_t thread = threadIdx.x, wave = thread / 64, lane = thread % 64;
     const std::uint32_t first_point = blockIdx.x * tile_points_k;
     const std::uint32_t chunks = (stride + chunk_bytes_k - 1) / chunk_bytes_k;
-    const float g = 2.f * (float)(dimensions + 16) * 0x1p-24f;
+    const float g = screen_g_wave(dimensions);
 
     // ---- thread (point i = thread % 64, quarter = thread / 64): the point's part of e, its running bound and its contenders
     const std::uint32_t scan_point = first_point + thread % tile_points_k;
     const float a2 = scan_point < count ? __builtin_bit_cast(float, point_norms[scan_point]) : 0.f;
     const float root_a = __builtin_sqrtf(a2);
-    bool handed_over = screen_square_out_of_band(a2) || (metric_ak == metric_cos_k && a2 == 0.f);
+    bool handed_over = square_out_of_band(a2, false) || (metric_ak == metric_cos_k && a2 == 0.f);
     float bound = __builtin_inff();
     float low[screen_slots_k];
     std::uint32_t index[screen_slots_k];
@@ -717,99 +668,30 @@ __global__ __launch_bounds__(256) void assign_screened_kernel(const std::uint8_t
     };
 
     // ---- staging: the 64 tile's (assign_tiled_kernel), next step's rows requested before this step's products
-    const std::uint32_t segment = thread % 8;
-    uint4 fetched[(tile_points_k + tile_centroids_k) / 32];
-    auto fetch = [&](std::uint32_t tile, std::uint32_t chunk) {
-        const std::uint32_t byte = chunk * chunk_bytes_k + segment * 16;
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_points_k / 32; ++pass) {
-            const std::uint32_t i = pass * 32 + thread / 8;
-            uint4 value = {0u, 0u, 0u, 0u};
-            if (first_point + i < count && byte < stride)
-                value = *reinterpret_cast<const uint4*>(points + (std::uint64_t)(first_point + i) * stride + byte);
-            fetched[pass] = value;
-        }
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_centroids_k / 32; ++pass) {
-            const std::uint32_t j = pass * 32 + thread / 8;
-            uint4 value = {0u, 0u, 0u, 0u};
-            if (tile + j < clusters && byte < stride)
-                value = *reinterpret_cast<const uint4*>(centroids + (std::uint64_t)(tile + j) * stride + byte);
-            fetched[tile_points_k / 32 + pass] = value;
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_points_k / 32; ++pass)
-            *reinterpret_cast<uint4*>(stage_p + (pass * 32 + thread / 8) * pitch_k + segment * 16) = fetched[pass];
-#pragma unroll
-        for (std::uint32_t pass = 0; pass < tile_centroids_k / 32; ++pass)
-            *reinterpret_cast<uint4*>(stage_c + (pass * 32 + thread / 8) * pitch_k + segment * 16) = fetched[tile_points_k / 32 + pass];
-    };
-    fetch(0, 0);
+    staged_stream_gt stream(kmeans_rows(points, first_point, count, stride), kmeans_rows(centroids, 0, clusters, stride), lds, thread);
+    stream.fetch(0, 0);
 
     for (std::uint32_t tile = 0; tile < clusters; tile += tile_centroids_k) {
         f32x16_t acc[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                acc[t][r] = 0;
-        if (thread < tile_centroids_k) { // read after the chunks' barriers; written again after the scan's
-            const float b2 = tile + thread < clusters ? __builtin_bit_cast(float, centroid_norms[tile + thread]) : 0.f;
-            squares_c[thread] = b2, roots_c[thread] = __builtin_sqrtf(b2);
-            if (screen_square_out_of_band(b2))
-                out_of_band = 1;
-        }
-        for (std::uint32_t chunk = 0; chunk < chunks; ++chunk) {
-            stash();
-            __syncthreads();
-            if (chunk + 1 < chunks)
-                fetch(tile, chunk + 1);
-            else if (tile + tile_centroids_k < clusters)
-                fetch(tile + tile_centroids_k, 0);
-            multiply_staged_chunk<scalar_ak>(stage_p, stage_c, wave, lane, acc);
-            __syncthreads();
-        }
+        multiply_staged_tile<scalar_ak>(stream, tile, chunks, acc, [&] {
+            if (thread < tile_centroids_k) { // read after the chunks' barriers; written again after the scan's
+                const float b2 = tile + thread < clusters ? __builtin_bit_cast(float, centroid_norms[tile + thread]) : 0.f;
+                squares_c[thread] = b2, roots_c[thread] = __builtin_sqrtf(b2);
+                if (square_out_of_band(b2, false))
+                    out_of_band = 1;
+            }
+        });
 
         // ---- scores of the tile into LDS (the staging area is free now): S[point][centroid of the tile]
-        {
-            const std::uint32_t j = wave * 32 + accumulator_column(lane);
-            const float b2 = squares_c[j], root_b = roots_c[j];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const std::uint32_t i = t * 32 + accumulator_row(r, lane);
-                    float score;
-                    if constexpr (metric_ak == metric_l2sq_k)
-                        score = b2 - 2.f * acc[t][r];
-                    else if constexpr (metric_ak == metric_ip_k)
-                        score = -acc[t][r];
-                    else
-                        score = b2 == 0.f ? 0.f : -acc[t][r] / root_b;
-                    tile_s[i * (tile_centroids_k + 1) + j] = score;
-                }
-            }
-        }
+        store_screen_scores<metric_ak>(acc, squares_c, roots_c, wave, lane, tile_s);
         __syncthreads();
 
         // ---- thread (point i, quarter q) offers centroids [32q, 32q + 32) of the tile to its set, in ascending order
         {
             const std::uint32_t i = thread % tile_points_k, first = (thread / tile_points_k) * (tile_centroids_k / 4);
             const std::uint32_t live = tile + first < clusters ? min((std::uint32_t)(tile_centroids_k / 4), clusters - tile - first) : 0u;
-            for (std::uint32_t s = 0; s < live; ++s) {
-                const float score = tile_s[i * (tile_centroids_k + 1) + first + s];
-                float e;
-                if constexpr (metric_ak == metric_l2sq_k) {
-                    const float both = root_a + roots_c[first + s];
-                    e = g * both * both;
-                } else if constexpr (metric_ak == metric_ip_k)
-                    e = __builtin_fmaf(g * root_a, roots_c[first + s], 0x1p-23f);
-                else
-                    e = g * root_a;
-                offer(score, e, tile + first + s);
-            }
+            for (std::uint32_t s = 0; s < live; ++s)
+                offer(tile_s[i * (tile_centroids_k + 1) + first + s], screen_error<metric_ak>(g, root_a, roots_c[first + s]), tile + first + s);
         }
         __syncthreads(); // the tile's scores are consumed: the area becomes staging again, the norms the next tile's
     }

@@ -16,8 +16,8 @@
 
 namespace usearch_amd {
 
-constexpr int kmeans_tile_points_k = 64;     ///< points per workgroup of the 64 tile
-constexpr int kmeans_tile_centroids_k = 128; ///< centroids per inner tile of the 64 tile
+constexpr int kmeans_tile_points_k = staged_a_rows_k;    ///< points per workgroup of the 64 tile
+constexpr int kmeans_tile_centroids_k = staged_b_rows_k; ///< centroids per inner tile of the 64 tile: 128
 
 /// Unforced, the wide tile takes a run from here on; both numbers are read off the sweep in profiles/r16_kmeans_wide/README.md
 /// (768-d bf16 on an MI355X). 65 536 points are 256 point tiles, one per compute unit of the chip (a workgroup's two staging
