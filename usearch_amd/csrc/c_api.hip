@@ -407,12 +407,13 @@ void usearch_amd_filtered_search_many_device(usearch_amd_snapshot_t snapshot, us
 }
 
 /// The `tiled` argument of the exact-search entries: 0 the wave kernel, 2 the screened route, anything else the tiles (as it always was).
-static int exact_route_from_c(int tiled) { return tiled == 0 ? exact_wave_k : tiled == 2 ? exact_screened_k : exact_tiled_k; }
+static exact_route_t exact_route_from_c(int tiled) { return tiled == 0 ? exact_wave_k : tiled == 2 ? exact_screened_k : exact_tiled_k; }
 
-void usearch_amd_filtered_exact_search_many(usearch_amd_snapshot_t snapshot, usearch_amd_filter_t filter, void const* queries,
-                                            int query_kind, size_t queries_count, size_t queries_stride, size_t wanted,
-                                            usearch_amd_key_t* keys, usearch_amd_distance_t* distances, uint64_t* counts,
-                                            int tiled, float* kernel_ms, usearch_amd_error_t* error) try {
+/// The body of the four host-buffer exact searches of a snapshot: they differ in the route, the optional filter and `remeasured`.
+static void exact_search_many(usearch_amd_snapshot_t snapshot, usearch_amd_filter_t filter, void const* queries, int query_kind,
+                              size_t queries_count, size_t queries_stride, size_t wanted, usearch_amd_key_t* keys,
+                              usearch_amd_distance_t* distances, uint64_t* counts, exact_route_t route, float* kernel_ms,
+                              uint64_t* remeasured, usearch_amd_error_t* error) try {
     const scalar_kind_t kind = scalar_from_c(query_kind);
     if (kind == scalar_unknown_k)
         return fail(error, "Unknown scalar kind!");
@@ -423,10 +424,18 @@ void usearch_amd_filtered_exact_search_many(usearch_amd_snapshot_t snapshot, use
         bits = as_filter(filter)->bits();
     }
     if (const char* e = as_snapshot(snapshot)->exact_host(queries, kind, queries_count, queries_stride, wanted, keys, distances,
-                                                          counts, kernel_ms, exact_route_from_c(tiled), bits))
+                                                          counts, kernel_ms, route, bits, remeasured))
         fail(error, e);
 } catch (...) {
     fail_from_exception(error);
+}
+
+void usearch_amd_filtered_exact_search_many(usearch_amd_snapshot_t snapshot, usearch_amd_filter_t filter, void const* queries,
+                                            int query_kind, size_t queries_count, size_t queries_stride, size_t wanted,
+                                            usearch_amd_key_t* keys, usearch_amd_distance_t* distances, uint64_t* counts,
+                                            int tiled, float* kernel_ms, usearch_amd_error_t* error) {
+    exact_search_many(snapshot, filter, queries, query_kind, queries_count, queries_stride, wanted, keys, distances, counts,
+                      exact_route_from_c(tiled), kernel_ms, nullptr, error);
 }
 
 void usearch_amd_cluster_many(usearch_amd_snapshot_t snapshot, void const* queries, int query_kind, size_t queries_count,
@@ -448,43 +457,25 @@ void usearch_amd_cluster_many(usearch_amd_snapshot_t snapshot, void const* queri
 void usearch_amd_exact_search_many(usearch_amd_snapshot_t snapshot, void const* queries, int query_kind,
                                    size_t queries_count, size_t queries_stride, size_t wanted, usearch_amd_key_t* keys,
                                    usearch_amd_distance_t* distances, uint64_t* counts, float* kernel_ms,
-                                   usearch_amd_error_t* error) try {
-    const scalar_kind_t kind = scalar_from_c(query_kind);
-    if (kind == scalar_unknown_k)
-        return fail(error, "Unknown scalar kind!");
-    if (const char* e = as_snapshot(snapshot)->exact_host(queries, kind, queries_count, queries_stride, wanted, keys,
-                                                          distances, counts, kernel_ms))
-        fail(error, e);
-} catch (...) {
-    fail_from_exception(error);
+                                   usearch_amd_error_t* error) {
+    exact_search_many(snapshot, nullptr, queries, query_kind, queries_count, queries_stride, wanted, keys, distances, counts,
+                      exact_wave_k, kernel_ms, nullptr, error);
 }
 
 void usearch_amd_exact_search_many_tiled(usearch_amd_snapshot_t snapshot, void const* queries, int query_kind,
                                          size_t queries_count, size_t queries_stride, size_t wanted,
                                          usearch_amd_key_t* keys, usearch_amd_distance_t* distances, uint64_t* counts,
-                                         float* kernel_ms, usearch_amd_error_t* error) try {
-    const scalar_kind_t kind = scalar_from_c(query_kind);
-    if (kind == scalar_unknown_k)
-        return fail(error, "Unknown scalar kind!");
-    if (const char* e = as_snapshot(snapshot)->exact_host(queries, kind, queries_count, queries_stride, wanted, keys,
-                                                          distances, counts, kernel_ms, exact_tiled_k))
-        fail(error, e);
-} catch (...) {
-    fail_from_exception(error);
+                                         float* kernel_ms, usearch_amd_error_t* error) {
+    exact_search_many(snapshot, nullptr, queries, query_kind, queries_count, queries_stride, wanted, keys, distances, counts,
+                      exact_tiled_k, kernel_ms, nullptr, error);
 }
 
 void usearch_amd_exact_search_many_screened(usearch_amd_snapshot_t snapshot, void const* queries, int query_kind,
                                             size_t queries_count, size_t queries_stride, size_t wanted,
                                             usearch_amd_key_t* keys, usearch_amd_distance_t* distances, uint64_t* counts,
-                                            float* kernel_ms, uint64_t* remeasured, usearch_amd_error_t* error) try {
-    const scalar_kind_t kind = scalar_from_c(query_kind);
-    if (kind == scalar_unknown_k)
-        return fail(error, "Unknown scalar kind!");
-    if (const char* e = as_snapshot(snapshot)->exact_host(queries, kind, queries_count, queries_stride, wanted, keys,
-                                                          distances, counts, kernel_ms, exact_screened_k, nullptr, remeasured))
-        fail(error, e);
-} catch (...) {
-    fail_from_exception(error);
+                                            float* kernel_ms, uint64_t* remeasured, usearch_amd_error_t* error) {
+    exact_search_many(snapshot, nullptr, queries, query_kind, queries_count, queries_stride, wanted, keys, distances, counts,
+                      exact_screened_k, kernel_ms, remeasured, error);
 }
 
 void usearch_amd_exact_search_many_device(usearch_amd_snapshot_t snapshot, void const* queries, size_t queries_count,
@@ -499,46 +490,45 @@ void usearch_amd_exact_search_many_device(usearch_amd_snapshot_t snapshot, void 
     fail_from_exception(error);
 }
 
+/// The body of the three exact searches of a raw dataset: they differ in the route and `remeasured`.
+static void exact_search_dataset(void const* dataset, size_t dataset_count, size_t dataset_stride, void const* queries,
+                                 size_t queries_count, size_t queries_stride, int scalar_kind, size_t dimensions, int metric_kind,
+                                 size_t wanted, usearch_amd_key_t* keys, size_t keys_stride, usearch_amd_distance_t* distances,
+                                 size_t distances_stride, exact_route_t route, uint64_t* remeasured, usearch_amd_error_t* error) try {
+    if (const char* e = exact_search_dataset_host(metric_from_c(metric_kind), scalar_from_c(scalar_kind), dimensions,
+                                                  dataset, dataset_count, dataset_stride, queries, queries_count,
+                                                  queries_stride, wanted, keys, keys_stride, distances,
+                                                  distances_stride, route, remeasured))
+        fail(error, e);
+} catch (...) {
+    fail_from_exception(error);
+}
+
 void usearch_amd_exact_search_dataset(void const* dataset, size_t dataset_count, size_t dataset_stride,
                                       void const* queries, size_t queries_count, size_t queries_stride,
                                       int scalar_kind, size_t dimensions, int metric_kind, size_t wanted,
                                       usearch_amd_key_t* keys, size_t keys_stride, usearch_amd_distance_t* distances,
-                                      size_t distances_stride, usearch_amd_error_t* error) try {
-    if (const char* e = exact_search_dataset_host(metric_from_c(metric_kind), scalar_from_c(scalar_kind), dimensions,
-                                                  dataset, dataset_count, dataset_stride, queries, queries_count,
-                                                  queries_stride, wanted, keys, keys_stride, distances,
-                                                  distances_stride))
-        fail(error, e);
-} catch (...) {
-    fail_from_exception(error);
+                                      size_t distances_stride, usearch_amd_error_t* error) {
+    exact_search_dataset(dataset, dataset_count, dataset_stride, queries, queries_count, queries_stride, scalar_kind, dimensions,
+                         metric_kind, wanted, keys, keys_stride, distances, distances_stride, exact_wave_k, nullptr, error);
 }
 
 void usearch_amd_exact_search_dataset_tiled(void const* dataset, size_t dataset_count, size_t dataset_stride,
                                             void const* queries, size_t queries_count, size_t queries_stride,
                                             int scalar_kind, size_t dimensions, int metric_kind, size_t wanted,
                                             usearch_amd_key_t* keys, size_t keys_stride, usearch_amd_distance_t* distances,
-                                            size_t distances_stride, usearch_amd_error_t* error) try {
-    if (const char* e = exact_search_dataset_host(metric_from_c(metric_kind), scalar_from_c(scalar_kind), dimensions,
-                                                  dataset, dataset_count, dataset_stride, queries, queries_count,
-                                                  queries_stride, wanted, keys, keys_stride, distances,
-                                                  distances_stride, exact_tiled_k))
-        fail(error, e);
-} catch (...) {
-    fail_from_exception(error);
+                                            size_t distances_stride, usearch_amd_error_t* error) {
+    exact_search_dataset(dataset, dataset_count, dataset_stride, queries, queries_count, queries_stride, scalar_kind, dimensions,
+                         metric_kind, wanted, keys, keys_stride, distances, distances_stride, exact_tiled_k, nullptr, error);
 }
 
 void usearch_amd_exact_search_dataset_screened(void const* dataset, size_t dataset_count, size_t dataset_stride,
                                                void const* queries, size_t queries_count, size_t queries_stride,
                                                int scalar_kind, size_t dimensions, int metric_kind, size_t wanted,
                                                usearch_amd_key_t* keys, size_t keys_stride, usearch_amd_distance_t* distances,
-                                               size_t distances_stride, uint64_t* remeasured, usearch_amd_error_t* error) try {
-    if (const char* e = exact_search_dataset_host(metric_from_c(metric_kind), scalar_from_c(scalar_kind), dimensions,
-                                                  dataset, dataset_count, dataset_stride, queries, queries_count,
-                                                  queries_stride, wanted, keys, keys_stride, distances,
-                                                  distances_stride, exact_screened_k, remeasured))
-        fail(error, e);
-} catch (...) {
-    fail_from_exception(error);
+                                               size_t distances_stride, uint64_t* remeasured, usearch_amd_error_t* error) {
+    exact_search_dataset(dataset, dataset_count, dataset_stride, queries, queries_count, queries_stride, scalar_kind, dimensions,
+                         metric_kind, wanted, keys, keys_stride, distances, distances_stride, exact_screened_k, remeasured, error);
 }
 
 void usearch_amd_comm_unique_id(void* out, usearch_amd_error_t* error) {

@@ -381,6 +381,16 @@ hipError_t launch_row_norms(const std::uint8_t* rows, std::uint64_t count, std::
     return hipGetLastError();
 }
 
+/// Σx² of the stored rows and of a batch of queries in their kind, what the exact-search tiles close cos and l2sq with.
+template <int scalar_ak>
+hipError_t launch_exact_norms(const snapshot_view_t& view, const std::uint8_t* queries, std::uint64_t count, std::uint64_t stride,
+                              std::uint32_t* row_norms, std::uint32_t* query_norms, hipStream_t stream) {
+    constexpr std::uint32_t norms_blocks = 1u << 20; // the grid of either launch at most
+    const hipError_t e = launch_row_norms<scalar_ak>(view.vectors, view.size, view.row_stride, view.bytes_per_vector, row_norms,
+                                                     norms_blocks, stream);
+    return e != hipSuccess ? e : launch_row_norms<scalar_ak>(queries, count, stride, view.bytes_per_vector, query_norms, norms_blocks, stream);
+}
+
 } // namespace
 
 } // namespace usearch_amd

@@ -1170,7 +1170,7 @@ static void search_exact_many(usearch_index_t handle, const made_filter_t* made,
         if (!device_index) // nothing indexed yet
             results.pad();
         else if (const char* e = device_index->exact_host(queries, kind, queries_count, queries_stride, count, results.keys(),
-                                                          results.distances(), results.found.data(), nullptr, false,
+                                                          results.distances(), results.found.data(), nullptr, exact_wave_k,
                                                           made && made->bitmap ? made->bitmap->bits() : nullptr))
             return fail(error, e);
         results.scatter();

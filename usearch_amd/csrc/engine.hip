@@ -15,7 +15,8 @@
 #include <hipcub/hipcub.hpp>
 
 #include "casts.hpp"
-#include "device_scratch.hpp"
+#include "exact_frame.hpp"
+#include "exact_plan.hpp"
 #include "host_util.hpp"
 #include "kernels.hpp"
 #include "search_plan.hpp"
@@ -1287,24 +1288,22 @@ static hipError_t launch_exact(metric_kind_t metric, scalar_kind_t scalar, const
     return hipErrorInvalidValue;
 }
 
-const char* exact_search_device(metric_kind_t metric, scalar_kind_t scalar, std::uint32_t lanes,
-                                const snapshot_view_t& view, const void* queries, std::size_t count,
-                                std::size_t stride_bytes, std::size_t wanted, bool map_keys, std::uint64_t* keys,
-                                float* distances, std::uint64_t* counts, hipStream_t stream, float* kernel_ms,
-                                const std::uint32_t* allow_bits) {
-    if (kernel_ms)
-        *kernel_ms = 0.f;
+const char* exact_search_device(const exact_call_t& call) {
+    const snapshot_view_t& view = call.view;
+    const std::size_t count = call.count, wanted = call.wanted;
+    if (call.kernel_ms)
+        *call.kernel_ms = 0.f;
     if (!count || !wanted)
         return nullptr;
     if (count >= none_slot_k || wanted > 4096)
         return "Batch is too large";
     if (view.size == 0) {
         const std::uint64_t cells = std::max<std::uint64_t>(count * wanted, count);
-        hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, keys,
-                           reinterpret_cast<std::uint32_t*>(distances), counts, counts, counts, (std::uint64_t)count,
-                           (std::uint64_t)wanted);
+        hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, call.stream, call.keys,
+                           reinterpret_cast<std::uint32_t*>(call.distances), call.counts, call.counts, call.counts,
+                           (std::uint64_t)count, (std::uint64_t)wanted);
         UA_HIP(hipGetLastError());
-        UA_HIP(hipStreamSynchronize(stream));
+        UA_HIP(hipStreamSynchronize(call.stream));
         return nullptr;
     }
     // enough (query, partition) waves to fill the chip, few enough candidates for one merge wave per query
@@ -1315,46 +1314,53 @@ const char* exact_search_device(metric_kind_t metric, scalar_kind_t scalar, std:
     const std::uint64_t rows_per_partition = (view.size + partitions - 1) / partitions;
     partitions = (view.size + rows_per_partition - 1) / rows_per_partition;
 
-    float* partial_distances = nullptr;
-    std::uint64_t *partial_keys = nullptr, *partial_counts = nullptr;
-    event_pair_t events;
-    device_scratch_t scratch(current_device_k); // the caller has selected the device the view lives on
-    UA_HIP(scratch.allocate(&partial_distances, partitions * count * wanted * 4));
-    UA_HIP(scratch.allocate(&partial_keys, partitions * count * wanted * 8));
-    UA_HIP(scratch.allocate(&partial_counts, partitions * count * 8));
-    if (kernel_ms) {
-        UA_HIP(events.create());
-        UA_HIP(hipEventRecord(events.begin, stream));
-    }
-    exact_params_t p{};
-    p.lanes = lanes;
-    p.lds_bytes = view.chunks * (query_chunk_bytes_of(scalar)) + 512 + (std::uint32_t)wanted * 8 + 16;
-    p.stream = stream;
-    p.queries = static_cast<const std::uint8_t*>(queries);
-    p.query_stride = stride_bytes;
-    p.query_count = (std::uint32_t)count;
-    p.wanted = (std::uint32_t)wanted;
-    p.partitions = (std::uint32_t)partitions;
-    p.rows_per_partition = rows_per_partition;
-    p.map_keys = map_keys ? 1u : 0u;
-    p.allow_bits = allow_bits;
-    p.out_distances = partial_distances;
-    p.out_keys = partial_keys;
-    p.out_counts = partial_counts;
-    UA_HIP(launch_exact(metric, scalar, p, view));
-    if (kernel_ms)
-        UA_HIP(hipEventRecord(events.end, stream));
-    if (const char* error = merge_shards_device(partial_distances, partial_keys, partial_counts, partitions, count, wanted, distances,
-                                                keys, counts, stream, false))
-        return error;
-    if (kernel_ms)
-        UA_HIP(hipEventElapsedTime(kernel_ms, events.begin, events.end));
+    return exact_partitioned(call, partitions, [&](const exact_partials_t& partials) -> const char* {
+        exact_params_t p{};
+        p.lanes = call.lanes;
+        p.lds_bytes = exact_kernel_lds_bytes(view, call.scalar, wanted);
+        p.stream = call.stream;
+        p.queries = static_cast<const std::uint8_t*>(call.queries);
+        p.query_stride = call.stride_bytes;
+        p.query_count = (std::uint32_t)count;
+        p.wanted = (std::uint32_t)wanted;
+        p.partitions = (std::uint32_t)partitions;
+        p.rows_per_partition = rows_per_partition;
+        p.map_keys = call.map_keys ? 1u : 0u;
+        p.allow_bits = call.allow_bits;
+        p.out_distances = partials.distances;
+        p.out_keys = partials.keys;
+        p.out_counts = partials.counts;
+        UA_HIP(launch_exact(call.metric, call.scalar, p, view));
+        return nullptr;
+    });
+}
+
+const char* exact_route_refusal(exact_route_t route, metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted) {
+    if (route == exact_screened_k && !exact_screened_available(metric, scalar, wanted))
+        return "No screened exact-search kernel for this metric / scalar kind / result count";
+    if (route == exact_tiled_k && !exact_tiled_available(metric, scalar, wanted))
+        return "No tiled exact-search kernel for this metric / scalar kind / result count";
     return nullptr;
+}
+
+const char* exact_search_routed(exact_route_t route, const exact_call_t& asked) {
+    if (asked.kernel_ms)
+        *asked.kernel_ms = 0.f;
+    if (const char* refusal = exact_route_refusal(route, asked.metric, asked.scalar, asked.wanted))
+        return refusal;
+    if (route == exact_wave_k) // the metric as it is: `launch_exact` normalises it
+        return exact_search_device(asked);
+    exact_call_t call = asked;
+    call.metric = kernel_metric(asked.metric);
+    if (route == exact_screened_k)
+        return exact_search_screened_device(call);
+    // b1: the bit tile (exact_bits.hip), same contract
+    return exact_bits_pair(call.metric, call.scalar, call.wanted) ? exact_search_bits_device(call) : exact_search_tiled_device(call);
 }
 
 const char* snapshot_t::exact_device(const void* queries, std::size_t count, std::size_t stride_bytes,
                                      std::size_t wanted, std::uint64_t* keys, float* distances, std::uint64_t* counts,
-                                     hipStream_t stream, float* kernel_ms, int tiled, const std::uint32_t* allow_bits) {
+                                     hipStream_t stream, float* kernel_ms, exact_route_t route, const std::uint32_t* allow_bits) {
     if (!count || !wanted)
         return nullptr;
     UA_HIP(hipSetDevice(device_));
@@ -1364,19 +1370,18 @@ const char* snapshot_t::exact_device(const void* queries, std::size_t count, std
             return e;
         stream = lease.workspace->stream;
     }
-    if (tiled == exact_screened_k)
-        return exact_search_screened_device(kernel_metric(metric_), scalar_, lanes_, view_, queries, count, stride_bytes, wanted, true,
-                                            keys, distances, counts, nullptr, stream, kernel_ms, allow_bits);
-    if (tiled)
-        return exact_search_tiled_device(kernel_metric(metric_), scalar_, view_, queries, count, stride_bytes, wanted, true, keys,
-                                         distances, counts, stream, kernel_ms, allow_bits);
-    return exact_search_device(metric_, scalar_, lanes_, view_, queries, count, stride_bytes, wanted, true, keys,
-                               distances, counts, stream, kernel_ms, allow_bits);
+    exact_call_t call;
+    call.view = view_, call.metric = metric_, call.scalar = scalar_, call.lanes = lanes_;
+    call.queries = queries, call.count = count, call.stride_bytes = stride_bytes, call.wanted = wanted;
+    call.map_keys = true, call.allow_bits = allow_bits;
+    call.keys = keys, call.distances = distances, call.counts = counts;
+    call.stream = stream, call.kernel_ms = kernel_ms;
+    return exact_search_routed(route, call);
 }
 
 const char* snapshot_t::exact_host(const void* queries, scalar_kind_t query_kind, std::size_t count,
                                    std::size_t stride_bytes, std::size_t wanted, std::uint64_t* keys, float* distances,
-                                   std::uint64_t* counts, float* kernel_ms, int tiled, const std::uint32_t* allow_bits,
+                                   std::uint64_t* counts, float* kernel_ms, exact_route_t route, const std::uint32_t* allow_bits,
                                    std::uint64_t* remeasured) {
     if (!count || !wanted)
         return nullptr;
@@ -1398,33 +1403,26 @@ const char* snapshot_t::exact_host(const void* queries, scalar_kind_t query_kind
     auto pad = [](std::size_t b) { return (b + 255) & ~(std::size_t)255; };
     if (const char* e = ws.reserve_stage(pad(bpv * count) + pad(count * wanted * 8) + pad(count * wanted * 4) + 2 * pad(count * 8), 0))
         return e;
-    std::uint8_t* d_queries = ws.d_stage;
-    std::uint64_t* d_keys = reinterpret_cast<std::uint64_t*>(d_queries + pad(bpv * count));
-    float* d_distances = reinterpret_cast<float*>(reinterpret_cast<std::uint8_t*>(d_keys) + pad(count * wanted * 8));
-    std::uint64_t* d_counts = reinterpret_cast<std::uint64_t*>(reinterpret_cast<std::uint8_t*>(d_distances) + pad(count * wanted * 4));
-    std::uint64_t* d_remeasured = d_counts + pad(count * 8) / 8;
-    UA_HIP(hipMemcpy(d_queries, dense.data(), bpv * count, hipMemcpyHostToDevice));
-    if (tiled == exact_screened_k) {
-        if (const char* e = exact_search_screened_device(kernel_metric(metric_), scalar_, lanes_, view_, d_queries, count, bpv, wanted,
-                                                         true, d_keys, d_distances, d_counts, d_remeasured, ws.stream, kernel_ms,
-                                                         allow_bits))
-            return e;
-        if (remeasured)
-            UA_HIP(hipMemcpy(remeasured, d_remeasured, count * 8, hipMemcpyDeviceToHost));
-    } else if (tiled) {
-        if (const char* e = exact_search_tiled_device(kernel_metric(metric_), scalar_, view_, d_queries, count, bpv, wanted,
-                                                      true, d_keys, d_distances, d_counts, ws.stream, kernel_ms, allow_bits))
-            return e;
-    } else if (const char* e = exact_search_device(metric_, scalar_, lanes_, view_, d_queries, count, bpv, wanted, true, d_keys,
-                                                   d_distances, d_counts, ws.stream, kernel_ms, allow_bits)) {
+    exact_call_t call;
+    call.view = view_, call.metric = metric_, call.scalar = scalar_, call.lanes = lanes_;
+    call.queries = ws.d_stage, call.count = count, call.stride_bytes = bpv, call.wanted = wanted;
+    call.map_keys = true, call.allow_bits = allow_bits;
+    call.keys = reinterpret_cast<std::uint64_t*>(ws.d_stage + pad(bpv * count));
+    call.distances = reinterpret_cast<float*>(reinterpret_cast<std::uint8_t*>(call.keys) + pad(count * wanted * 8));
+    call.counts = reinterpret_cast<std::uint64_t*>(reinterpret_cast<std::uint8_t*>(call.distances) + pad(count * wanted * 4));
+    call.remeasured = call.counts + pad(count * 8) / 8;
+    call.stream = ws.stream, call.kernel_ms = kernel_ms;
+    UA_HIP(hipMemcpy(ws.d_stage, dense.data(), bpv * count, hipMemcpyHostToDevice));
+    if (const char* e = exact_search_routed(route, call))
         return e;
-    }
+    if (remeasured && route == exact_screened_k)
+        UA_HIP(hipMemcpy(remeasured, call.remeasured, count * 8, hipMemcpyDeviceToHost));
     if (keys)
-        UA_HIP(hipMemcpy(keys, d_keys, count * wanted * 8, hipMemcpyDeviceToHost));
+        UA_HIP(hipMemcpy(keys, call.keys, count * wanted * 8, hipMemcpyDeviceToHost));
     if (distances)
-        UA_HIP(hipMemcpy(distances, d_distances, count * wanted * 4, hipMemcpyDeviceToHost));
+        UA_HIP(hipMemcpy(distances, call.distances, count * wanted * 4, hipMemcpyDeviceToHost));
     if (counts)
-        UA_HIP(hipMemcpy(counts, d_counts, count * 8, hipMemcpyDeviceToHost));
+        UA_HIP(hipMemcpy(counts, call.counts, count * 8, hipMemcpyDeviceToHost));
     return nullptr;
 }
 
@@ -1432,69 +1430,58 @@ const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar
                                       const void* dataset, std::size_t dataset_count, std::size_t dataset_stride,
                                       const void* queries, std::size_t queries_count, std::size_t queries_stride,
                                       std::size_t wanted, std::uint64_t* keys, std::size_t keys_stride,
-                                      float* distances, std::size_t distances_stride, int tiled, std::uint64_t* remeasured) {
+                                      float* distances, std::size_t distances_stride, exact_route_t route,
+                                      std::uint64_t* remeasured) {
     // (f8 has the matrix-unit tiles and nothing else so far: asked for by name it is the tiles' table that answers, any other way
     // it is refused like every pair without a kernel)
-    if (!kernel_available(metric, scalar) && !(tiled && scalar == scalar_f8_k))
+    if (!kernel_available(metric, scalar) && !(route != exact_wave_k && scalar == scalar_f8_k))
         return "No MI355X kernel for this metric / scalar kind combination";
     if (!queries_count || !wanted)
         return nullptr;
-    if (tiled == exact_screened_k && !exact_screened_available(metric, scalar, wanted)) // by name too, and never rerouted
-        return "No screened exact-search kernel for this metric / scalar kind / result count";
-    if (tiled && tiled != exact_screened_k && !exact_tiled_available(metric, scalar, wanted)) // asked for by name: no quiet detour over the wave kernel
-        return "No tiled exact-search kernel for this metric / scalar kind / result count";
+    // a route asked for by name is never rerouted: no quiet detour over the wave kernel
+    if (const char* refusal = exact_route_refusal(route, metric, scalar, wanted))
+        return refusal;
     if (dataset_count >= none_slot_k)
         return "Dataset is too large for 32-bit offsets";
     const std::size_t bpv = bytes_per_vector(scalar, dimensions);
     if (dataset_stride < bpv || queries_stride < bpv)
         return "Stride is smaller than one vector";
-    std::uint32_t lanes = 1, row_stride = 16, row_chunks = 1;
-    row_geometry(bpv, lanes, row_stride, row_chunks);
+    exact_call_t call;
+    call.metric = metric, call.scalar = scalar;
+    row_geometry(bpv, call.lanes, call.view.row_stride, call.view.chunks);
+    const std::uint32_t row_stride = call.view.row_stride;
     std::uint8_t *d_rows = nullptr, *d_queries = nullptr;
-    std::uint64_t *d_keys = nullptr, *d_counts = nullptr;
-    float* d_distances = nullptr;
     device_scratch_t scratch(current_device_k); // no snapshot here: the dataset goes to the caller's device
     UA_HIP(scratch.allocate(&d_rows, dataset_count * row_stride));
     UA_HIP(scratch.allocate(&d_queries, queries_count * bpv));
-    UA_HIP(scratch.allocate(&d_keys, queries_count * wanted * 8));
-    UA_HIP(scratch.allocate(&d_distances, queries_count * wanted * 4));
-    UA_HIP(scratch.allocate(&d_counts, queries_count * 8));
-    std::uint64_t* d_remeasured = nullptr;
-    UA_HIP(scratch.allocate(&d_remeasured, queries_count * 8));
+    UA_HIP(scratch.allocate(&call.keys, queries_count * wanted * 8));
+    UA_HIP(scratch.allocate(&call.distances, queries_count * wanted * 4));
+    UA_HIP(scratch.allocate(&call.counts, queries_count * 8));
+    UA_HIP(scratch.allocate(&call.remeasured, queries_count * 8));
     if (const char* error = upload_rows(d_rows, row_stride, static_cast<const std::uint8_t*>(dataset), dataset_stride, bpv, dataset_count))
         return error;
     if (const char* error = upload_rows(d_queries, (std::uint32_t)bpv, static_cast<const std::uint8_t*>(queries), queries_stride, bpv,
                                         queries_count))
         return error;
-    snapshot_view_t view{};
-    view.vectors = d_rows;
-    view.size = dataset_count;
-    view.row_stride = row_stride;
-    view.chunks = row_chunks;
-    view.bytes_per_vector = (std::uint32_t)bpv;
-    view.dimensions = (std::uint32_t)dimensions;
+    call.view.vectors = d_rows;
+    call.view.size = dataset_count;
+    call.view.bytes_per_vector = (std::uint32_t)bpv;
+    call.view.dimensions = (std::uint32_t)dimensions;
+    call.queries = d_queries, call.count = queries_count, call.stride_bytes = bpv, call.wanted = wanted;
     // i8: the matrix-unit kernel returns the very same bits (exact integer sums, same closing arithmetic, same tie order);
     // the float kinds only reach it when asked (`tiled`: a derived bound instead of bit equality), and so does b1, whose bit tile
     // (exact_bits.hip) returns the wave kernel's bits too: routing it unasked waits for its speed to be measured
-    const char* error = nullptr;
-    if (tiled == exact_screened_k) {
-        error = exact_search_screened_device(kernel_metric(metric), scalar, lanes, view, d_queries, queries_count, bpv, wanted, false,
-                                             d_keys, d_distances, d_counts, d_remeasured, nullptr, nullptr);
-        if (!error && remeasured)
-            UA_HIP(hipMemcpy(remeasured, d_remeasured, queries_count * 8, hipMemcpyDeviceToHost));
-    } else if (tiled || (scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
-                  !env_size("USEARCH_AMD_NO_TILED_EXACT", 0)))
-        error = exact_search_tiled_device(kernel_metric(metric), scalar, view, d_queries, queries_count, bpv, wanted, false, d_keys,
-                                          d_distances, d_counts, nullptr, nullptr);
-    else
-        error = exact_search_device(metric, scalar, lanes, view, d_queries, queries_count, bpv, wanted, false, d_keys, d_distances,
-                                    d_counts, nullptr, nullptr);
-    if (error)
+    if (route == exact_wave_k && scalar == scalar_i8_k && exact_tiled_available(metric, scalar, wanted) && queries_count >= 32 &&
+        !env_size("USEARCH_AMD_NO_TILED_EXACT", 0))
+        route = exact_tiled_k;
+    if (const char* error = exact_search_routed(route, call))
         return error;
+    if (remeasured && route == exact_screened_k)
+        UA_HIP(hipMemcpy(remeasured, call.remeasured, queries_count * 8, hipMemcpyDeviceToHost));
     std::vector<std::uint64_t> host_keys(queries_count * wanted);
     std::vector<float> host_distances(queries_count * wanted);
-    UA_HIP(hipMemcpy(host_keys.data(), d_keys, host_keys.size() * 8, hipMemcpyDeviceToHost));
-    UA_HIP(hipMemcpy(host_distances.data(), d_distances, host_distances.size() * 4, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(host_keys.data(), call.keys, host_keys.size() * 8, hipMemcpyDeviceToHost));
+    UA_HIP(hipMemcpy(host_distances.data(), call.distances, host_distances.size() * 4, hipMemcpyDeviceToHost));
     for (std::size_t q = 0; q < queries_count; ++q) {
         std::memcpy(reinterpret_cast<std::uint8_t*>(keys) + q * keys_stride, host_keys.data() + q * wanted, wanted * 8);
         std::memcpy(reinterpret_cast<std::uint8_t*>(distances) + q * distances_stride, host_distances.data() + q * wanted,

@@ -340,14 +340,14 @@ class snapshot_t {
     /// applies too (index.hpp:4260-4263).
     const char* exact_device(const void* queries, std::size_t count, std::size_t stride_bytes, std::size_t wanted,
                              std::uint64_t* keys, float* distances, std::uint64_t* counts, hipStream_t stream,
-                             float* kernel_ms, int tiled = exact_wave_k, const std::uint32_t* allow_bits = nullptr);
-    /// Same with host buffers and any query scalar kind. `tiled` = `exact_tiled_k`: the matrix-unit kernel where one exists for the
+                             float* kernel_ms, exact_route_t route = exact_wave_k, const std::uint32_t* allow_bits = nullptr);
+    /// Same with host buffers and any query scalar kind. `route` = `exact_tiled_k`: the matrix-unit kernel where one exists for the
     /// pair (exact_tiled.hip; an error otherwise) instead of the bit-exact wave-per-query one; `exact_screened_k`: the screened
     /// route (exact_screened.hip; the wave kernel's bits, an error for a pair without it), which also fills `remeasured` ([count],
     /// host, optional: rows measured per query).
     const char* exact_host(const void* queries, scalar_kind_t query_kind, std::size_t count, std::size_t stride_bytes,
                            std::size_t wanted, std::uint64_t* keys, float* distances, std::uint64_t* counts,
-                           float* kernel_ms, int tiled = exact_wave_k, const std::uint32_t* allow_bits = nullptr,
+                           float* kernel_ms, exact_route_t route = exact_wave_k, const std::uint32_t* allow_bits = nullptr,
                            std::uint64_t* remeasured = nullptr);
 
     /// out[q][j] = metric(query q, stored row slots[q][j]); host buffers, queries in storage kind.
@@ -563,59 +563,77 @@ const char* mark_list_starts(const std::uint32_t* upper_ref, std::uint64_t membe
                              hipStream_t stream);
 
 /**
- *  Exact search over the rows of `view` (device pointers everywhere; `view` needs `vectors`, sizes and — when
- *  `map_keys` — `keys`): partition scan + fold. Results as `index_gt::search_exact_` gives them: top-`wanted` under
- *  (distance ↑, slot ↓), padded with key 0 / signalling NaN.
+ *  One exact search as every route takes it: device pointers everywhere, the device the view lives on selected by the caller.
+ *  Results as `index_gt::search_exact_` gives them: per query the top-`wanted` under (distance ↑, slot ↓), padded with key 0 /
+ *  signalling NaN.
  */
-const char* exact_search_device(metric_kind_t metric, scalar_kind_t scalar, std::uint32_t lanes,
-                                const snapshot_view_t& view, const void* queries, std::size_t count,
-                                std::size_t stride_bytes, std::size_t wanted, bool map_keys, std::uint64_t* keys,
-                                float* distances, std::uint64_t* counts, hipStream_t stream, float* kernel_ms,
-                                const std::uint32_t* allow_bits = nullptr);
+struct exact_call_t {
+    snapshot_view_t view{};                     ///< needs `vectors`, the sizes and — with `map_keys` — `keys`
+    metric_kind_t metric = metric_unknown_k;    ///< as the index has it: `exact_search_routed` hands each route the form it takes
+    scalar_kind_t scalar = scalar_unknown_k;
+    std::uint32_t lanes = 1;                    ///< lanes per stored row (`row_geometry`)
+    const void* queries = nullptr;              ///< [count] rows in the storage kind, `stride_bytes` apart
+    std::size_t count = 0, stride_bytes = 0;
+    std::size_t wanted = 0;
+    bool map_keys = false;                      ///< keys are `view.keys[slot]`; otherwise the slots themselves
+    const std::uint32_t* allow_bits = nullptr;  ///< optional, one bit per slot: the caller's predicate
+    std::uint64_t* keys = nullptr;              ///< [count][wanted]
+    float* distances = nullptr;                 ///< [count][wanted]
+    std::uint64_t* counts = nullptr;            ///< [count]
+    std::uint64_t* remeasured = nullptr;        ///< [count], optional, the screened route only: rows measured per query
+    hipStream_t stream = nullptr;
+    float* kernel_ms = nullptr;                 ///< optional: the kernels' HIP-event time
+};
+
+/// The one way into the routes below. It refuses a route asked for a pair that has none (`exact_route_refusal`), hands the wave
+/// kernel the metric as it is (its launcher normalises it) and the tiles `kernel_metric` of it, and sends the b1 pairs of the tiled
+/// route to the bit tile. A new route is one more line here, not one in every entry point.
+const char* exact_search_routed(exact_route_t route, const exact_call_t& call);
+/// What `exact_search_routed` refuses `route` with for this pair and result count, or null — for callers that want the refusal
+/// before they upload anything.
+const char* exact_route_refusal(exact_route_t route, metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted);
+
+/// Dynamic LDS of `exact_kernel`, which the screened route's closing pass instantiates too: the staged query, the lanes' partial
+/// sums, the list of `wanted`.
+inline std::uint32_t exact_kernel_lds_bytes(const snapshot_view_t& view, scalar_kind_t scalar, std::size_t wanted) {
+    return view.chunks * query_chunk_bytes_of(scalar) + 512 + (std::uint32_t)wanted * 8 + 16;
+}
+
+/// The wave-per-query route (engine.hip): partition scan + fold, the bits every other route is held to.
+const char* exact_search_device(const exact_call_t& call);
 
 /// Is there a tiled (matrix-unit) exact-search kernel for this pair and result count? (exact_tiled.hip: cos / ip / l2sq over f16
 /// and bf16 — float tolerance —, cos / ip over f32 — a derived bound, not bit equality; l2sq over f32 stays refused — and over i8 — bit-identical to the wave-per-query
 /// kernel. The table itself: `exact_tiled_pair` of exact_plan.hpp.) Or a bit tile (exact_bits.hip: hamming, tanimoto / jaccard and
 /// sorensen over b1, no matrix unit, bit-identical to the wave-per-query kernel, NaN included; its table: `exact_bits_pair`)? Either
-/// one makes the tiled routes available: `exact_search_tiled_device` runs whichever the pair has.
+/// one makes the tiled route available: `exact_search_routed` runs whichever the pair has.
 bool exact_tiled_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted);
 
-/// Many-to-many exact search as a tiled matrix product (index_plugins.hpp:2071-2164): rows are read once per 64 queries — or, for the
-/// b1 pairs of `exact_bits_pair`, the bit tile below. Same contract as `exact_search_device`.
-const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar, const snapshot_view_t& view,
-                                      const void* queries, std::size_t count, std::size_t stride_bytes, std::size_t wanted,
-                                      bool map_keys, std::uint64_t* keys, float* distances, std::uint64_t* counts,
-                                      hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits = nullptr);
+/// Many-to-many exact search as a tiled matrix product (index_plugins.hpp:2071-2164): rows are read once per 64 queries. The pairs of
+/// `exact_tiled_pair`, `kernel_metric` of the metric. Same contract as `exact_search_device`.
+const char* exact_search_tiled_device(const exact_call_t& call);
 
 /// Screened exact search (exact_screened.hip) of the pairs of `exact_screened_pair` (exact_plan.hpp: cos, ip and l2sq over f32): the
 /// f32 matrix-unit tile forms a score and a derived error per (query, row) and keeps the rows that can be among the `wanted`
 /// nearest; `exact_remeasure_kernel` measures those with `exact_kernel`'s instantiation for `lanes`. Keys, distance bits and counts
 /// are `exact_search_device`'s; queries the screen cannot decide are handed to that function. Same contract as it, plus
-/// `remeasured` ([count], device, optional): rows measured per query. Every other pair or count is refused by name.
-/// `exact_screened_available`: the table (`exact_screened_pair`) for callers that want the refusal before they upload anything.
+/// `remeasured`. `exact_screened_available`: the table (`exact_screened_pair`).
 bool exact_screened_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted);
-const char* exact_search_screened_device(metric_kind_t metric, scalar_kind_t scalar, std::uint32_t lanes, const snapshot_view_t& view,
-                                         const void* queries, std::size_t count, std::size_t stride_bytes, std::size_t wanted,
-                                         bool map_keys, std::uint64_t* keys, float* distances, std::uint64_t* counts,
-                                         std::uint64_t* remeasured, hipStream_t stream, float* kernel_ms,
-                                         const std::uint32_t* allow_bits = nullptr);
+const char* exact_search_screened_device(const exact_call_t& call);
 
 /// The bit tile (exact_bits.hip): rows are read once per 256 queries, popcount(a ∧ b) on the vector ALU. `metric`: hamming, tanimoto,
-/// jaccard or sorensen; the view's rows are b1. Same contract and the same refusals as `exact_search_tiled_device`, which is its
-/// one caller.
-const char* exact_search_bits_device(metric_kind_t metric, const snapshot_view_t& view, const void* queries, std::size_t count,
-                                     std::size_t stride_bytes, std::size_t wanted, bool map_keys, std::uint64_t* keys, float* distances,
-                                     std::uint64_t* counts, hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits = nullptr);
+/// jaccard or sorensen; the view's rows are b1. Same contract as `exact_search_tiled_device`.
+const char* exact_search_bits_device(const exact_call_t& call);
 
 /// Host-buffer exact search of a raw dataset — `usearch_exact_search` (c/usearch.h:467-474): keys are dataset offsets.
-/// `tiled` = `exact_tiled_k`: the matrix-unit kernel (or the bit tile) over the uploaded rows for any pair that has one (`exact_tiled_available`; refused otherwise)
+/// `route` = `exact_tiled_k`: the matrix-unit kernel (or the bit tile) over the uploaded rows for any pair that has one (`exact_tiled_available`; refused otherwise)
 /// instead of the bit-exact wave-per-query one, which stays what the float kinds get unasked. `exact_screened_k`: the screened route
 /// over the uploaded rows (refused for a pair without it); `remeasured`: [queries_count], host, optional.
 const char* exact_search_dataset_host(metric_kind_t metric, scalar_kind_t scalar, std::size_t dimensions,
                                       const void* dataset, std::size_t dataset_count, std::size_t dataset_stride,
                                       const void* queries, std::size_t queries_count, std::size_t queries_stride,
                                       std::size_t wanted, std::uint64_t* keys, std::size_t keys_stride,
-                                      float* distances, std::size_t distances_stride, int tiled = exact_wave_k,
+                                      float* distances, std::size_t distances_stride, exact_route_t route = exact_wave_k,
                                       std::uint64_t* remeasured = nullptr);
 
 /// Lanes per stored row, the row pitch and the 16-byte chunks the kernels read of a row of `bytes` bytes (the summation layout

@@ -28,8 +28,8 @@
 
 #include "common.hpp"
 #include "device_math.hpp"
-#include "device_scratch.hpp"
 #include "engine.hpp"
+#include "exact_frame.hpp"
 #include "exact_plan.hpp"
 #include "host_util.hpp"
 
@@ -272,13 +272,9 @@ hipError_t launch_bits(const snapshot_view_t& view, const std::uint8_t* queries,
 
 } // namespace
 
-const char* exact_search_bits_device(metric_kind_t metric, const snapshot_view_t& view, const void* queries, std::size_t count,
-                                     std::size_t stride_bytes, std::size_t wanted, bool map_keys, std::uint64_t* keys, float* distances,
-                                     std::uint64_t* counts, hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits) {
-    if (kernel_ms)
-        *kernel_ms = 0.f;
-    if (!exact_bits_pair(metric, scalar_b1x8_k, wanted))
-        return "No tiled exact-search kernel for this metric / scalar kind / result count";
+const char* exact_search_bits_device(const exact_call_t& call) {
+    const snapshot_view_t& view = call.view;
+    const std::size_t count = call.count, wanted = call.wanted;
     if (!count)
         return nullptr;
     if (count >= none_slot_k || view.size >= none_slot_k)
@@ -286,46 +282,28 @@ const char* exact_search_bits_device(metric_kind_t metric, const snapshot_view_t
     exact_bits_plan_t plan; // how many partitions, which workgroup takes which (query tile, partition): exact_plan.hpp
     if (const char* refusal = plan_exact_bits(view.size, view.bytes_per_vector, view.row_stride, count, wanted, plan))
         return refusal;
-    const bool counted = metric != metric_hamming_k;
 
-    event_pair_t events;
     device_scratch_t scratch(current_device_k); // the caller has selected the device the view lives on
     std::uint32_t *padded = nullptr, *row_counts = nullptr, *query_counts = nullptr;
-    float* partial_distances = nullptr;
-    std::uint64_t *partial_keys = nullptr, *partial_counts = nullptr;
     UA_HIP(scratch.allocate(&padded, plan.padded_queries * plan.padded_query_bytes));
     UA_HIP(scratch.allocate(&query_counts, plan.padded_queries * 4));
-    if (counted)
+    if (call.metric != metric_hamming_k)
         UA_HIP(scratch.allocate(&row_counts, view.size * 4));
-    UA_HIP(scratch.allocate(&partial_distances, plan.partitions * count * wanted * 4));
-    UA_HIP(scratch.allocate(&partial_keys, plan.partitions * count * wanted * 8));
-    UA_HIP(scratch.allocate(&partial_counts, plan.partitions * count * 8));
-    if (kernel_ms) {
-        UA_HIP(events.create());
-        UA_HIP(hipEventRecord(events.begin, stream));
-    }
-    const std::uint8_t* query_bytes = static_cast<const std::uint8_t*>(queries);
-    hipError_t e = hipErrorInvalidValue;
+    return exact_partitioned(call, plan.partitions, [&](const exact_partials_t& partials) -> const char* {
+        hipError_t e = hipErrorInvalidValue;
 #define UA_BITS(m)                                                                                                                     \
-    e = launch_bits<m>(view, query_bytes, stride_bytes, (std::uint32_t)count, (std::uint32_t)wanted, plan, padded, row_counts,        \
-                       query_counts, map_keys, allow_bits, partial_distances, partial_keys, partial_counts, stream)
-    if (metric == metric_hamming_k)
-        UA_BITS(metric_hamming_k);
-    else if (metric == metric_sorensen_k)
-        UA_BITS(metric_sorensen_k);
-    else // tanimoto, and jaccard, which is tanimoto over bit sets (index_plugins.hpp:2003-2004)
-        UA_BITS(metric_tanimoto_k);
+    e = launch_bits<m>(view, static_cast<const std::uint8_t*>(call.queries), call.stride_bytes, (std::uint32_t)count,                 \
+                       (std::uint32_t)wanted, plan, padded, row_counts, query_counts, call.map_keys, call.allow_bits,                 \
+                       partials.distances, partials.keys, partials.counts, call.stream)
+        if (call.metric == metric_hamming_k)
+            UA_BITS(metric_hamming_k);
+        else if (call.metric == metric_sorensen_k)
+            UA_BITS(metric_sorensen_k);
+        else // tanimoto, and jaccard, which is tanimoto over bit sets (index_plugins.hpp:2003-2004)
+            UA_BITS(metric_tanimoto_k);
 #undef UA_BITS
-    if (e != hipSuccess)
-        return hip_message(e);
-    if (kernel_ms)
-        UA_HIP(hipEventRecord(events.end, stream));
-    if (const char* error = merge_shards_device(partial_distances, partial_keys, partial_counts, plan.partitions, count, wanted, distances,
-                                                keys, counts, stream, false))
-        return error;
-    if (kernel_ms)
-        UA_HIP(hipEventElapsedTime(kernel_ms, events.begin, events.end));
-    return nullptr;
+        return e == hipSuccess ? nullptr : hip_message(e);
+    });
 }
 
 } // namespace usearch_amd

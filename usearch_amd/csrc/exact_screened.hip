@@ -238,23 +238,19 @@ hipError_t launch_screen(const snapshot_view_t& view, const std::uint8_t* querie
     return hipGetLastError();
 }
 
-constexpr std::uint32_t norms_blocks_k = 1u << 20; ///< the grid of the Σx² launches at most
-
 } // namespace
 
 bool exact_screened_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted) {
     return exact_screened_pair(metric, scalar, wanted); // the table: exact_plan.hpp
 }
 
-const char* exact_search_screened_device(metric_kind_t metric, scalar_kind_t scalar, std::uint32_t lanes, const snapshot_view_t& view,
-                                         const void* queries, std::size_t count, std::size_t stride_bytes, std::size_t wanted,
-                                         bool map_keys, std::uint64_t* keys, float* distances, std::uint64_t* counts,
-                                         std::uint64_t* remeasured, hipStream_t stream, float* kernel_ms,
-                                         const std::uint32_t* allow_bits) {
-    if (kernel_ms)
-        *kernel_ms = 0.f;
-    if (!exact_screened_pair(metric, scalar, wanted))
-        return "No screened exact-search kernel for this metric / scalar kind / result count";
+const char* exact_search_screened_device(const exact_call_t& call) {
+    const snapshot_view_t& view = call.view;
+    const std::size_t count = call.count, wanted = call.wanted, stride_bytes = call.stride_bytes;
+    const std::uint32_t* allow_bits = call.allow_bits;
+    std::uint64_t* remeasured = call.remeasured;
+    hipStream_t stream = call.stream;
+    float* kernel_ms = call.kernel_ms;
     if (!count)
         return nullptr;
     if (count >= none_slot_k || view.size >= none_slot_k)
@@ -262,8 +258,7 @@ const char* exact_search_screened_device(metric_kind_t metric, scalar_kind_t sca
     if (view.size == 0) { // nothing to screen: the wave route's empty results, nothing measured
         if (remeasured)
             UA_HIP(hipMemsetAsync(remeasured, 0, count * 8, stream));
-        return exact_search_device(metric, scalar, lanes, view, queries, count, stride_bytes, wanted, map_keys, keys, distances, counts,
-                                   stream, kernel_ms, allow_bits);
+        return exact_search_device(call);
     }
     // partitions, the capacity of a (query, partition) buffer, the scratch in all: exact_plan.hpp
     std::size_t free_bytes = 0, total_bytes = 0;
@@ -290,12 +285,11 @@ const char* exact_search_screened_device(metric_kind_t metric, scalar_kind_t sca
         UA_HIP(events.create());
         UA_HIP(hipEventRecord(events.begin, stream));
     }
-    const std::uint8_t* query_bytes = static_cast<const std::uint8_t*>(queries);
-    UA_HIP(launch_row_norms<scalar_f32_k>(view.vectors, view.size, view.row_stride, view.bytes_per_vector, row_norms, norms_blocks_k, stream));
-    UA_HIP(launch_row_norms<scalar_f32_k>(query_bytes, count, stride_bytes, view.bytes_per_vector, query_norms, norms_blocks_k, stream));
+    const std::uint8_t* query_bytes = static_cast<const std::uint8_t*>(call.queries);
+    UA_HIP(launch_exact_norms<scalar_f32_k>(view, query_bytes, count, stride_bytes, row_norms, query_norms, stream));
     exact_remeasure_params_t p{};
-    p.lanes = lanes;
-    p.lds_bytes = view.chunks * query_chunk_bytes_of(scalar) + 512 + (std::uint32_t)wanted * 8 + 16; // `exact_kernel`'s
+    p.lanes = call.lanes;
+    p.lds_bytes = exact_kernel_lds_bytes(view, call.scalar, wanted);
     p.stream = stream;
     p.queries = query_bytes;
     p.query_stride = stride_bytes;
@@ -307,14 +301,14 @@ const char* exact_search_screened_device(metric_kind_t metric, scalar_kind_t sca
     p.contender_lows = contender_lows;
     p.contender_counts = contender_counts;
     p.bounds = bounds;
-    p.map_keys = map_keys ? 1u : 0u;
+    p.map_keys = call.map_keys ? 1u : 0u;
     p.handed = handed;
-    p.out_distances = distances;
-    p.out_keys = keys;
-    p.out_counts = counts;
+    p.out_distances = call.distances;
+    p.out_keys = call.keys;
+    p.out_counts = call.counts;
     p.remeasured = remeasured;
 #define UA_SCREENED(m, name)                                                                                                           \
-    if (metric == m) {                                                                                                                 \
+    if (call.metric == m) {                                                                                                            \
         UA_HIP(launch_screen<m>(view, query_bytes, stride_bytes, (std::uint32_t)count, (std::uint32_t)wanted, plan, row_norms,         \
                                 query_norms, allow_bits, contender_slots, contender_lows, contender_counts, bounds, handed, stream));  \
         UA_HIP(launch_exact_remeasure_##name(p, view));                                                                                \
@@ -340,14 +334,14 @@ const char* exact_search_screened_device(metric_kind_t metric, scalar_kind_t sca
     const std::size_t listed = list.size(), bytes = view.bytes_per_vector;
     std::uint32_t* d_list = nullptr;
     std::uint8_t* gathered = nullptr;
-    std::uint64_t *wave_keys = nullptr, *wave_counts = nullptr;
-    float* wave_distances = nullptr;
     unsigned long long* allowed = nullptr;
+    float wave_ms = 0.f;
+    exact_call_t wave = call; // the same search of the gathered queries, into lists of their own
     UA_HIP(scratch.allocate(&d_list, listed * 4));
     UA_HIP(scratch.allocate(&gathered, listed * bytes));
-    UA_HIP(scratch.allocate(&wave_keys, listed * wanted * 8));
-    UA_HIP(scratch.allocate(&wave_distances, listed * wanted * 4));
-    UA_HIP(scratch.allocate(&wave_counts, listed * 8));
+    UA_HIP(scratch.allocate(&wave.keys, listed * wanted * 8));
+    UA_HIP(scratch.allocate(&wave.distances, listed * wanted * 4));
+    UA_HIP(scratch.allocate(&wave.counts, listed * 8));
     UA_HIP(scratch.allocate(&allowed, 8));
     UA_HIP(hipMemcpy(d_list, list.data(), listed * 4, hipMemcpyHostToDevice));
     UA_HIP(hipMemsetAsync(allowed, 0, 8, stream));
@@ -358,14 +352,14 @@ const char* exact_search_screened_device(metric_kind_t metric, scalar_kind_t sca
     hipLaunchKernelGGL(count_allowed_kernel, dim3((unsigned)std::min<std::uint64_t>((view.size + 255) / 256, 1u << 16)), dim3(256), 0, stream,
                        view, allow_bits, allowed);
     UA_HIP(hipGetLastError());
-    float wave_ms = 0.f;
-    if (const char* error = exact_search_device(metric, scalar, lanes, view, gathered, listed, bytes, wanted, map_keys, wave_keys,
-                                                wave_distances, wave_counts, stream, kernel_ms ? &wave_ms : nullptr, allow_bits))
+    wave.queries = gathered, wave.count = listed, wave.stride_bytes = bytes;
+    wave.kernel_ms = kernel_ms ? &wave_ms : nullptr;
+    if (const char* error = exact_search_device(wave))
         return error;
     hipLaunchKernelGGL(scatter_results_kernel, dim3((unsigned)std::min<std::uint64_t>((listed * wanted + 255) / 256, 1u << 16)), dim3(256), 0,
-                       stream, (const std::uint32_t*)d_list, (std::uint32_t)listed, (std::uint32_t)wanted, (const std::uint64_t*)wave_keys,
-                       (const float*)wave_distances, (const std::uint64_t*)wave_counts, (const unsigned long long*)allowed, keys, distances,
-                       counts, remeasured);
+                       stream, (const std::uint32_t*)d_list, (std::uint32_t)listed, (std::uint32_t)wanted, (const std::uint64_t*)wave.keys,
+                       (const float*)wave.distances, (const std::uint64_t*)wave.counts, (const unsigned long long*)allowed, call.keys,
+                       call.distances, call.counts, remeasured);
     UA_HIP(hipGetLastError());
     UA_HIP(hipStreamSynchronize(stream));
     if (kernel_ms)

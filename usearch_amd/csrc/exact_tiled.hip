@@ -33,8 +33,8 @@
 
 #include "common.hpp"
 #include "device_math.hpp"
-#include "device_scratch.hpp"
 #include "engine.hpp"
+#include "exact_frame.hpp"
 #include "exact_plan.hpp"
 #include "host_util.hpp"
 #include "wide_stage.hpp"
@@ -1056,25 +1056,16 @@ hipError_t launch_tiled(const snapshot_view_t& view, const std::uint8_t* queries
     return hipGetLastError();
 }
 
-constexpr std::uint32_t norms_blocks_k = 1u << 20; ///< the grid of the Σx² launches at most
-
 } // namespace
 
 bool exact_tiled_available(metric_kind_t metric, scalar_kind_t scalar, std::size_t wanted) {
     return exact_tiled_pair(metric, scalar, wanted) || exact_bits_pair(metric, scalar, wanted); // the tables: exact_plan.hpp
 }
 
-const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar, const snapshot_view_t& view,
-                                      const void* queries, std::size_t count, std::size_t stride_bytes, std::size_t wanted,
-                                      bool map_keys, std::uint64_t* keys, float* distances, std::uint64_t* counts,
-                                      hipStream_t stream, float* kernel_ms, const std::uint32_t* allow_bits) {
-    if (kernel_ms)
-        *kernel_ms = 0.f;
-    if (exact_bits_pair(metric, scalar, wanted)) // b1: the bit tile (exact_bits.hip), same contract
-        return exact_search_bits_device(metric, view, queries, count, stride_bytes, wanted, map_keys, keys, distances, counts, stream,
-                                        kernel_ms, allow_bits);
-    if (!exact_tiled_pair(metric, scalar, wanted))
-        return "No tiled exact-search kernel for this metric / scalar kind / result count";
+const char* exact_search_tiled_device(const exact_call_t& call) {
+    const snapshot_view_t& view = call.view;
+    const std::size_t count = call.count, wanted = call.wanted;
+    hipStream_t stream = call.stream;
     if (!count)
         return nullptr;
     if (count >= none_slot_k || view.size >= none_slot_k)
@@ -1086,18 +1077,11 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
                                          env_size("USEARCH_AMD_EXACT_GLOBAL_LISTS", 0) != 0, plan))
         return refusal;
     const bool wide = plan.wide != 0;
-    const std::uint64_t partitions = plan.partitions, rows_per_partition = plan.rows_per_partition;
 
-    event_pair_t events;
     device_scratch_t scratch(current_device_k); // the caller has selected the device the view lives on
     std::uint32_t *row_norms = nullptr, *query_norms = nullptr;
-    float* partial_distances = nullptr;
-    std::uint64_t *partial_keys = nullptr, *partial_counts = nullptr;
     UA_HIP(scratch.allocate(&row_norms, view.size * 4));
     UA_HIP(scratch.allocate(&query_norms, count * 4));
-    UA_HIP(scratch.allocate(&partial_distances, partitions * count * wanted * 4));
-    UA_HIP(scratch.allocate(&partial_keys, partitions * count * wanted * 8));
-    UA_HIP(scratch.allocate(&partial_counts, partitions * count * 8));
     std::uint8_t* padded_queries = nullptr;
     std::uint32_t* shared_bounds = nullptr;
     if (wide) {
@@ -1107,66 +1091,53 @@ const char* exact_search_tiled_device(metric_kind_t metric, scalar_kind_t scalar
         UA_HIP(scratch.allocate(&shared_bounds, count * 4));
         UA_HIP(hipMemsetAsync(shared_bounds, 0xFF, count * 4, stream));
     }
-    if (kernel_ms) {
-        UA_HIP(events.create());
-        UA_HIP(hipEventRecord(events.begin, stream));
-    }
-    const std::uint8_t* query_bytes = static_cast<const std::uint8_t*>(queries);
-    hipError_t e = hipSuccess;
+    const std::uint8_t* query_bytes = static_cast<const std::uint8_t*>(call.queries);
+    return exact_partitioned(call, plan.partitions, [&](const exact_partials_t& partials) -> const char* {
+        hipError_t e = hipSuccess;
 #define UA_TILED(m, sc)                                                                                                 \
-    if (e == hipSuccess && metric == m && scalar == sc) {                                                              \
-        e = launch_row_norms<sc>(view.vectors, view.size, view.row_stride, view.bytes_per_vector, row_norms,        \
-                                  norms_blocks_k, stream);                                                             \
-        if (e == hipSuccess)                                                                                           \
-            e = launch_row_norms<sc>(query_bytes, count, stride_bytes, view.bytes_per_vector, query_norms,          \
-                                      norms_blocks_k, stream);                                                         \
+    if (e == hipSuccess && call.metric == m && call.scalar == sc) {                                                    \
+        e = launch_exact_norms<sc>(view, query_bytes, count, call.stride_bytes, row_norms, query_norms, stream);       \
         if (e == hipSuccess && wide)                                                                                   \
-            e = launch_wide<m, sc>(view, query_bytes, stride_bytes, padded_queries, (std::uint32_t)count,              \
-                                   (std::uint32_t)wanted, plan, row_norms, query_norms,                                 \
-                                   map_keys, allow_bits, shared_bounds, partial_distances, partial_keys, partial_counts,  \
-                                   stream);                                                                         \
+            e = launch_wide<m, sc>(view, query_bytes, call.stride_bytes, padded_queries, (std::uint32_t)count,         \
+                                   (std::uint32_t)wanted, plan, row_norms, query_norms, call.map_keys, call.allow_bits, \
+                                   shared_bounds, partials.distances, partials.keys, partials.counts, stream);         \
         else if (e == hipSuccess)                                                                                      \
-            e = launch_tiled<m, sc>(view, query_bytes, stride_bytes, (std::uint32_t)count, (std::uint32_t)wanted,      \
-                                    (std::uint32_t)partitions, rows_per_partition, row_norms, query_norms, map_keys,   \
-                                    allow_bits, partial_distances, partial_keys, partial_counts, stream);              \
+            e = launch_tiled<m, sc>(view, query_bytes, call.stride_bytes, (std::uint32_t)count, (std::uint32_t)wanted, \
+                                    (std::uint32_t)plan.partitions, plan.rows_per_partition, row_norms, query_norms,   \
+                                    call.map_keys, call.allow_bits, partials.distances, partials.keys, partials.counts, \
+                                    stream);                                                                           \
     }
-    UA_TILED(metric_cos_k, scalar_f16_k)
-    UA_TILED(metric_ip_k, scalar_f16_k)
-    UA_TILED(metric_cos_k, scalar_bf16_k)
-    UA_TILED(metric_ip_k, scalar_bf16_k)
-    UA_TILED(metric_l2sq_k, scalar_f16_k)
-    UA_TILED(metric_l2sq_k, scalar_bf16_k)
-    UA_TILED(metric_cos_k, scalar_i8_k)
-    UA_TILED(metric_ip_k, scalar_i8_k)
-    UA_TILED(metric_l2sq_k, scalar_i8_k)
-    UA_TILED(metric_cos_k, scalar_f32_k)
-    UA_TILED(metric_ip_k, scalar_f32_k)
-    UA_TILED(metric_cos_k, scalar_f8_k)
-    UA_TILED(metric_ip_k, scalar_f8_k)
-    UA_TILED(metric_l2sq_k, scalar_f8_k)
+        UA_TILED(metric_cos_k, scalar_f16_k)
+        UA_TILED(metric_ip_k, scalar_f16_k)
+        UA_TILED(metric_cos_k, scalar_bf16_k)
+        UA_TILED(metric_ip_k, scalar_bf16_k)
+        UA_TILED(metric_l2sq_k, scalar_f16_k)
+        UA_TILED(metric_l2sq_k, scalar_bf16_k)
+        UA_TILED(metric_cos_k, scalar_i8_k)
+        UA_TILED(metric_ip_k, scalar_i8_k)
+        UA_TILED(metric_l2sq_k, scalar_i8_k)
+        UA_TILED(metric_cos_k, scalar_f32_k)
+        UA_TILED(metric_ip_k, scalar_f32_k)
+        UA_TILED(metric_cos_k, scalar_f8_k)
+        UA_TILED(metric_ip_k, scalar_f8_k)
+        UA_TILED(metric_l2sq_k, scalar_f8_k)
 #undef UA_TILED
-    if (e != hipSuccess)
-        return hip_message(e);
+        if (e != hipSuccess)
+            return hip_message(e);
 #ifdef USEARCH_AMD_EXACT_PHASES
-    if (wide) {
-        unsigned long long ticks[8] = {0};
-        UA_HIP(hipStreamSynchronize(stream));
-        UA_HIP(hipMemcpyFromSymbol(ticks, HIP_SYMBOL(exact_phase_ticks), sizeof(ticks)));
-        const double chunks_done = (double)std::max<unsigned long long>(ticks[4], 1);
-        std::fprintf(stderr, "[usearch_amd] exact phases, shader-clock ticks per chunk (wave 0 of every workgroup): multiply %.0f fold %.0f "
-                             "own fills %.0f barrier %.0f; tiles folded with the thresholds inside the sums %llu, by the general fold %llu\n", ticks[0] / chunks_done, ticks[1] / chunks_done, ticks[2] / chunks_done, ticks[3] / chunks_done, ticks[5], ticks[6]);
-        unsigned long long zeros[8] = {0};
-        UA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(exact_phase_ticks), zeros, sizeof(zeros)));
-    }
+        if (wide) {
+            unsigned long long ticks[8] = {0};
+            UA_HIP(hipStreamSynchronize(stream));
+            UA_HIP(hipMemcpyFromSymbol(ticks, HIP_SYMBOL(exact_phase_ticks), sizeof(ticks)));
+            const double chunks_done = (double)std::max<unsigned long long>(ticks[4], 1);
+            std::fprintf(stderr, "[usearch_amd] exact phases, shader-clock ticks per chunk (wave 0 of every workgroup): multiply %.0f fold %.0f "
+                                 "own fills %.0f barrier %.0f; tiles folded with the thresholds inside the sums %llu, by the general fold %llu\n", ticks[0] / chunks_done, ticks[1] / chunks_done, ticks[2] / chunks_done, ticks[3] / chunks_done, ticks[5], ticks[6]);
+            unsigned long long zeros[8] = {0};
+            UA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(exact_phase_ticks), zeros, sizeof(zeros)));
+        }
 #endif
-    if (kernel_ms)
-        UA_HIP(hipEventRecord(events.end, stream));
-    if (const char* error = merge_shards_device(partial_distances, partial_keys, partial_counts, partitions, count, wanted,
-                                                distances, keys, counts, stream, false))
-        return error;
-    if (kernel_ms)
-        UA_HIP(hipEventElapsedTime(kernel_ms, events.begin, events.end));
-    return nullptr;
+        return nullptr;
+    });
 }
 
 } // namespace usearch_amd

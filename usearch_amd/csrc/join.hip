@@ -304,10 +304,12 @@ const char* join_snapshots(snapshot_t& a, snapshot_t& b, const join_config_t& co
             snapshot_t::lease_t women_lease(women);
             if (const char* e = women_lease.take())
                 return e;
-            if (const char* e = exact_search_device(women.metric(), women.scalar(), women.lanes_per_row(), women.view(), queries, count,
-                                                    men_view.row_stride, width, false, pref_slots + first * width,
-                                                    pref_distances + first * width, pref_counts + first, women_lease.workspace->stream,
-                                                    nullptr))
+            exact_call_t call; // slots out: `map_keys` stays false
+            call.view = women.view(), call.metric = women.metric(), call.scalar = women.scalar(), call.lanes = women.lanes_per_row();
+            call.queries = queries, call.count = count, call.stride_bytes = men_view.row_stride, call.wanted = width;
+            call.keys = pref_slots + first * width, call.distances = pref_distances + first * width, call.counts = pref_counts + first;
+            call.stream = women_lease.workspace->stream;
+            if (const char* e = exact_search_device(call))
                 return e;
             s.computed_distances += count * n_women;
         } else {

@@ -353,6 +353,12 @@ def _pointer(array: Optional[np.ndarray]):
     return C.c_void_p(array.ctypes.data) if array is not None else None
 
 
+def _exact_route(tiled: Union[bool, str]) -> int:
+    """The `tiled` integer of the C ABI's exact-search entries: False → 0, the wave kernel; True or "tiled" → 1, the tiles;
+    "screened" → 2."""
+    return 2 if tiled == "screened" else int(bool(tiled))
+
+
 @dataclass
 class Matches:
     """Results of one query — `usearch.index.Matches` (index.py:303-331)."""
@@ -738,40 +744,25 @@ class Index:
         computed = np.zeros(q, dtype=np.uint64)
         stats = Stats()
         err = C.c_char_p()
-        if exact and filter is not None:  # brute force over the members the filter lets through (index.hpp:4260-4263)
-            # (exact="screened" too, `tiled` = 2 — but the filtered entry has no `remeasured` output: `computed` stays zero here)
+        if exact:  # brute force over every stored vector (Index.search(..., exact=True), index.py:700-748), or over the members the
+            # filter lets through (index.hpp:4260-4263). exact="tiled": the matrix-unit kernel (f16 / bf16 within float tolerance; f32
+            # within a derived bound; i8 bit-identical) or, for b1, the bit tile (hamming / tanimoto / jaccard / sorensen: bit-identical,
+            # NaN included). exact="screened": the matrix units rule rows out, the wave kernel measures the rest: exact=True's bits
+            route = _exact_route(exact if exact in ("tiled", "screened") else False)
             kernel_ms = C.c_float()
-            library().usearch_amd_filtered_exact_search_many(
-                self._handle, filter._handle, _pointer(vectors), SCALAR_KINDS[dtype], q,
-                vectors.shape[1] * vectors.itemsize if q <= 1 else vectors.strides[0], count, _pointer(keys), _pointer(distances),
-                _pointer(counts), 2 if exact == "screened" else int(exact == "tiled"), C.byref(kernel_ms), C.byref(err))
-            _raise(err, "usearch_amd_filtered_exact_search_many")
+            call = (_pointer(vectors), SCALAR_KINDS[dtype], q, vectors.shape[1] * vectors.itemsize if q <= 1 else vectors.strides[0],
+                    count, _pointer(keys), _pointer(distances), _pointer(counts))
+            entry = "usearch_amd_exact_search_many" + ("", "_tiled", "_screened")[route]
+            if filter is not None:  # this entry has no `remeasured` output: `computed` stays zero here, for every route
+                entry, call = "usearch_amd_filtered_exact_search_many", (filter._handle, *call, route, C.byref(kernel_ms))
+            elif route == 2:  # `computed`: rows measured
+                call = (*call, C.byref(kernel_ms), _pointer(computed))
+            else:
+                call = (*call, C.byref(kernel_ms))
+                computed[:] = len(self)
+            getattr(library(), entry)(self._handle, *call, C.byref(err))
+            _raise(err, entry)
             stats.kernel_ms = kernel_ms.value
-            batch = BatchMatches(keys, distances, counts, 0, 0, visited, computed, stats)
-            return batch[0] if single else batch
-        if exact == "screened":  # the matrix units rule rows out, the wave kernel measures the rest: exact=True's bits (exact_screened.hip)
-            kernel_ms = C.c_float()
-            library().usearch_amd_exact_search_many_screened(
-                self._handle, _pointer(vectors), SCALAR_KINDS[dtype], q,
-                vectors.shape[1] * vectors.itemsize if q <= 1 else vectors.strides[0], count, _pointer(keys), _pointer(distances),
-                _pointer(counts), C.byref(kernel_ms), _pointer(computed), C.byref(err))
-            _raise(err, "usearch_amd_exact_search_many_screened")
-            stats.kernel_ms = kernel_ms.value
-            batch = BatchMatches(keys, distances, counts, 0, int(computed.sum()), visited, computed, stats)  # computed: rows measured
-            return batch[0] if single else batch
-        if exact:  # brute force over every stored vector (Index.search(..., exact=True), index.py:700-748)
-            kernel_ms = C.c_float()
-            # exact="tiled": the matrix-unit kernel (f16 / bf16 within float tolerance; f32 within a derived bound; i8 bit-identical)
-            # or, for b1, the bit tile (hamming / tanimoto / jaccard / sorensen: bit-identical, NaN included)
-            entry = (library().usearch_amd_exact_search_many_tiled if exact == "tiled"
-                     else library().usearch_amd_exact_search_many)
-            entry(self._handle, _pointer(vectors), SCALAR_KINDS[dtype], q,
-                                                    vectors.shape[1] * vectors.itemsize if q <= 1 else vectors.strides[0],
-                                                    count, _pointer(keys), _pointer(distances), _pointer(counts),
-                                                    C.byref(kernel_ms), C.byref(err))
-            _raise(err, "usearch_amd_exact_search_many")
-            stats.kernel_ms = kernel_ms.value
-            computed[:] = len(self)
             batch = BatchMatches(keys, distances, counts, 0, int(computed.sum()), visited, computed, stats)
             return batch[0] if single else batch
         ef = self.expansion_search if expansion is None else expansion
@@ -828,7 +819,7 @@ class Index:
         err = C.c_char_p()
         library().usearch_amd_exact_search_many_device(self._handle, C.c_void_p(queries_ptr), queries_count, queries_stride,
                                                        count, C.c_void_p(keys_ptr), C.c_void_p(distances_ptr),
-                                                       C.c_void_p(counts_ptr), C.c_void_p(stream), 2 if tiled == "screened" else int(tiled),
+                                                       C.c_void_p(counts_ptr), C.c_void_p(stream), _exact_route(tiled),
                                                        C.byref(kernel_ms), C.byref(err))
         _raise(err, "usearch_amd_exact_search_many_device")
         return float(kernel_ms.value)
@@ -1133,16 +1124,12 @@ def exact_search(dataset: np.ndarray, queries: np.ndarray, count: int, metric: s
     keys = np.zeros((len(queries), count), dtype=np.uint64)
     distances = np.zeros((len(queries), count), dtype=np.float32)
     err = C.c_char_p()
-    if tiled == "screened":
-        library().usearch_amd_exact_search_dataset_screened(
-            _pointer(dataset), len(dataset), dataset.strides[0], _pointer(queries), len(queries), queries.strides[0], SCALAR_KINDS[dtype],
-            ndim, metric_kind, count, _pointer(keys), keys.strides[0], _pointer(distances), distances.strides[0], None, C.byref(err))
-        _raise(err, "usearch_amd_exact_search_dataset_screened")
-        return keys, distances
-    entry = "usearch_amd_exact_search_dataset_tiled" if tiled else "usearch_amd_exact_search_dataset"
+    route = _exact_route(tiled)
+    entry = "usearch_amd_exact_search_dataset" + ("", "_tiled", "_screened")[route]
     getattr(library(), entry)(_pointer(dataset), len(dataset), dataset.strides[0], _pointer(queries), len(queries),
                               queries.strides[0], SCALAR_KINDS[dtype], ndim, metric_kind, count, _pointer(keys), keys.strides[0],
-                              _pointer(distances), distances.strides[0], C.byref(err))
+                              _pointer(distances), distances.strides[0], *((None,) if route == 2 else ()),  # no `remeasured` wanted
+                              C.byref(err))
     _raise(err, entry)
     return keys, distances
 
